@@ -15,9 +15,20 @@ rank its own --elements stripe instead.  `stages` reports T_enc (all P parties' 
 T_agg (the aggregate alone: decryption factor + combine), P*N/T_enc and N/T_agg.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scheme jl|lom] [--elements 10000000]
-                    [--parties 8] [--weak]
+                    [--parties 8] [--weak] [--dump-outputs DIR] [--full]
 
-At N = 1 the line also carries `end_to_end` (SURVEY 8(f), rank 0 only, outside the headline's clock): the
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the result
+line (metric, value, unit, ms_per_step = the wall milliseconds of one timed step, the configuration).
+`--dump-outputs DIR` then writes what the last timed step returned (the averaged float64 vector the
+step's caller receives) as DIR/aggregate.npy -- the whole vector up to 64 MB, else a fixed seeded
+sample of its elements; the inputs are seeded (fedbiomed_amd/workload.py), so two builds run with the
+same arguments can be compared output for output.
+
+Everything else is measured only with `--full`, after the headline (runs of their own, never inside
+its clock): the per-kernel times and rooflines of one serialised step, `stages`, the LOM legs, the
+N > 1 party-per-rank legs, `end_to_end`, `cpu_baseline`; the `--no-*` switches below trim a full run.
+
+With --full at N = 1 the line also carries `end_to_end` (SURVEY 8(f), rank 0 only, outside the headline's clock): the
 same work from pinned host memory, the reference's list API (one node's encrypt at 1M / 10M, the
 researcher's aggregate at 1M x 8 and at the metric size, JL and LOM list round trips), each also after the
 extensions that issue a call's work ahead (`prepare_encrypt` / `prepare_aggregate`: the factors, the output
@@ -165,6 +176,32 @@ def quiet_clipping_warnings():
     logging.getLogger("fedbiomed_amd").addFilter(Once())
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(folder: str, arrays: dict) -> dict:
+    """Writes each output of the timed path as folder/<name>.npy (float64; float32 stays float32).  All of
+    them together stay within DUMP_LIMIT_BYTES: an output larger than its equal share is written as a sample
+    of its flattened elements at fixed indices (a seeded choice that depends only on the output's size, in
+    ascending order), so two runs with the same arguments write the same positions."""
+    os.makedirs(folder, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    report = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        if a.dtype != np.float32:
+            a = a.astype(np.float64, copy=False)
+        keep = (share - 4096) // a.itemsize  # 4096: room for the .npy header
+        sampled = a.size > keep
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(folder, name + ".npy"), np.ascontiguousarray(a))
+        report[name] = {"file": name + ".npy", "dtype": str(a.dtype), "elements": int(a.size), "sampled": sampled}
+    return report
+
+
 XGMI_LINK_BPS = 153e9  # one xGMI link, one direction (7 per MI355X): the all-gather model of the scaling probe
 
 
@@ -204,6 +241,12 @@ def parse():
                          "gather over RCCL (all_gather_shards) as every rank of an N-GPU run does")
     ap.add_argument("--node-list-n", type=int, nargs="*", default=[1_000_000, 10_000_000],
                     help="elements of the per-node list-API encrypt legs (one party's SecaggCrypter.encrypt)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else (per-kernel times and rooflines, stages, "
+                         "the LOM and party-per-rank legs, the end-to-end legs, the CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (rank 0's) as DIR/aggregate.npy (float64, at most 64 MB: "
+                         "a fixed seeded sample of a larger vector)")
     return ap.parse_args()
 
 
@@ -390,13 +433,14 @@ def main():
 
     # LOM stripes are ChaCha20-block (8-element) aligned: with the JL stripe (ciphertext aligned)
     # as the main workload, the LOM leg takes its own 8-aligned split of the same vector
-    if args.scheme == "jl" and strong and world > 1:
+    lom_extra = args.full and not args.no_lom_extra
+    if args.scheme == "jl" and strong and world > 1 and lom_extra:
         lo_l, hi_l = distributed.shard_range(args.n, world, rank, 8)
         xs_l = [torch.from_numpy(W.party_params(p + 1000 * rank, hi_l - lo_l)).to(dev) for p in range(P)]
     else:
         lo_l, hi_l, xs_l = lo, hi, xs
     Y = (torch.empty((P, hi_l - lo_l), dtype=torch.int64, device=dev)
-         if args.scheme == "lom" or not args.no_lom_extra else None)
+         if args.scheme == "lom" or lom_extra else None)
 
     def step_lom(serial=False):
         # the parties' overflow-guard status words are checked once per step, after the aggregate
@@ -440,8 +484,9 @@ def main():
                 "note": "median of %d: protects, 512 MB scratch write (2x the MALL), then the aggregate alone "
                         "(HIP events on its stream); the warm figure is the aggregate inside the step" % reps}
 
-    def timed(step, steps, warmup, prof=False):
-        """prof=True: serialised launches (one stream) with per-kernel HIP events, so each
+    def timed(step, steps, warmup, prof=False, keep=None):
+        """keep: a list that receives the last timed step's output (--dump-outputs).
+        prof=True: serialised launches (one stream) with per-kernel HIP events, so each
         event pair brackets exactly one kernel's execution (roofline durations).  The event timer
         is the test build's (include/fbm_secagg_test.h): a profiled step runs through it
         (_native.test_hooks: the same kernel objects, the C ABI compiled with the timer), after one
@@ -457,8 +502,11 @@ def main():
             if prof:
                 _native.prof_enable(True)
             t0 = time.perf_counter()
-            for _ in range(steps):
-                step(serial=prof)
+            for i in range(steps):
+                out = step(serial=prof)
+                if keep is not None and i == steps - 1:
+                    keep.append(out)
+                del out
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             if prof:
@@ -473,9 +521,36 @@ def main():
     step = step_jl if args.scheme == "jl" else step_lom
     if args.serial:
         step = (lambda f: (lambda serial=False: f(serial=True)))(step)
-    elapsed, _ = timed(step, args.steps, args.warmup)
+    last = []
+    elapsed, _ = timed(step, args.steps, args.warmup, keep=last if args.dump_outputs else None)
     value = n_total * args.steps / elapsed
     ms_per_step = 1000.0 * elapsed / args.steps
+    n_ct = (n + cr - 1) // cr
+    line = {
+        "metric": "params/s secagg encrypt+aggregate (device-resident), 10M-elem vector @1/8 GPU",
+        "value": value, "unit": "params/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if strong else "weak",
+        "vs_baseline": None, "dtype": "u32-limb bigint (JL) / u64 (LOM); f32 in, f64 out",
+        "data": "synthetic (float32 N(0,0.05^2) + 0.1% +/-4.0 outliers per party; biprime0; random 2040-bit keys)",
+        "config": {"workload": f"{'Joye-Libert' if args.scheme == 'jl' else 'LOM'} encrypt (all {P} parties) + "
+                               f"aggregate, {n:,} elements per GPU", "scheme": args.scheme, "parties": P,
+                   "elements_per_gpu": n, "elements_total": n_total, "ciphertexts_per_party_per_gpu":
+                   n_ct if args.scheme == "jl" else None, "parallelism": f"element-range x{world}"},
+    }
+    if args.dump_outputs and rank == 0:
+        line["outputs"] = dump_outputs(args.dump_outputs, {"aggregate": last.pop()})
+    last.clear()
+
+    def finish():
+        if args.rccl_world1:
+            line["config"]["gather"] = "all_gather_shards over a world-1 RCCL group (--rccl-world1)"
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1 or args.rccl_world1:
+            torch.distributed.destroy_process_group()
+
+    if not args.full:  # a plain run ends here
+        return finish()
     # one extra serialised step for the per-kernel durations (not part of `value`)
     prof_steps = 1
     with GfxClockSampler(local) as clk_s:
@@ -483,7 +558,6 @@ def main():
     clk = clk_s.summary()
 
     # ---- roofline of the dominant kernel, from the live per-kernel HIP events ----
-    n_ct = (n + cr - 1) // cr
     if args.scheme == "jl":
         cnt, ms = kprof.get("jl_exp", (0, 0.0))
         # algorithmic bytes of the launch(es) timed: the P parties' encrypts (4N +
@@ -527,19 +601,8 @@ def main():
         roof["note"] = ("jl_exp_kernel moves ~1e-4 of the HBM roofline's bytes by construction: it is bound by "
                         "integer multiply issue (v_mad_u64_u32), reported in roofline_valu; one launch = every "
                         "party's and the decryption factor's exponentiations (batched)")
-    line = {
-        "metric": "params/s secagg encrypt+aggregate (device-resident), 10M-elem vector @1/8 GPU",
-        "value": value, "unit": "params/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if strong else "weak",
-        "vs_baseline": None, "dtype": "u32-limb bigint (JL) / u64 (LOM); f32 in, f64 out",
-        "data": "synthetic (float32 N(0,0.05^2) + 0.1% +/-4.0 outliers per party; biprime0; random 2040-bit keys)",
-        "config": {"workload": f"{'Joye-Libert' if args.scheme == 'jl' else 'LOM'} encrypt (all {P} parties) + "
-                               f"aggregate, {n:,} elements per GPU", "scheme": args.scheme, "parties": P,
-                   "elements_per_gpu": n, "elements_total": n_total, "ciphertexts_per_party_per_gpu":
-                   n_ct if args.scheme == "jl" else None, "parallelism": f"element-range x{world}"},
-        "roofline": roof,
-        "kernels_ms": {k: {"launches": c, "total_ms": round(t, 3)} for k, (c, t) in sorted(kprof.items())},
-    }
+    line["roofline"] = roof
+    line["kernels_ms"] = {k: {"launches": c, "total_ms": round(t, 3)} for k, (c, t) in sorted(kprof.items())}
     if args.scheme == "jl" and cnt:
         ach = mads / sec / 1e12
         line["roofline_valu"] = {"bound": "int-valu (v_mad_u64_u32)", "achieved": ach, "peak": MAD_PEAK_TOPS,
@@ -682,7 +745,7 @@ def main():
             del cts_all
 
     # ---- secondary: LOM at the same size (cheap), so both schemes are on record ----
-    if args.scheme == "jl" and not args.no_lom_extra:
+    if args.scheme == "jl" and lom_extra:
         k2 = max(args.steps, 10)
         el2, _ = timed(step_lom, k2, 2)  # the step as it runs
         _, kp2 = timed(step_lom, 1, 0, prof=True)  # one instrumented step: per-kernel durations
@@ -704,7 +767,7 @@ def main():
     #      reduce-scatter of the u64 sums over xGMI leaves it the masked total of its stripe; it
     #      averages + dequantises that stripe and all-gathers the float64 stripes.  The output is
     #      checked bit for bit against the element-range LOM leg's gathered vector. ----
-    if args.scheme == "jl" and strong and world > 1 and not args.no_lom_extra and P % world == 0:
+    if args.scheme == "jl" and strong and world > 1 and lom_extra and P % world == 0:
         mine = [p for p in range(P) if p % world == rank]
         bnd = [distributed.shard_range(args.n, world, r, 8) for r in range(world)]
         xs_pp = [torch.from_numpy(np.concatenate([W.party_params(p + 1000 * r, b - a) for r, (a, b) in
@@ -739,7 +802,7 @@ def main():
     #      all-to-all of ciphertext stripes (RCCL over xGMI; the modular product is no RCCL reduction),
     #      the aggregate of its ciphertext stripe at its ct_offset, all-gather of the float64 stripes;
     #      checked bit for bit against the element-range JL step's gathered vector ----
-    if args.scheme == "jl" and strong and world > 1 and not args.no_lom_extra and P % world == 0:
+    if args.scheme == "jl" and strong and world > 1 and lom_extra and P % world == 0:
         ppr = P // world
         mine = list(range(rank * ppr, (rank + 1) * ppr))  # rank-major party blocks
         bnd = [distributed.shard_range(args.n, world, r, cr) for r in range(world)]
@@ -1193,12 +1256,7 @@ def main():
                     "note": f"the reference crypter itself ran {r:.3f}x the oracle's time on this sample in the "
                             "build container (profiles/cpu_calibration.json); it cannot run on the GPU box"}
         line["gpu_over_cpu"] = value / (ns / tc)
-    if args.rccl_world1:
-        line["config"]["gather"] = "all_gather_shards over a world-1 RCCL group (--rccl-world1)"
-    if rank == 0:
-        print(json.dumps(line))
-    if world > 1 or args.rccl_world1:
-        torch.distributed.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

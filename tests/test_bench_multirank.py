@@ -14,7 +14,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--elements", "300000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-e2e"]
+# --full: the party-per-rank legs and the per-stage times are not part of a plain run
+SMALL = ["--full", "--elements", "300000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-e2e"]
 
 
 def _bench(args, timeout=110):

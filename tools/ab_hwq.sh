@@ -8,7 +8,7 @@ mkdir -p $O
 cd $R
 for q in 4 8 16 4 8 16; do
   for n in 1250010 10000000; do
-    GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python -u bench.py --elements $n --steps 3 --warmup 1 --no-cpu-baseline --no-lom-extra --no-e2e --no-stages > $O/q${q}_n${n}.json 2> $O/q${q}_n${n}.err || exit 1
+    GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python -u bench.py --full --elements $n --steps 3 --warmup 1 --no-cpu-baseline --no-lom-extra --no-e2e --no-stages > $O/q${q}_n${n}.json 2> $O/q${q}_n${n}.err || exit 1
     python3 -c "import json,sys; d=json.loads(open('$O/q${q}_n${n}.json').read().strip().splitlines()[-1]); print('q=$q n=$n', round(d['ms_per_step'],2), 'ms/step', round(d['value']/1e6,3), 'M/s')"
   done
 done

@@ -60,34 +60,34 @@ run_step() {
     timeout -k 10 300 $PY -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
     local rc=$?; tail -1 $O/smoke.txt; return $rc ;;
   bench)
-    timeout -k 10 600 $PY bench.py > $O/bench.json 2> $O/bench.err
+    timeout -k 10 600 $PY bench.py --full > $O/bench.json 2> $O/bench.err
     local rc=$?; tail -c 600 $O/bench.json; echo; return $rc ;;
   jlprof)
     mkdir -p $O/jl
     (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-      -d $O/jl/prof -o run -- python3 $R/bench.py $JLARGS > $O/jl/prof_bench.json 2> $O/jl/prof.err) ;;
+      -d $O/jl/prof -o run -- python3 $R/bench.py --full $JLARGS > $O/jl/prof_bench.json 2> $O/jl/prof.err) ;;
   jlpmc)
     mkdir -p $O/jl
     (cd /tmp && export TMPDIR=/tmp &&
       timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/jl/pmc_fetch -o run -- \
-        python3 $R/bench.py $JLARGS > /dev/null 2> $O/jl/pmc_fetch.err &&
+        python3 $R/bench.py --full $JLARGS > /dev/null 2> $O/jl/pmc_fetch.err &&
       timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/jl/pmc_write -o run -- \
-        python3 $R/bench.py $JLARGS > /dev/null 2> $O/jl/pmc_write.err) ;;
+        python3 $R/bench.py --full $JLARGS > /dev/null 2> $O/jl/pmc_write.err) ;;
   lompmc)
     mkdir -p $O/lom
     (cd /tmp && export TMPDIR=/tmp &&
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/lom/prof -o run -- \
-        python3 $R/bench.py $LOMARGS > $O/lom/prof_bench.json 2> $O/lom/prof.err &&
+        python3 $R/bench.py --full $LOMARGS > $O/lom/prof_bench.json 2> $O/lom/prof.err &&
       timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/lom/pmc_fetch -o run -- \
-        python3 $R/bench.py $LOMARGS > /dev/null 2> $O/lom/pmc_fetch.err &&
+        python3 $R/bench.py --full $LOMARGS > /dev/null 2> $O/lom/pmc_fetch.err &&
       timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/lom/pmc_write -o run -- \
-        python3 $R/bench.py $LOMARGS > /dev/null 2> $O/lom/pmc_write.err)
+        python3 $R/bench.py --full $LOMARGS > /dev/null 2> $O/lom/pmc_write.err)
     local rc=$?; tail -c 800 $O/lom/prof_bench.json; echo; return $rc ;;
   dist8|dist8full)
     local a="--elements 2000000 --steps 2 --warmup 1"
     [ $s = dist8full ] && a="--elements 10000000 --steps 20 --warmup 5"
     local t0=$(date +%s)
-    timeout -k 10 900 $PY bench.py --gpus 8 --dist-backend gloo $a > $O/$s.json 2> $O/$s.err
+    timeout -k 10 900 $PY bench.py --full --gpus 8 --dist-backend gloo $a > $O/$s.json 2> $O/$s.err
     local rc=$?
     echo "{\"step\": \"$s\", \"rc\": $rc, \"wall_s\": $(( $(date +%s) - t0 )), \"lines\": $(wc -l < $O/$s.json)}" \
       > $O/$s.meta.json
@@ -97,7 +97,7 @@ run_step() {
   dist8run)
     local t0=$(date +%s)
     timeout -k 10 900 $PY -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-      --master-port 29533 bench.py --gpus 8 --dist-backend gloo --elements 2000000 --steps 2 --warmup 1 \
+      --master-port 29533 bench.py --full --gpus 8 --dist-backend gloo --elements 2000000 --steps 2 --warmup 1 \
       > $O/$s.json 2> $O/$s.err
     local rc=$?
     echo "{\"step\": \"$s\", \"rc\": $rc, \"wall_s\": $(( $(date +%s) - t0 )), \"json_lines\": $(grep -c '^{' $O/$s.json)}" \

@@ -8,8 +8,8 @@ timeout -k 10 300 python -u -m pytest $R/tests/test_gpu_parity.py $R/tests/test_
 cd /tmp && export TMPDIR=/tmp
 A="--steps 1 --warmup 0 --serial --no-cpu-baseline --no-lom-extra --no-e2e --no-stages"
 for n in 10000000 1250010; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -o run -- python3 $R/bench.py $A --elements $n > $O/bench_$n.json 2> $O/kt_$n.err || exit 1
-  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch_$n -o run -- python3 $R/bench.py $A --elements $n > /dev/null 2> $O/fetch_$n.err || exit 1
-  timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write_$n -o run -- python3 $R/bench.py $A --elements $n > /dev/null 2> $O/write_$n.err || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -o run -- python3 $R/bench.py --full $A --elements $n > $O/bench_$n.json 2> $O/kt_$n.err || exit 1
+  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch_$n -o run -- python3 $R/bench.py --full $A --elements $n > /dev/null 2> $O/fetch_$n.err || exit 1
+  timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write_$n -o run -- python3 $R/bench.py --full $A --elements $n > /dev/null 2> $O/write_$n.err || exit 1
 done
 echo done

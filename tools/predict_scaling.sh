@@ -8,7 +8,7 @@ O=$R/gpurun_out/${1:-predict}
 mkdir -p $O
 cd $R
 for n in 10000000 5000010 2500020 1250010; do
-  timeout -k 10 240 python -u bench.py --elements $n --steps 5 --warmup 1 --no-cpu-baseline --no-lom-extra --no-e2e \
+  timeout -k 10 240 python -u bench.py --full --elements $n --steps 5 --warmup 1 --no-cpu-baseline --no-lom-extra --no-e2e \
     > $O/bench_$n.json 2> $O/bench_$n.err || exit $?
 done
 python3 - "$O" <<'PY'

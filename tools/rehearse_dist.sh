@@ -7,7 +7,7 @@ O=$R/gpurun_out/${1:-dist}
 mkdir -p $O
 cd $R
 for g in 2 4; do
-  timeout -k 10 300 python -u bench.py --gpus $g --dist-backend gloo --elements 2000000 --steps 2 --warmup 1 \
+  timeout -k 10 300 python -u bench.py --full --gpus $g --dist-backend gloo --elements 2000000 --steps 2 --warmup 1 \
     > $O/dist$g.json 2> $O/dist$g.err || { rc=$?; echo "gpus=$g rc=$rc"; tail -c 1500 $O/dist$g.err; exit $rc; }
   tail -c 300 $O/dist$g.json; echo
 done
