@@ -142,6 +142,7 @@ TEST_SIGNATURES = {
     "fbm_test_modinv": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "fbm_test_nadic_consts": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "fbm_test_short_consts": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "fbm_test_schedule": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "fbm_test_short_cache": (c_int, [c_vp, c_int]),
     "fbm_test_fdh_gcd": (c_int, [c_vp, c_vp, c_vp]),
     "fbm_test_gen_exp": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),

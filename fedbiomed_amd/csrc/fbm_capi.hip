@@ -2288,6 +2288,20 @@ int fbm_test_short_consts(const uint32_t* n32, const uint32_t* key, uint32_t* kw
   return q ? sc.sbits : -2;
 }
 
+int fbm_test_schedule(const uint32_t* key64, uint16_t* ops512, int* n_ops, int* first) {
+  if (!key64 || !ops512 || !n_ops || !first) {
+    set_error("fbm_test_schedule: null pointer");
+    return FBM_E_ARG;
+  }
+  JlSched sc;
+  int is_zero = 0;
+  const int rc = build_schedule(key64, sc, is_zero);
+  memcpy(ops512, sc.op, sizeof(sc.op));
+  *n_ops = sc.n_ops;
+  *first = sc.first;
+  return rc ? rc : (is_zero ? 1 : FBM_OK);
+}
+
 int fbm_test_modinv(const uint32_t* x, const uint32_t* n, uint32_t* out, int* batches) {
   if (!x || !n || !out || !(n[0] & 1u)) {
     set_error("fbm_test_modinv: null pointer or even modulus");

@@ -83,6 +83,13 @@ int fbm_test_nadic_consts(const uint32_t* n32, uint32_t* nk, uint32_t* r2na, uin
  * mod N^2), d: 36 limbs of N - 2^261.  Returns s = bit length of |key| - 1 (-1 for a zero key), or
  * -2 when N is outside the path's domain (N <= 2^262 or even). */
 int fbm_test_short_consts(const uint32_t* n32, const uint32_t* key, uint32_t* kw, uint32_t* corr, uint32_t* d);
+/* host test hook (no GPU): the table path's sliding-window schedule of |key| (64 words) as the library
+ * builds it (build_schedule) -- ops512: FBM_MAX_OPS = 512 u16 ops, op k = (squarings before the multiply)
+ * << 6 | (table index + 1, 0 = no multiply), the first *n_ops of them valid; *first: the table index of
+ * the leading window.  Replayed, e = 2 first + 1, then per op e <<= nsq, e += 2 idx + 1, gives |key|.
+ * Returns build_schedule's status (FBM_OK, or FBM_E_ARG where the ops would pass FBM_MAX_OPS), or 1
+ * for a zero key (is_zero: no schedule, *n_ops = *first = 0). */
+int fbm_test_schedule(const uint32_t* key64, uint16_t* ops512, int* n_ops, int* first);
 /* host test hook (no GPU): the raw words of the short path's cache entries (each: an 8-word digest
  * and 72 limbs of C); returns the word count (out == NULL: a size query), FBM_E_ARG if cap_words is
  * too small. */
