@@ -308,6 +308,13 @@ int fbm_ves_unpack(const uint32_t* pt, uint64_t n_ct, int pw, int es, int cr, ui
  *   elem_offset  global index of secret[0] (element-range shards draw disjoint streams)
  * The reference's MT19937 stream is not reproduced: the contract is sum == v exactly and the
  * share ranges.
+ * Counter layout (a tested contract: tests/test_ass_draws.py holds the kernel to a model of it,
+ * oracle/secagg_oracle.py ass_share_draws).  The stream is ChaCha20(seed) with a 64-bit block
+ * counter in state words 12-13 and the nonce in words 14-15.  Element i of a call owns the
+ * ceil((n_shares - 1) / 4) blocks from (elem_offset + i) * ceil((n_shares - 1) / 4); its share s
+ * (s < n_shares - 1) is drawn from the four words 4 (s & 3) .. 4 (s & 3) + 3 of block s >> 2 of
+ * those, read as one 128-bit little-endian x: share = floor(x (2^b + 1) / 2^128).  No two draws
+ * of a call, or of calls over disjoint element ranges, read the same word.
  * fbm_ass_reconstruct replaces AdditiveShares.reconstruct (:252-267): exact int128 column sum.
  */
 int fbm_ass_split(const void* secret, int secret_dtype, uint64_t n, int n_shares, int bit_length,
@@ -321,6 +328,11 @@ int fbm_ass_reconstruct(const int64_t* shares, int n_shares, uint64_t n, int64_t
  *   secret  device, l_in x n words;  shares device, n_shares x l_out x n words, where
  *   l_out >= words of (b + ceil(log2 n_shares) + 2) bits (the caller sizes it; b <= 32*l_in
  *   when bit_length < 0);  bit_length >= 0 overrides the per-element |v| bit length.
+ * Counter layout (tested as above, ass_share_draws_wide): every draw owns
+ *   blocks = ceil((bmax + 64) / 512) ChaCha20 blocks, bmax = bit_length, or 32 * l_in when
+ *   bit_length < 0; share s (s < n_shares - 1) of element i starts at block
+ *   ((elem_offset + i) * (n_shares - 1) + s) * blocks.  x = the first b + 64 bits of that stream
+ *   (little-endian words, the last one masked), share = floor(x (2^b + 1) / 2^(b + 64)).
  * fbm_ass_reconstruct_wide: out (l x n words) = column sum mod 2^(32 l) of n_shares
  *   l-limb values -- exact when the caller's l holds the true sum. */
 int fbm_ass_split_wide(const uint32_t* secret, uint64_t n, int l_in, int n_shares, int bit_length, int l_out,

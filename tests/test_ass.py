@@ -2,8 +2,11 @@
 
 Contract: split shares sum exactly to the secret and the first n-1 lie in [0, 2**bit_length]
 (bit_length = the secret's bit length unless given); reconstruct is an exact column sum -- checked
-against the reference's own shares in tests/golden/ass.json.  An int secret's shares are the
-reference's own MT19937 draws (seeded as the fixture was made); a vector's come from ChaCha20.
+against the reference's own shares in tests/golden/ass.json.  By default every secret, an int (a
+node's JL key at setup) or a vector, draws its shares from the device's OS-keyed ChaCha20; only
+reference_rng=True draws the reference's own MT19937 stream (seeded as the fixtures were made), and
+that path is the one the fixtures pin value for value.  The default draws are pinned, share for
+share, to a model of the kernels' counter layout in tests/test_ass_draws.py.
 """
 
 import numpy as np
