@@ -227,9 +227,35 @@ def _x_dtype(x: torch.Tensor) -> int:
         return N.FBM_F32
     if x.dtype == torch.float64:
         return N.FBM_F64
+    if x.dtype == torch.float16:
+        return N.FBM_F16
+    if x.dtype == torch.bfloat16:
+        return N.FBM_BF16
     if x.dtype in (torch.int64, torch.uint64):
         return N.FBM_U64
     raise FedbiomedSecaggCrypterError(f"{ErrorNumbers.FB624.value}: unsupported input dtype {x.dtype}")
+
+
+_OUT_DTYPES = {torch.float64: N.FBM_F64, torch.float32: N.FBM_F32, torch.float16: N.FBM_F16,
+               torch.bfloat16: N.FBM_BF16}
+
+
+def _out_tensor(n: int, dev, out_dtype: Optional[torch.dtype], out: Optional[torch.Tensor]) -> Tuple[torch.Tensor, int]:
+    """The aggregate's destination and its FBM dtype code: `out` (a 1-D contiguous tensor of n elements on
+    `dev`, e.g. a slice of a flat parameter buffer in the model's dtype; its dtype is the output dtype) or a
+    new tensor of `out_dtype` (None: float64).  ValueError for an `out` of another shape, device, layout or
+    of a dtype that disagrees with an explicit `out_dtype`."""
+    if out is not None:
+        if out.dim() != 1 or out.numel() != n or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous 1-D tensor of {n} elements on {dev}, got "
+                             f"{tuple(out.shape)} on {out.device}")
+        if out_dtype is not None and out.dtype != out_dtype:
+            raise ValueError(f"out is {out.dtype} but out_dtype is {out_dtype}")
+        out_dtype = out.dtype
+    dt = torch.float64 if out_dtype is None else out_dtype
+    if dt not in _OUT_DTYPES:
+        raise ValueError(f"unsupported output dtype {dt}: float64, float32, float16 or bfloat16")
+    return (out if out is not None else torch.empty(n, dtype=dt, device=dev)), _OUT_DTYPES[dt]
 
 
 # ------------------------------------------------------------------------------------------
@@ -620,7 +646,9 @@ def _nonce_block(nonce: bytes) -> np.ndarray:
 def lom_protect(x: torch.Tensor, secrets: Sequence[bytes], signs: Sequence[int], nonce: bytes, tau: int,
                 n_nodes: int, clip=None, target=None, weight: int = 1, raw_seeds: bool = False,
                 elem_offset: int = 0, out: Optional[torch.Tensor] = None, check_now: bool = False) -> torch.Tensor:
-    """One party's masked vector (u64 bit patterns in an int64 tensor); raises the
+    """One party's masked vector (u64 bit patterns in an int64 tensor) of a float16 / bfloat16 / float32 /
+    float64 tensor x (quantised; a 16-bit element counts as its exact value, so the result is that of
+    x.double()) or an int64 one (integers as they are); raises the
     reference's LOM overflow error when max(bit_length(q*w)) >= 64 - ceil(log2(n_nodes)).
     check_now: check the status word before returning even inside `deferred_checks`."""
     dev = x.device
@@ -769,8 +797,11 @@ def prf_key(secret: bytes, nonce: bytes, tau: int, dev=None) -> bytes:
 
 
 def lom_aggregate(Y: torch.Tensor, total_weight: int, clip=None, target=None,
-                  want_out: bool = True, want_sums: bool = False):
-    """Column sum (mod 2^64) + average + dequantise of a [P, n] int64 (u64) tensor."""
+                  want_out: bool = True, want_sums: bool = False, out_dtype: Optional[torch.dtype] = None,
+                  out: Optional[torch.Tensor] = None):
+    """Column sum (mod 2^64) + average + dequantise of a [P, n] int64 (u64) tensor.
+    `out_dtype`: float64 (None, the default), float32, float16 or bfloat16 -- written by the kernel, bit for
+    bit the float64 result's `.to(out_dtype)`; `out`: the destination (see _out_tensor), returned."""
     dev = Y.device
     lib = N.load()
     target = target or SAParameters.TARGET_RANGE
@@ -782,21 +813,28 @@ def lom_aggregate(Y: torch.Tensor, total_weight: int, clip=None, target=None,
     negc, step = dequant_params(clip, target)
     Y = Y.contiguous()
     P, n = Y.shape
-    out = torch.empty(n, dtype=torch.float64, device=dev) if want_out else None
+    out, odt = _out_tensor(n, dev, out_dtype, out) if want_out else (None, N.FBM_F64)
     sums = torch.empty(n, dtype=torch.int64, device=dev) if want_sums else None
     st = _stats(dev)
-    _call(lib.fbm_lom_aggregate, _ptr(Y), P, n, int(total_weight), negc, step, _ptr(out), _ptr(sums), _ptr(st),
-          _stream())
+    if odt == N.FBM_F64:
+        _call(lib.fbm_lom_aggregate, _ptr(Y), P, n, int(total_weight), negc, step, _ptr(out), _ptr(sums), _ptr(st),
+              _stream())
+    else:
+        _call(lib.fbm_lom_aggregate_as, _ptr(Y), P, n, int(total_weight), negc, step, _ptr(out), odt, _ptr(sums),
+              _ptr(st), _stream())
     _check_stats_or_defer(st)  # (inside deferred_checks: at its exit, e.g. the list aggregate's, after the D2H)
     return out, sums
 
 
-def dequantize(u: torch.Tensor, clip=None, target=None) -> torch.Tensor:
+def dequantize(u: torch.Tensor, clip=None, target=None, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     target = target or SAParameters.TARGET_RANGE
     negc, step = dequant_params(clip, target)
     u = u.contiguous()
-    out = torch.empty(u.numel(), dtype=torch.float64, device=u.device)
-    _call(N.load().fbm_dequantize, _ptr(u), u.numel(), negc, step, _ptr(out), _stream())
+    out, odt = _out_tensor(u.numel(), u.device, out_dtype, None)
+    if odt == N.FBM_F64:
+        _call(N.load().fbm_dequantize, _ptr(u), u.numel(), negc, step, _ptr(out), _stream())
+    else:
+        _call(N.load().fbm_dequantize_as, _ptr(u), u.numel(), negc, step, _ptr(out), odt, _stream())
     return out
 
 
@@ -1044,7 +1082,8 @@ def jl_encrypt(x: torch.Tensor, biprime: int, key: int, tau: int, n_users: int, 
                weight: int = 1, slot: Optional[Tuple[int, int]] = None, ct_offset: int = 0,
                defer_exp: bool = False, kind: Optional[str] = None, out: Optional[torch.Tensor] = None,
                factor: Optional[torch.Tensor] = None):
-    """One party's JL ciphertexts as an int32 [n_ct, 64] tensor of 32-bit limbs.
+    """One party's JL ciphertexts as an int32 [n_ct, 64] tensor of 32-bit limbs, of a float16 / bfloat16 /
+    float32 / float64 tensor x (quantised; a 16-bit element counts as its exact value) or an int64 one.
     `factor`: this party's H(t_k)^key for these ciphertexts computed ahead (jl_decrypt_factor with the
     party's key, round and ct_offset): the encrypt is then (N pt + 1) F mod N^2 (fbm_jl_encrypt_factor),
     bit for bit the exponentiation's; odd N >= 3 only.
@@ -1192,9 +1231,11 @@ def jl_decrypt_factor(n_ct: int, biprime: int, key: int, tau: int, ct_offset: in
 
 def jl_aggregate(cts: torch.Tensor, biprime: int, key: int, tau: int, n_expected: int, total_weight: int,
                  clip=None, target=None, want_out: bool = True, want_sums: bool = False,
-                 slot: Optional[Tuple[int, int]] = None, ct_offset: int = 0, factor: Optional[torch.Tensor] = None):
+                 slot: Optional[Tuple[int, int]] = None, ct_offset: int = 0, factor: Optional[torch.Tensor] = None,
+                 out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None):
     """Aggregate [P, n_ct, 64] int32 ciphertext limbs -> (float64 [n_out], int64 [n_out, 2] sums).
-    `factor`: the round's precomputed jl_decrypt_factor (same key, tau, ct range), or None."""
+    `factor`: the round's precomputed jl_decrypt_factor (same key, tau, ct range), or None.
+    `out_dtype` / `out`: as lom_aggregate's."""
     dev = cts.device
     lib = N.load()
     target = target or SAParameters.TARGET_RANGE
@@ -1208,7 +1249,7 @@ def jl_aggregate(cts: torch.Tensor, biprime: int, key: int, tau: int, n_expected
         raise FedbiomedSecaggCrypterError(
             f"{ErrorNumbers.FB624.value}: total_sample_size must be in [1, 2^64) for the device path")
     tl = _check_round(tau) if factor is None else None  # a given factor fixes the round already
-    out = torch.empty(n_out, dtype=torch.float64, device=dev) if want_out else None
+    out, odt = _out_tensor(n_out, dev, out_dtype, out) if want_out else (None, N.FBM_F64)
     sums = torch.empty((n_out, 2), dtype=torch.int64, device=dev) if want_sums else None
     if n_ct == 0:
         return out, sums
@@ -1229,12 +1270,19 @@ def jl_aggregate(cts: torch.Tensor, biprime: int, key: int, tau: int, n_expected
             break
         st = _stats(dev)
         o, sm = _ptr(out[e0:e1] if want_out else None), _ptr(sums[e0:e1] if want_sums else None)
-        if factor is None:
+        if factor is None and odt == N.FBM_F64:
             _call(lib.fbm_jl_aggregate, _ptr(part), P, k1 - k0, es, cr, e1 - e0, _np_ptr(bp), _np_ptr(kl), kneg,
                   _np_ptr(tl), int(ct_offset) + k0, int(total_weight), negc, step, o, sm, _ptr(ws), _ptr(st), _stream())
-        else:
+        elif factor is None:
+            _call(lib.fbm_jl_aggregate_as, _ptr(part), P, k1 - k0, es, cr, e1 - e0, _np_ptr(bp), _np_ptr(kl), kneg,
+                  _np_ptr(tl), int(ct_offset) + k0, int(total_weight), negc, step, o, odt, sm, _ptr(ws), _ptr(st),
+                  _stream())
+        elif odt == N.FBM_F64:
             _call(lib.fbm_jl_aggregate_factor, _ptr(part), P, k1 - k0, es, cr, e1 - e0, _np_ptr(bp),
                   _ptr(factor[k0:k1]), int(total_weight), negc, step, o, sm, _ptr(ws), _ptr(st), _stream())
+        else:
+            _call(lib.fbm_jl_aggregate_factor_as, _ptr(part), P, k1 - k0, es, cr, e1 - e0, _np_ptr(bp),
+                  _ptr(factor[k0:k1]), int(total_weight), negc, step, o, odt, sm, _ptr(ws), _ptr(st), _stream())
         _check_stats_or_defer(st)  # (inside deferred_checks: at its exit, e.g. the list aggregate's stripes)
     return out, sums
 

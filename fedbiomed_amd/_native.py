@@ -61,6 +61,8 @@ FBM_U64 = 2
 FBM_I64 = 3
 FBM_U128 = 4
 FBM_PT = 5
+FBM_F16 = 6  # IEEE binary16 (an input dtype, and an output dtype of the *_as entry points)
+FBM_BF16 = 7
 STATS_WORDS = 4
 
 _lock = threading.Lock()
@@ -90,6 +92,13 @@ SIGNATURES = {
     "fbm_prf_key": (c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
     "fbm_dequantize": (c_int, [c_vp, c_u64, c_dbl, c_dbl, c_vp, c_vp]),
     "fbm_lom_aggregate": (c_int, [c_vp, c_int, c_u64, c_u64, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp]),
+    # the *_as entry points: `double* out` of their namesakes as `void* out, int out_dtype`
+    "fbm_dequantize_as": (c_int, [c_vp, c_u64, c_dbl, c_dbl, c_vp, c_int, c_vp]),
+    "fbm_lom_aggregate_as": (c_int, [c_vp, c_int, c_u64, c_u64, c_dbl, c_dbl, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "fbm_jl_aggregate_as": (c_int, [c_vp, c_int, c_u64, c_int, c_int, c_u64, c_vp, c_vp, c_int, c_vp, c_u64, c_u64,
+                                    c_dbl, c_dbl, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "fbm_jl_aggregate_factor_as": (c_int, [c_vp, c_int, c_u64, c_int, c_int, c_u64, c_vp, c_vp, c_u64, c_dbl, c_dbl,
+                                           c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     # host-buffer LOM calls, synchronous (ABI 6)
     "fbm_lom_host_workspace": (c_u64, [c_u64, c_int]),
     "fbm_lom_protect_host": (c_int, [c_vp, c_int, c_u64, c_dbl, c_dbl, c_dbl, c_u64, c_u64, c_vp, c_vp, c_int,
@@ -139,6 +148,8 @@ TEST_SIGNATURES = {
     "fbm_jl_set_short": (c_int, [c_int]),
     "fbm_jl_engine_for": (c_int, [c_u64]),
     "fbm_test_true_div_big": (c_int, [c_vp, c_u64, c_vp, c_int, c_int, c_vp]),
+    "fbm_test_widen16": (c_int, [ctypes.c_uint16, c_int, c_vp]),
+    "fbm_test_narrow": (c_int, [c_dbl, c_int, c_vp]),
     "fbm_test_modinv": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "fbm_test_nadic_consts": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "fbm_test_short_consts": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -1067,6 +1067,17 @@ int fbm_check_stats(const uint32_t* st, int lom_nodes, uint32_t* max_bits_out) {
   return FBM_OK;
 }
 
+// the element types that are quantised (inputs) and that an *_as entry point writes (outputs)
+static bool float_dtype(int dtype) {
+  return dtype == FBM_F32 || dtype == FBM_F64 || dtype == FBM_F16 || dtype == FBM_BF16;
+}
+
+static int check_out_dtype(int out_dtype) {
+  if (float_dtype(out_dtype)) return FBM_OK;
+  set_error("out_dtype=%d must be FBM_F64, FBM_F32, FBM_F16 or FBM_BF16", out_dtype);
+  return FBM_E_ARG;
+}
+
 int fbm_lom_protect(const void* x, int x_dtype, uint64_t n, double clip, double two_clip, double target_f,
                     uint64_t target_m1, uint64_t weight, const uint8_t* secrets, const int8_t* signs, int n_peers,
                     int raw_seeds, const uint8_t* nonce, uint64_t tau, uint64_t elem_offset, uint64_t* y,
@@ -1076,8 +1087,8 @@ int fbm_lom_protect(const void* x, int x_dtype, uint64_t n, double clip, double 
   if (rc) return rc;
   QuantParams qp;
   if ((rc = quant_params(clip, two_clip, target_f, target_m1, qp))) return rc;
-  if (x_dtype != FBM_F32 && x_dtype != FBM_F64 && x_dtype != FBM_U64) {
-    set_error("x_dtype must be FBM_F32, FBM_F64 or FBM_U64");
+  if (!float_dtype(x_dtype) && x_dtype != FBM_U64) {
+    set_error("x_dtype must be FBM_F16, FBM_BF16, FBM_F32, FBM_F64 or FBM_U64");
     return FBM_E_ARG;
   }
   if (n_peers < 0) {
@@ -1137,25 +1148,38 @@ int fbm_prf_key(const uint8_t* secret, const uint8_t* nonce, uint64_t tau, uint8
   return launch_prf_key(pe, (uint32_t*)seed_out, (hipStream_t)stream);
 }
 
-int fbm_dequantize(const uint64_t* u, uint64_t n, double neg_clip, double step, double* out, void* stream) {
+int fbm_dequantize_as(const uint64_t* u, uint64_t n, double neg_clip, double step, void* out, int out_dtype,
+                      void* stream) {
+  int rc = check_out_dtype(out_dtype);
+  if (rc) return rc;
   if (n > 0 && (!u || !out)) {
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
-  return launch_dequantize(u, n, neg_clip, step, out, (hipStream_t)stream);
+  return launch_dequantize(u, n, neg_clip, step, out, out_dtype, (hipStream_t)stream);
+}
+
+int fbm_dequantize(const uint64_t* u, uint64_t n, double neg_clip, double step, double* out, void* stream) {
+  return fbm_dequantize_as(u, n, neg_clip, step, out, FBM_F64, stream);
 }
 
 int fbm_lom_aggregate(const uint64_t* y, int n_parties, uint64_t n, uint64_t total_weight, double neg_clip,
                       double step, double* out, uint64_t* sums, uint32_t* stats, void* stream) {
+  return fbm_lom_aggregate_as(y, n_parties, n, total_weight, neg_clip, step, out, FBM_F64, sums, stats, stream);
+}
+
+int fbm_lom_aggregate_as(const uint64_t* y, int n_parties, uint64_t n, uint64_t total_weight, double neg_clip,
+                         double step, void* out, int out_dtype, uint64_t* sums, uint32_t* stats, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  int rc = zero_stats(stats, s);
+  int rc = check_out_dtype(out_dtype);  // (first: an argument error that needs no device)
   if (rc) return rc;
+  if ((rc = zero_stats(stats, s))) return rc;
   if (n_parties < 1 || total_weight == 0 || (n > 0 && !y)) {
     set_error("invalid aggregate arguments (n_parties=%d, total_weight=%llu)", n_parties,
               (unsigned long long)total_weight);
     return FBM_E_ARG;
   }
-  return timed("lom_aggregate", s, [&] { return launch_lom_aggregate(y, n_parties, n, total_weight, neg_clip, step, out, sums, stats, s); });
+  return timed("lom_aggregate", s, [&] { return launch_lom_aggregate(y, n_parties, n, total_weight, neg_clip, step, out, out_dtype, sums, stats, s); });
 }
 
 // ---- host-buffer LOM calls (small vectors): copy in, kernel, copy out, one stream synchronisation ----
@@ -1205,15 +1229,15 @@ int fbm_lom_protect_host(const void* x_host, int x_dtype, uint64_t n, double cli
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
-  if (x_dtype != FBM_F32 && x_dtype != FBM_F64 && x_dtype != FBM_U64) {
-    set_error("x_dtype must be FBM_F32, FBM_F64 or FBM_U64");
+  if (!float_dtype(x_dtype) && x_dtype != FBM_U64) {
+    set_error("x_dtype must be FBM_F16, FBM_BF16, FBM_F32, FBM_F64 or FBM_U64");
     return FBM_E_ARG;
   }
   uint8_t* w = (uint8_t*)workspace;
   void* x = w;
   uint64_t* y = (uint64_t*)(w + align256(n * 8));
   uint32_t* st = (uint32_t*)(w + align256(n * 8) + n * 8);
-  const uint64_t xb = n * (x_dtype == FBM_F32 ? 4u : 8u);
+  const uint64_t xb = n * (x_dtype == FBM_F16 || x_dtype == FBM_BF16 ? 2u : x_dtype == FBM_F32 ? 4u : 8u);
   int rc = host_copy(x, x_host, xb, hipMemcpyHostToDevice, s, "x");
   if (!rc) rc = fbm_lom_protect(x, x_dtype, n, clip, two_clip, target_f, target_m1, weight, secrets, signs, n_peers,
                                 raw_seeds, nonce, tau, elem_offset, y, st, stream);
@@ -1285,8 +1309,8 @@ static int jl_encrypt_impl(const void* x, int x_dtype, uint64_t n, double clip, 
   if ((phase & 1) && (rc = zero_stats(stats, s))) return rc;
   QuantParams qp;
   if ((rc = quant_params(clip, two_clip, target_f, target_m1, qp))) return rc;
-  if (x_dtype != FBM_F32 && x_dtype != FBM_F64 && x_dtype != FBM_U64 && x_dtype != FBM_U128 && x_dtype != FBM_PT) {
-    set_error("x_dtype must be FBM_F32, FBM_F64, FBM_U64, FBM_U128 or FBM_PT");
+  if (!float_dtype(x_dtype) && x_dtype != FBM_U64 && x_dtype != FBM_U128 && x_dtype != FBM_PT) {
+    set_error("x_dtype must be FBM_F16, FBM_BF16, FBM_F32, FBM_F64, FBM_U64, FBM_U128 or FBM_PT");
     return FBM_E_ARG;
   }
   if ((x_dtype == FBM_U128 || x_dtype == FBM_PT) && weight != 1) {
@@ -1435,8 +1459,8 @@ int fbm_jl_encrypt_factor(const void* x, int x_dtype, uint64_t n, double clip, d
   if (rc) return rc;
   QuantParams qp;
   if ((rc = quant_params(clip, two_clip, target_f, target_m1, qp))) return rc;
-  if (x_dtype != FBM_F32 && x_dtype != FBM_F64 && x_dtype != FBM_U64 && x_dtype != FBM_U128 && x_dtype != FBM_PT) {
-    set_error("x_dtype must be FBM_F32, FBM_F64, FBM_U64, FBM_U128 or FBM_PT");
+  if (!float_dtype(x_dtype) && x_dtype != FBM_U64 && x_dtype != FBM_U128 && x_dtype != FBM_PT) {
+    set_error("x_dtype must be FBM_F16, FBM_BF16, FBM_F32, FBM_F64, FBM_U64, FBM_U128 or FBM_PT");
     return FBM_E_ARG;
   }
   if ((x_dtype == FBM_U128 || x_dtype == FBM_PT) && weight != 1) {
@@ -1616,8 +1640,8 @@ static int jl_factor_impl(uint64_t n_ct, const uint32_t* biprime, const uint32_t
 // x_raw != NULL: ServerKey.decrypt's x to x_raw [n_ct][32] instead of decode/average/dequantise
 static int jl_combine_impl(const uint32_t* cts, int n_parties, uint64_t n_ct, int es, int cr, uint64_t n_out,
                            const uint32_t* biprime, const uint32_t* factor, uint64_t total_weight, double neg_clip,
-                           double step, double* out, uint64_t* sums, const JlAggWs& w, uint32_t* stats, hipStream_t s,
-                           uint32_t* x_raw = nullptr) {
+                           double step, void* out, int out_dtype, uint64_t* sums, const JlAggWs& w, uint32_t* stats,
+                           hipStream_t s, uint32_t* x_raw = nullptr) {
   JlParams jp;
   int rc;
   if (jl_is_one(biprime)) {  // the reference's invert(delta^2, N^2) has no nonzero result modulo 1
@@ -1638,7 +1662,7 @@ static int jl_combine_impl(const uint32_t* cts, int n_parties, uint64_t n_ct, in
       return rc;
     if (x_raw) return FBM_OK;
     return timed("jl_decode", s, [&] {
-      return launch_jl_decode(w.xs, es, cr, n_out, total_weight, neg_clip, step, out, sums, stats, s);
+      return launch_jl_decode(w.xs, es, cr, n_out, total_weight, neg_clip, step, out, out_dtype, sums, stats, s);
     });
   }
   if ((rc = build_jl_params(biprime, es, cr, nullptr, 0, jp))) return rc;
@@ -1655,7 +1679,7 @@ static int jl_combine_impl(const uint32_t* cts, int n_parties, uint64_t n_ct, in
     return rc;
   if (x_raw) return FBM_OK;
   return timed("jl_decode", s, [&] {
-    return launch_jl_decode(w.xs, es, cr, n_out, total_weight, neg_clip, step, out, sums, stats, s);
+    return launch_jl_decode(w.xs, es, cr, n_out, total_weight, neg_clip, step, out, out_dtype, sums, stats, s);
   });
 }
 
@@ -1676,9 +1700,18 @@ int fbm_jl_aggregate(const uint32_t* cts, int n_parties, uint64_t n_ct, int es, 
                      const uint32_t* biprime, const uint32_t* key, int key_negative, const uint32_t* tau, uint64_t ct_offset,
                      uint64_t total_weight, double neg_clip, double step, double* out, uint64_t* sums,
                      void* workspace, uint32_t* stats, void* stream) {
+  return fbm_jl_aggregate_as(cts, n_parties, n_ct, es, cr, n_out, biprime, key, key_negative, tau, ct_offset,
+                             total_weight, neg_clip, step, out, FBM_F64, sums, workspace, stats, stream);
+}
+
+int fbm_jl_aggregate_as(const uint32_t* cts, int n_parties, uint64_t n_ct, int es, int cr, uint64_t n_out,
+                        const uint32_t* biprime, const uint32_t* key, int key_negative, const uint32_t* tau,
+                        uint64_t ct_offset, uint64_t total_weight, double neg_clip, double step, void* out,
+                        int out_dtype, uint64_t* sums, void* workspace, uint32_t* stats, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  int rc = zero_stats(stats, s);
+  int rc = check_out_dtype(out_dtype);  // (first: an argument error that needs no device)
   if (rc) return rc;
+  if ((rc = zero_stats(stats, s))) return rc;
   if ((rc = jl_agg_checks(n_parties, n_ct, biprime, total_weight))) return rc;
   if (!key) {
     set_error("null key");
@@ -1692,8 +1725,8 @@ int fbm_jl_aggregate(const uint32_t* cts, int n_parties, uint64_t n_ct, int es, 
   }
   const JlAggWs w = agg_ws(workspace, n_ct);
   if ((rc = jl_factor_impl(n_ct, biprime, key, key_negative, tau, ct_offset, w.F, w, stats, s))) return rc;
-  return jl_combine_impl(cts, n_parties, n_ct, es, cr, n_out, biprime, w.F, total_weight, neg_clip, step, out, sums, w,
-                         stats, s);
+  return jl_combine_impl(cts, n_parties, n_ct, es, cr, n_out, biprime, w.F, total_weight, neg_clip, step, out, out_dtype,
+                         sums, w, stats, s);
 }
 
 int fbm_jl_decrypt_factor(uint64_t n_ct, const uint32_t* biprime, const uint32_t* key, int key_negative, const uint32_t* tau,
@@ -1733,9 +1766,18 @@ int fbm_jl_decrypt_factor_phase(uint64_t n_ct, const uint32_t* biprime, const ui
 int fbm_jl_aggregate_factor(const uint32_t* cts, int n_parties, uint64_t n_ct, int es, int cr, uint64_t n_out,
                             const uint32_t* biprime, const uint32_t* factor, uint64_t total_weight, double neg_clip,
                             double step, double* out, uint64_t* sums, void* workspace, uint32_t* stats, void* stream) {
+  return fbm_jl_aggregate_factor_as(cts, n_parties, n_ct, es, cr, n_out, biprime, factor, total_weight, neg_clip, step,
+                                    out, FBM_F64, sums, workspace, stats, stream);
+}
+
+int fbm_jl_aggregate_factor_as(const uint32_t* cts, int n_parties, uint64_t n_ct, int es, int cr, uint64_t n_out,
+                               const uint32_t* biprime, const uint32_t* factor, uint64_t total_weight, double neg_clip,
+                               double step, void* out, int out_dtype, uint64_t* sums, void* workspace, uint32_t* stats,
+                               void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  int rc = zero_stats(stats, s);
+  int rc = check_out_dtype(out_dtype);  // (first: an argument error that needs no device)
   if (rc) return rc;
+  if ((rc = zero_stats(stats, s))) return rc;
   if ((rc = jl_agg_checks(n_parties, n_ct, biprime, total_weight))) return rc;
   if (n_ct == 0) return FBM_OK;
   if (n_out > n_ct * (uint64_t)cr) n_out = n_ct * (uint64_t)cr;
@@ -1743,8 +1785,8 @@ int fbm_jl_aggregate_factor(const uint32_t* cts, int n_parties, uint64_t n_ct, i
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
-  return jl_combine_impl(cts, n_parties, n_ct, es, cr, n_out, biprime, factor, total_weight, neg_clip, step, out, sums,
-                         agg_ws(workspace, n_ct), stats, s);
+  return jl_combine_impl(cts, n_parties, n_ct, es, cr, n_out, biprime, factor, total_weight, neg_clip, step, out,
+                         out_dtype, sums, agg_ws(workspace, n_ct), stats, s);
 }
 
 // ---- the JoyeLibert object API (fedbiomed_amd/secagg/_jls.py) ----
@@ -1782,7 +1824,7 @@ int fbm_jl_unpack(const uint32_t* pt, uint64_t n_ct, int es, int cr, uint64_t n_
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
-  return timed("jl_decode", s, [&] { return launch_jl_decode(pt, es, cr, n_out, 1, 0.0, 1.0, nullptr, vals, nullptr, s); });
+  return timed("jl_decode", s, [&] { return launch_jl_decode(pt, es, cr, n_out, 1, 0.0, 1.0, nullptr, FBM_F64, vals, nullptr, s); });
 }
 
 int fbm_jl_fdh(uint64_t n_ct, const uint32_t* modulus_odd, int modulus_even, const uint32_t* tau, uint64_t ct_offset,
@@ -1917,7 +1959,8 @@ int fbm_jl_decrypt(const uint32_t* cts, int n_parties, uint64_t n_ct, const uint
   }
   const JlAggWs w = agg_ws(workspace, n_ct);
   if ((rc = jl_factor_impl(n_ct, biprime, key, key_negative, tau, ct_offset, w.F, w, stats, s))) return rc;
-  return jl_combine_impl(cts, n_parties, n_ct, 1, 1, 0, biprime, w.F, 1, 0.0, 1.0, nullptr, nullptr, w, stats, s, x);
+  return jl_combine_impl(cts, n_parties, n_ct, 1, 1, 0, biprime, w.F, 1, 0.0, 1.0, nullptr, FBM_F64, nullptr, w, stats, s,
+                         x);
 }
 
 // out[k] = nude_k * h[k]^key mod N^2 for caller-given bases (a PublicParam whose hashing function
@@ -1997,7 +2040,7 @@ int fbm_jl_decrypt_with(const uint32_t* cts, int n_parties, uint64_t n_ct, const
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
-  return jl_combine_impl(cts, n_parties, n_ct, 1, 1, 0, biprime, factor, 1, 0.0, 1.0, nullptr, nullptr,
+  return jl_combine_impl(cts, n_parties, n_ct, 1, 1, 0, biprime, factor, 1, 0.0, 1.0, nullptr, FBM_F64, nullptr,
                          agg_ws(workspace, n_ct), stats, s, x);
 }
 
@@ -2218,6 +2261,31 @@ int fbm_test_true_div_big(const uint64_t* x, uint64_t n, const uint32_t* k, int 
     return FBM_E_ARG;
   }
   host_true_div_big(x, n, k, k_words, negative, out);
+  return FBM_OK;
+}
+
+int fbm_test_widen16(uint16_t bits, int dtype, double* out) {
+  if (!out || (dtype != FBM_F16 && dtype != FBM_BF16)) {
+    set_error("fbm_test_widen16: dtype must be FBM_F16 or FBM_BF16, out not NULL");
+    return FBM_E_ARG;
+  }
+  if (dtype == FBM_F16) {
+    const fbm_f16 h{bits};
+    *out = fbm_widen(h);
+  } else {
+    const fbm_bf16 h{bits};
+    *out = fbm_widen(h);
+  }
+  return FBM_OK;
+}
+
+int fbm_test_narrow(double v, int dtype, uint32_t* bits_out) {
+  if (!bits_out || (dtype != FBM_F32 && dtype != FBM_F16 && dtype != FBM_BF16)) {
+    set_error("fbm_test_narrow: dtype must be FBM_F32, FBM_F16 or FBM_BF16, bits_out not NULL");
+    return FBM_E_ARG;
+  }
+  *bits_out = dtype == FBM_F32 ? fbm_out<float>::bits(v)
+                               : dtype == FBM_F16 ? (uint32_t)fbm_out<fbm_f16>::bits(v) : (uint32_t)fbm_out<fbm_bf16>::bits(v);
   return FBM_OK;
 }
 

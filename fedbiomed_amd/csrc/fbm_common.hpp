@@ -103,6 +103,121 @@ FBM_HD double fbm_dequantize(double v, double neg_c, double step) {
 }
 
 // ------------------------------------------------------------------------------------
+// 16-bit inputs and narrow outputs (FBM_F16 / FBM_BF16, the *_as entry points)
+// ------------------------------------------------------------------------------------
+// Integer bit operations only, so that the host (the test build's fbm_test_widen16 / fbm_test_narrow)
+// and the device run the same source, whatever either one's denormal mode is.
+//
+// Widening is exact: the reference takes List[float], so a 16-bit parameter reaches its quantiser as the
+// Python float of that value -- subnormals, signed zeros and infinities as they are, a NaN as a NaN.
+// Narrowing is round-to-nearest-even, float64 -> float32 first and the 16-bit types from that float32:
+// the two roundings of `aggregate_tensor(...).to(dtype)` on a float64 result, which is what the fused
+// output must equal bit for bit (1 + 2^-8 + 2^-40 becomes bf16 1.0, where one rounding gives 1.0078125).
+struct fbm_f16 { uint16_t bits; };   // IEEE binary16
+struct fbm_bf16 { uint16_t bits; };  // the upper half of a float32
+
+FBM_HD double fbm_f64_from_bits(uint64_t b) { return __builtin_bit_cast(double, b); }
+FBM_HD uint64_t fbm_f64_bits(double v) { return __builtin_bit_cast(uint64_t, v); }
+
+// Both 16-bit formats have at most 10 significand bits, so the low word of the double is zero and the
+// high word is made with 32-bit operations: sign | exponent << 20 | significand.  A subnormal (binary16
+// below 2^-14; bfloat16 below 2^-126, the float32 denormals: none is flushed) is a normal double: its
+// leading one moves to the hidden-bit position and the exponent drops by as much.
+FBM_HD double fbm_widen16(uint32_t bits, int ebits) {
+  const int mbits = 15 - ebits;                      // 10 (binary16: 5 exponent bits), 7 (bfloat16: 8)
+  const uint32_t emax = (1u << ebits) - 1u, bias = emax >> 1;
+  const uint32_t sign = (bits & 0x8000u) << 16;
+  const uint32_t e = (bits >> mbits) & emax;
+  uint32_t m = bits & ((1u << mbits) - 1u);
+  uint32_t hi;
+  if (e == emax) {
+    hi = 0x7ff00000u | (m << (20 - mbits));           // inf; a NaN keeps its payload
+  } else if (e != 0) {
+    hi = ((e + 1023u - bias) << 20) | (m << (20 - mbits));
+  } else if (m == 0) {
+    hi = 0;
+  } else {
+    const int sh = __builtin_clz(m) - (31 - mbits);  // 1 <= sh <= mbits
+    m = (m << sh) & ((1u << mbits) - 1u);
+    hi = ((1023u - bias + 1u - (uint32_t)sh) << 20) | (m << (20 - mbits));
+  }
+  return fbm_f64_from_bits((uint64_t)(sign | hi) << 32);
+}
+FBM_HD double fbm_widen(fbm_f16 h) { return fbm_widen16(h.bits, 5); }
+FBM_HD double fbm_widen(fbm_bf16 h) { return fbm_widen16(h.bits, 8); }
+FBM_HD double fbm_widen(float x) { return (double)x; }
+FBM_HD double fbm_widen(double x) { return x; }
+
+// q + 1 when the dropped bits `rem` (of `bits` bits) round q up under round-half-even
+FBM_HD uint32_t fbm_rne(uint32_t q, uint64_t rem, int bits) {
+  const uint64_t half = 1ull << (bits - 1);
+  return q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u);
+}
+
+// RN-even float32 of a double, as bits.  A carry out of the significand runs into the exponent field,
+// which is the next binade (or the infinity past FLT_MAX) in this encoding; NaN stays NaN (quiet).
+FBM_HD uint32_t fbm_f64_to_f32_bits(double v) {
+  const uint64_t b = fbm_f64_bits(v);
+  const uint32_t sign = (uint32_t)(b >> 32) & 0x80000000u;
+  const int e = (int)((b >> 52) & 0x7ffu);
+  const uint64_t m = b & 0xfffffffffffffull;
+  if (e == 0x7ff) return sign | 0x7f800000u | (m ? 0x400000u | (uint32_t)(m >> 29) : 0u);
+  const int ef = e - 1023 + 127;
+  if (ef >= 0xff) return sign | 0x7f800000u;
+  if (ef > 0) return sign | fbm_rne(((uint32_t)ef << 23) | (uint32_t)(m >> 29), m & 0x1fffffffull, 29);
+  if (ef < -24) return sign;  // below half the smallest denormal (and every double zero / subnormal)
+  const int sh = 30 - ef;     // float32 denormal: units of 2^-149 (30 <= sh <= 54)
+  const uint64_t full = m | (1ull << 52);
+  return sign | fbm_rne((uint32_t)(full >> sh), full & ((1ull << sh) - 1ull), sh);
+}
+
+FBM_HD uint16_t fbm_f32_bits_to_bf16(uint32_t f) {
+  if ((f & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((f >> 16) | 0x40u);  // NaN, quiet
+  return (uint16_t)((f + 0x7fffu + ((f >> 16) & 1u)) >> 16);
+}
+
+FBM_HD uint16_t fbm_f32_bits_to_f16(uint32_t f) {
+  const uint32_t sign = (f >> 16) & 0x8000u;
+  const int e = (int)((f >> 23) & 0xffu);
+  const uint32_t m = f & 0x7fffffu;
+  if (e == 0xff) return (uint16_t)(sign | 0x7c00u | (m ? 0x200u | (m >> 13) : 0u));
+  const int eh = e - 127 + 15;
+  if (eh >= 0x1f) return (uint16_t)(sign | 0x7c00u);
+  if (eh > 0) return (uint16_t)(sign | fbm_rne(((uint32_t)eh << 10) | (m >> 13), m & 0x1fffu, 13));
+  if (eh < -10) return (uint16_t)sign;  // below half the smallest subnormal (and every float32 denormal)
+  const int sh = 14 - eh;               // binary16 subnormal: units of 2^-24 (14 <= sh <= 24)
+  const uint32_t full = m | 0x800000u;
+  return (uint16_t)(sign | fbm_rne(full >> sh, full & ((1u << sh) - 1u), sh));
+}
+
+// An output element type OT of the *_as entry points: the integer word stored for it and the rounding
+// of the float64 result v to it (double: v itself).
+template <typename OT> struct fbm_out;
+template <> struct fbm_out<double> {
+  typedef uint64_t word;
+  static FBM_HD word bits(double v) { return fbm_f64_bits(v); }
+};
+template <> struct fbm_out<float> {
+  typedef uint32_t word;
+  static FBM_HD word bits(double v) { return fbm_f64_to_f32_bits(v); }
+};
+template <> struct fbm_out<fbm_f16> {
+  typedef uint16_t word;
+  static FBM_HD word bits(double v) { return fbm_f32_bits_to_f16(fbm_f64_to_f32_bits(v)); }
+};
+template <> struct fbm_out<fbm_bf16> {
+  typedef uint16_t word;
+  static FBM_HD word bits(double v) { return fbm_f32_bits_to_bf16(fbm_f64_to_f32_bits(v)); }
+};
+
+template <typename OT>
+FBM_HD void fbm_store_as(OT* p, double v) {
+  *reinterpret_cast<typename fbm_out<OT>::word*>(p) = fbm_out<OT>::bits(v);
+}
+template <>
+FBM_HD void fbm_store_as<double>(double* p, double v) { *p = v; }
+
+// ------------------------------------------------------------------------------------
 // ChaCha20 block (RFC 7539 rounds; OpenSSL's 16-byte IV = 64-bit LE counter || 8 B nonce)
 // ------------------------------------------------------------------------------------
 FBM_HD uint32_t fbm_rotl(uint32_t v, int n) { return (v << n) | (v >> (32 - n)); }

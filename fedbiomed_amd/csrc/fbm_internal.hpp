@@ -49,12 +49,14 @@ void set_error(const char* fmt, ...);
 int launch_lom_protect(const void* x, int x_dtype, uint64_t n, const QuantParams& qp, uint64_t weight,
                        const LomPeers& peers, uint64_t* y, uint32_t* stats, hipStream_t s);
 int launch_lom_mask_accumulate(uint64_t n, const LomPeers& peers, uint64_t* y, hipStream_t s);
-int launch_dequantize(const uint64_t* u, uint64_t n, double neg_c, double step, double* out, hipStream_t s);
+// out_dtype of the output launchers: FBM_F64 / FBM_F32 / FBM_F16 / FBM_BF16 (the C ABI checks it)
+int launch_dequantize(const uint64_t* u, uint64_t n, double neg_c, double step, void* out, int out_dtype,
+                      hipStream_t s);
 int launch_prf_key(const LomPeers& peers, uint32_t* seed_out, hipStream_t s);
 // the aggregate kernel's name (test build: fbm_test_lom_aggregate_kernel)
 int lom_aggregate_kernel_name(int n_parties, uint64_t n, const void* y, char* buf, int len);
 int launch_lom_aggregate(const uint64_t* y, int n_parties, uint64_t n, uint64_t total_weight, double neg_c,
-                         double step, double* out, uint64_t* sums, uint32_t* stats, hipStream_t s);
+                         double step, void* out, int out_dtype, uint64_t* sums, uint32_t* stats, hipStream_t s);
 
 // ---- Joye-Libert -------------------------------------------------------------------
 // exponent schedule (host-computed sliding window, uniform across lanes)
@@ -256,7 +258,7 @@ int host_gcd_is_one_r8(const uint32_t* r8, const uint32_t* n32, uint32_t* err);
 int launch_jl_inv(uint64_t n_ct, const JlParams& jp, const uint32_t* cst, const uint32_t* Ed, uint32_t* Y,
                   const uint32_t* nude, uint32_t* out, uint32_t* stats, hipStream_t s);
 int launch_jl_decode(const uint32_t* xs, int es, int cr, uint64_t n_out, uint64_t total_weight, double neg_c,
-                     double step, double* out, uint64_t* sums, uint32_t* stats, hipStream_t s);
+                     double step, void* out, int out_dtype, uint64_t* sums, uint32_t* stats, hipStream_t s);
 
 // ---- the generic JL engine (fbm_gen.hip): any biprime N, even ones included ------------
 // Constants of one (N, key), host-built (fbm_capi.hip build_gen_ctx), copied into the call's

@@ -40,10 +40,12 @@ namespace fbm {
 // ------------------------------------------------------------------------------------
 // pack: one work-item per 32-bit limb of a packed plaintext
 // ------------------------------------------------------------------------------------
-// XT = float/double: quantise (crypter path);  XT = uint64_t: raw integers (JoyeLibert.protect)
+// XT = float/double/fbm_f16/fbm_bf16: quantise (crypter path);  XT = uint64_t: raw integers
+// (JoyeLibert.protect).  The 16-bit types take the generic template's element loads: this launch is
+// dwarfed by the exponentiation behind it, so it has no 16-byte load path as lom_protect_kernel's.
 template <typename XT>
 __device__ __forceinline__ uint64_t jl_input(const XT* x, uint64_t i, const QuantParams& qp, bool& clipped) {
-  const double v = (double)x[i];
+  const double v = fbm_widen(x[i]);
   clipped |= fbm_outside_clip(v, qp);
   return fbm_quantize(v, qp);
 }
@@ -2028,9 +2030,11 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_lift_kernel(uint64_t n_ct, Jl
 // ------------------------------------------------------------------------------------
 // decode + average + dequantise: one work-item per output element
 // ------------------------------------------------------------------------------------
+// OT: the output element (fbm_out<OT> rounds the float64 result to it)
+template <typename OT>
 __global__ void __launch_bounds__(256) jl_decode_kernel(const uint32_t* __restrict__ xs, int es, int cr,
                                                         uint64_t n_out, uint64_t total_weight, double neg_c,
-                                                        double step, double* __restrict__ out,
+                                                        double step, OT* __restrict__ out,
                                                         uint64_t* __restrict__ sums, uint32_t* __restrict__ stats) {
   const uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= n_out) return;
@@ -2060,10 +2064,10 @@ __global__ void __launch_bounds__(256) jl_decode_kernel(const uint32_t* __restri
   const double a = fbm_true_div_u128(v, total_weight);
   if (a >= 18446744073709551616.0) {  // reverse_quantize guard (only when dequantising)
     atomicOr(stats + FBM_STAT_ERRFLAGS, FBM_ERR_DEQUANT_RANGE);
-    out[o] = 0.0;
+    fbm_store_as(out + o, 0.0);
     return;
   }
-  out[o] = fbm_dequantize(a, neg_c, step);
+  fbm_store_as(out + o, fbm_dequantize(a, neg_c, step));
 }
 
 // ------------------------------------------------------------------------------------
@@ -2104,6 +2108,12 @@ int launch_jl_pack(const void* x, int x_dtype, uint64_t n, const QuantParams& qp
                        es, cr, n_ct, pt, stats);
   else if (x_dtype == FBM_F64)
     hipLaunchKernelGGL(jl_pack_kernel<double>, grid1(n_ct * 32, 256), dim3(256), 0, s, (const double*)x, n, qp,
+                       weight, es, cr, n_ct, pt, stats);
+  else if (x_dtype == FBM_F16)
+    hipLaunchKernelGGL(jl_pack_kernel<fbm_f16>, grid1(n_ct * 32, 256), dim3(256), 0, s, (const fbm_f16*)x, n, qp,
+                       weight, es, cr, n_ct, pt, stats);
+  else if (x_dtype == FBM_BF16)
+    hipLaunchKernelGGL(jl_pack_kernel<fbm_bf16>, grid1(n_ct * 32, 256), dim3(256), 0, s, (const fbm_bf16*)x, n, qp,
                        weight, es, cr, n_ct, pt, stats);
   else if (x_dtype == FBM_U128)
     hipLaunchKernelGGL(jl_pack_wide_kernel, grid1(n_ct * 32, 256), dim3(256), 0, s, (const uint64_t*)x, n, es, cr,
@@ -2511,10 +2521,26 @@ int host_gcd_is_one_r8(const uint32_t* r8, const uint32_t* n32, uint32_t* err) {
 }
 
 int launch_jl_decode(const uint32_t* xs, int es, int cr, uint64_t n_out, uint64_t total_weight, double neg_c,
-                     double step, double* out, uint64_t* sums, uint32_t* stats, hipStream_t s) {
+                     double step, void* out, int out_dtype, uint64_t* sums, uint32_t* stats, hipStream_t s) {
   if (n_out == 0) return FBM_OK;
-  hipLaunchKernelGGL(jl_decode_kernel, grid1(n_out, 256), dim3(256), 0, s, xs, es, cr, n_out, total_weight, neg_c,
-                     step, out, sums, stats);
+  const dim3 grid = grid1(n_out, 256), block(256);
+  switch (out_dtype) {
+    case FBM_F32:
+      hipLaunchKernelGGL(jl_decode_kernel<float>, grid, block, 0, s, xs, es, cr, n_out, total_weight, neg_c, step,
+                         (float*)out, sums, stats);
+      break;
+    case FBM_F16:
+      hipLaunchKernelGGL(jl_decode_kernel<fbm_f16>, grid, block, 0, s, xs, es, cr, n_out, total_weight, neg_c, step,
+                         (fbm_f16*)out, sums, stats);
+      break;
+    case FBM_BF16:
+      hipLaunchKernelGGL(jl_decode_kernel<fbm_bf16>, grid, block, 0, s, xs, es, cr, n_out, total_weight, neg_c, step,
+                         (fbm_bf16*)out, sums, stats);
+      break;
+    default:
+      hipLaunchKernelGGL(jl_decode_kernel<double>, grid, block, 0, s, xs, es, cr, n_out, total_weight, neg_c, step,
+                         (double*)out, sums, stats);
+  }
   return check_launch("jl_decode_kernel");
 }
 

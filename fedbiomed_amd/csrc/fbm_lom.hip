@@ -8,9 +8,11 @@
 //                        + _apply_average (secagg/_secagg_crypter.py:233-249)
 //                        + reverse_quantize (utils/_secagg_utils.py:152-187)
 //
-// Layout in HBM: x (f32 or f64, n), y (u64, n) per party; aggregate input is a
-// P x n row-major u64 matrix (party-major) -> out f64 n (+ optional u64 sums).
+// Layout in HBM: x (f16, bf16, f32 or f64, n), y (u64, n) per party; aggregate input is a
+// P x n row-major u64 matrix (party-major) -> out n of f64 (or f32 / f16 / bf16: the *_as entry
+// points) (+ optional u64 sums).
 #include <cstdio>
+#include <type_traits>
 
 #include "fbm_internal.hpp"
 
@@ -20,11 +22,20 @@ namespace fbm {
 // peer).  Peers are looped inside (uniform control flow); their 32-byte secrets arrive
 // as kernel arguments and their per-round seeds (eval_key, one ChaCha20 block each) are
 // derived once per workgroup into LDS.
-// XT = float/double: quantise + weight (crypter path); XT = uint64_t: raw integer input
-// (LOM.protect on a list of ints), x == nullptr means an all-zero input.
+// XT = float/double/fbm_f16/fbm_bf16: quantise + weight (crypter path); XT = uint64_t: raw integer
+// input (LOM.protect on a list of ints), x == nullptr means an all-zero input.
 template <typename XT>
 __device__ __forceinline__ uint64_t lom_input(const XT* x, uint64_t i, const QuantParams& qp, bool& clipped) {
   const double v = (double)x[i];
+  clipped |= fbm_outside_clip(v, qp);
+  return fbm_quantize(v, qp);
+}
+// a 16-bit element already in a register (lom_protect_kernel loads a block's eight at once)
+template <typename XT>
+__device__ __forceinline__ uint64_t lom_input16(uint32_t bits, const QuantParams& qp, bool& clipped) {
+  XT h;
+  h.bits = (uint16_t)bits;
+  const double v = fbm_widen(h);
   clipped |= fbm_outside_clip(v, qp);
   return fbm_quantize(v, qp);
 }
@@ -99,12 +110,27 @@ __global__ void __launch_bounds__(256, 8) lom_protect_kernel(const XT* __restric
       }
     }
 
+    // 16-bit inputs: a block is 16 bytes -- one load when it is full and x + base is 16-byte aligned
+    // (the compiler does not merge 16-bit scalar loads), element loads for a caller's slice that is
+    // only 2-byte aligned and for the partial last block
+    uint4 h = make_uint4(0u, 0u, 0u, 0u);
+    bool whole = false;
+    if constexpr (sizeof(XT) == 2) {
+      whole = cnt == 8 && (reinterpret_cast<uintptr_t>(x + base) & 15u) == 0;
+      if (whole) h = *reinterpret_cast<const uint4*>(x + base);
+    }
+
     // quantise + weight
     uint64_t val[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       uint64_t q = 0;
-      if (j < cnt) q = lom_input<XT>(x, base + j, qp, clipped);
+      if constexpr (sizeof(XT) == 2) {
+        const uint32_t hw = j < 2 ? h.x : j < 4 ? h.y : j < 6 ? h.z : h.w;
+        if (j < cnt) q = lom_input16<XT>(whole ? hw >> (16 * (j & 1)) : (uint32_t)x[base + j].bits, qp, clipped);
+      } else {
+        if (j < cnt) q = lom_input<XT>(x, base + j, qp, clipped);
+      }
       const uint64_t lo = q * weight;
       const uint64_t hi = __umul64hi(q, weight);
       val[j] = lo;
@@ -212,16 +238,31 @@ __device__ __forceinline__ double lom_avg_dequant(uint64_t s, uint64_t total_wei
   return fbm_dequantize(a >= 18446744073709551616.0 ? 0.0 : a, neg_c, step);
 }
 
-template <int EPT, int PC>
+// The output element type of the aggregate kernels is an OPTIONAL trailing template argument: none is
+// float64, so that the float64 kernels keep their names ("lom_aggregate_kernel<2, 8>",
+// "lom_aggregate_ws_kernel<2, 4, 8>": committed profiles and the bench's traffic lookup are keyed on them)
+// and their code (the ws kernels instruction for instruction; lom_aggregate_kernel gained the destination's
+// alignment in its `vec` test); float, fbm_f16 or fbm_bf16 (the *_as entry points) has fbm_out<OT> round the
+// float64 result to it.
+template <typename... OTS> struct agg_out { typedef double type; };
+template <typename T> struct agg_out<T> { typedef T type; };
+
+template <int EPT, int PC, typename... OTS>
 __global__ void __launch_bounds__(256) lom_aggregate_kernel(const uint64_t* __restrict__ y, int n_parties,
                                                             uint64_t n, uint64_t total_weight, double neg_c,
-                                                            double step, double* __restrict__ out,
+                                                            double step,
+                                                            typename agg_out<OTS...>::type* __restrict__ out,
                                                             uint64_t* __restrict__ sums, uint32_t* __restrict__ stats) {
+  typedef typename agg_out<OTS...>::type OT;
   const int P = PC > 0 ? PC : n_parties;
   const uint64_t ngrp = (n + EPT - 1) / EPT;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   // rows start (EPT*8)-byte aligned only when n is a multiple of EPT (and y is aligned)
-  const bool vec = (n % EPT) == 0 && (reinterpret_cast<uintptr_t>(y) % (EPT * 8)) == 0;
+  // -- and a thread's EPT outputs go out as one store only where the destination is aligned for it (a
+  // caller's `out` may start at any element): element loads and stores otherwise
+  const bool vec = (n % EPT) == 0 && (reinterpret_cast<uintptr_t>(y) % (EPT * 8)) == 0 &&
+                   (reinterpret_cast<uintptr_t>(out) % (EPT * sizeof(OT))) == 0 &&
+                   (reinterpret_cast<uintptr_t>(sums) % (EPT * 8)) == 0;
   uint32_t err = 0;
   for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < ngrp; t += stride) {
     const uint64_t i = (uint64_t)EPT * t;
@@ -255,9 +296,9 @@ __global__ void __launch_bounds__(256) lom_aggregate_kernel(const uint64_t* __re
     for (int e = 0; e < EPT; ++e) o[e] = (i + e < n) ? lom_avg_dequant(sm[e], total_weight, neg_c, step, err) : 0.0;
     if (vec) {
       if (out) {
-        double* od = static_cast<double*>(__builtin_assume_aligned(out + i, EPT * 8));
+        OT* od = static_cast<OT*>(__builtin_assume_aligned(out + i, EPT * sizeof(OT)));
 #pragma unroll
-        for (int e = 0; e < EPT; ++e) od[e] = o[e];
+        for (int e = 0; e < EPT; ++e) fbm_store_as(od + e, o[e]);
       }
       if (sums) {
         uint64_t* sd = static_cast<uint64_t*>(__builtin_assume_aligned(sums + i, EPT * 8));
@@ -268,7 +309,7 @@ __global__ void __launch_bounds__(256) lom_aggregate_kernel(const uint64_t* __re
 #pragma unroll
       for (int e = 0; e < EPT; ++e) {
         if (i + e < n) {
-          if (out) out[i + e] = o[e];
+          if (out) fbm_store_as(out + i + e, o[e]);
           if (sums) sums[i + e] = sm[e];
         }
       }
@@ -291,12 +332,19 @@ __global__ void __launch_bounds__(256) lom_aggregate_kernel(const uint64_t* __re
 #ifndef FBM_AGG_WS_W8
 #define FBM_AGG_WS_W8 4  // waves per workgroup at 8 parties (two rows per wave)
 #endif
-template <int EPT, int W, int PC>
+// Narrow outputs (OT = float, fbm_f16, fbm_bf16: the *_as entry points).  The epilogue keeps one element per
+// thread -- the division stays spread over the tile's lanes -- and neighbouring lanes then hand their rounded
+// bits to the lane whose destination address is 8-byte aligned, which stores the group (2 floats, 4 halves)
+// with one 8-byte nontemporal store: no lane issues a sub-dword store (the slow store form) except at the
+// edges.  The grouping follows the destination ADDRESS, so an `out` that starts at an odd element still
+// packs; a group that would cross the wave, the tile's valid end or n falls back to element stores.
+template <int EPT, int W, int PC, typename... OTS>
 __global__ void __launch_bounds__(64 * W) lom_aggregate_ws_kernel(const uint64_t* __restrict__ y, uint64_t n,
                                                                   uint64_t total_weight, double neg_c, double step,
-                                                                  double* __restrict__ out,
+                                                                  typename agg_out<OTS...>::type* __restrict__ out,
                                                                   uint64_t* __restrict__ sums,
                                                                   uint32_t* __restrict__ stats) {
+  typedef typename agg_out<OTS...>::type OT;
   static_assert(PC % W == 0, "rows per wave");
   constexpr int TILE = 64 * EPT, RPW = PC / W;
   __shared__ uint64_t part[W][TILE];
@@ -330,13 +378,45 @@ __global__ void __launch_bounds__(64 * W) lom_aggregate_ws_kernel(const uint64_t
   for (int e = 0; e < EPT; ++e) part[w][l * EPT + e] = sm[e];
   __syncthreads();
   uint32_t err = 0;
-  for (int e = threadIdx.x; e < TILE; e += 64 * W) {
-    if (base + e >= n) break;
-    uint64_t s = 0;
+  if constexpr (sizeof(OT) == 8) {
+    for (int e = threadIdx.x; e < TILE; e += 64 * W) {
+      if (base + e >= n) break;
+      uint64_t s = 0;
 #pragma unroll
-    for (int q = 0; q < W; ++q) s += part[q][e];
-    if (out) __builtin_nontemporal_store(lom_avg_dequant(s, total_weight, neg_c, step, err), out + base + e);
-    if (sums) __builtin_nontemporal_store(s, sums + base + e);
+      for (int q = 0; q < W; ++q) s += part[q][e];
+      if (out) __builtin_nontemporal_store(lom_avg_dequant(s, total_weight, neg_c, step, err), out + base + e);
+      if (sums) __builtin_nontemporal_store(s, sums + base + e);
+    }
+  } else {
+    typedef typename fbm_out<OT>::word OW;
+    constexpr int G = 8 / (int)sizeof(OT);  // elements of one 8-byte store
+    // (TILE and the stride are multiples of 64: every wave runs whole iterations, as the shuffles need)
+    for (int e = threadIdx.x; e < TILE; e += 64 * W) {
+      const bool ok = base + e < n;
+      uint64_t s = 0;
+#pragma unroll
+      for (int q = 0; q < W; ++q) s += part[q][e];
+      if (sums && ok) __builtin_nontemporal_store(s, sums + base + e);
+      if (!out) continue;
+      const uint32_t b = ok ? (uint32_t)fbm_out<OT>::bits(lom_avg_dequant(s, total_weight, neg_c, step, err)) : 0u;
+      uint64_t pk = b;
+      if constexpr (G == 2) {
+        pk |= (uint64_t)__shfl_down(b, 1) << 32;
+      } else {
+        pk |= (uint64_t)__shfl_down(b, 1) << 16;
+        pk |= (uint64_t)__shfl_down(b, 2) << 32;
+        pk |= (uint64_t)__shfl_down(b, 3) << 48;
+      }
+      OT* dst = out + base + e;
+      const int r = (int)((reinterpret_cast<uintptr_t>(dst) / sizeof(OT)) % G);  // place in its 8-byte group
+      const int lead = l - r;  // the group's first lane (e & 63 == l)
+      const bool packed = lead >= 0 && lead + G <= 64 && base + (uint64_t)(e - r) + G <= n;
+      if (packed) {
+        if (r == 0) __builtin_nontemporal_store(pk, reinterpret_cast<uint64_t*>(dst));
+      } else if (ok) {
+        __builtin_nontemporal_store((OW)b, reinterpret_cast<OW*>(dst));
+      }
+    }
   }
   if (err && out) atomicOr(stats + FBM_STAT_ERRFLAGS, FBM_ERR_DEQUANT_RANGE);
 }
@@ -350,6 +430,12 @@ int launch_lom_protect(const void* x, int x_dtype, uint64_t n, const QuantParams
   const dim3 grid((unsigned)g), block(256);
   if (x_dtype == FBM_F32)
     hipLaunchKernelGGL(lom_protect_kernel<float>, grid, block, 0, s, (const float*)x, n, qp, weight, peers, y, stats);
+  else if (x_dtype == FBM_F16)
+    hipLaunchKernelGGL(lom_protect_kernel<fbm_f16>, grid, block, 0, s, (const fbm_f16*)x, n, qp, weight, peers, y,
+                       stats);
+  else if (x_dtype == FBM_BF16)
+    hipLaunchKernelGGL(lom_protect_kernel<fbm_bf16>, grid, block, 0, s, (const fbm_bf16*)x, n, qp, weight, peers, y,
+                       stats);
   else if (x_dtype == FBM_F64)
     hipLaunchKernelGGL(lom_protect_kernel<double>, grid, block, 0, s, (const double*)x, n, qp, weight, peers, y, stats);
   else
@@ -358,19 +444,34 @@ int launch_lom_protect(const void* x, int x_dtype, uint64_t n, const QuantParams
   return check_launch("lom_protect_kernel");
 }
 
-// reverse_quantize of already-truncated values: -c + step * double(u)  (numpy order, no FMA)
+// reverse_quantize of already-truncated values: -c + step * double(u)  (numpy order, no FMA), rounded to OT
+template <typename OT>
 __global__ void __launch_bounds__(256) dequantize_kernel(const uint64_t* __restrict__ u, uint64_t n, double neg_c,
-                                                         double step, double* __restrict__ out) {
+                                                         double step, OT* __restrict__ out) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double du = (double)u[i];
   const double prod = step * du;
-  out[i] = neg_c + prod;
+  fbm_store_as(out + i, neg_c + prod);
 }
 
-int launch_dequantize(const uint64_t* u, uint64_t n, double neg_c, double step, double* out, hipStream_t s) {
+int launch_dequantize(const uint64_t* u, uint64_t n, double neg_c, double step, void* out, int out_dtype,
+                      hipStream_t s) {
   if (n == 0) return FBM_OK;
-  hipLaunchKernelGGL(dequantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, u, n, neg_c, step, out);
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  switch (out_dtype) {
+    case FBM_F32:
+      hipLaunchKernelGGL(dequantize_kernel<float>, grid, block, 0, s, u, n, neg_c, step, (float*)out);
+      break;
+    case FBM_F16:
+      hipLaunchKernelGGL(dequantize_kernel<fbm_f16>, grid, block, 0, s, u, n, neg_c, step, (fbm_f16*)out);
+      break;
+    case FBM_BF16:
+      hipLaunchKernelGGL(dequantize_kernel<fbm_bf16>, grid, block, 0, s, u, n, neg_c, step, (fbm_bf16*)out);
+      break;
+    default:
+      hipLaunchKernelGGL(dequantize_kernel<double>, grid, block, 0, s, u, n, neg_c, step, (double*)out);
+  }
   return check_launch("dequantize_kernel");
 }
 
@@ -412,16 +513,32 @@ int lom_aggregate_kernel_name(int n_parties, uint64_t n, const void* y, char* bu
   return w < len ? FBM_OK : FBM_E_ARG;
 }
 
-int launch_lom_aggregate(const uint64_t* y, int n_parties, uint64_t n, uint64_t total_weight, double neg_c, double step,
-                         double* out, uint64_t* sums, uint32_t* stats, hipStream_t s) {
-  if (n == 0) return FBM_OK;
+// the kernel of an output type: float64 is the kernel without the trailing type argument
+template <typename OT, int EPT, int W, int PC>
+static constexpr auto lom_agg_ws_fn() {
+  if constexpr (std::is_same<OT, double>::value)
+    return &lom_aggregate_ws_kernel<EPT, W, PC>;
+  else
+    return &lom_aggregate_ws_kernel<EPT, W, PC, OT>;
+}
+template <typename OT, int EPT, int PC>
+static constexpr auto lom_agg_fn() {
+  if constexpr (std::is_same<OT, double>::value)
+    return &lom_aggregate_kernel<EPT, PC>;
+  else
+    return &lom_aggregate_kernel<EPT, PC, OT>;
+}
+
+template <typename OT>
+static int launch_lom_aggregate_as(const uint64_t* y, int n_parties, uint64_t n, uint64_t total_weight, double neg_c,
+                                   double step, OT* out, uint64_t* sums, uint32_t* stats, hipStream_t s) {
   if (lom_agg_ws(n_parties, n, y)) {
     const dim3 grid((unsigned)((n + 127) / 128));
     if (n_parties == 16)
-      hipLaunchKernelGGL((lom_aggregate_ws_kernel<2, 8, 16>), grid, dim3(512), 0, s, y, n, total_weight, neg_c, step,
-                         out, sums, stats);
+      hipLaunchKernelGGL((lom_agg_ws_fn<OT, 2, 8, 16>()), grid, dim3(512), 0, s, y, n, total_weight, neg_c, step, out,
+                         sums, stats);
     else
-      hipLaunchKernelGGL((lom_aggregate_ws_kernel<2, FBM_AGG_WS_W8, 8>), grid, dim3(64 * FBM_AGG_WS_W8), 0, s, y, n,
+      hipLaunchKernelGGL((lom_agg_ws_fn<OT, 2, FBM_AGG_WS_W8, 8>()), grid, dim3(64 * FBM_AGG_WS_W8), 0, s, y, n,
                          total_weight, neg_c, step, out, sums, stats);
     return check_launch("lom_aggregate_ws_kernel");
   }
@@ -431,19 +548,34 @@ int launch_lom_aggregate(const uint64_t* y, int n_parties, uint64_t n, uint64_t 
   const uint64_t gmax = 256ull * FBM_AGG_WG_PER_CU;  // 256 CUs, grid-stride beyond
   if (FBM_AGG_WG_PER_CU > 0 && g > gmax) g = gmax;
   const dim3 grid((unsigned)g), block(256);
-#define FBM_AGG_CASE(PC)                                                                                          \
-  case PC:                                                                                                        \
-    hipLaunchKernelGGL((lom_aggregate_kernel<EPT, PC>), grid, block, 0, s, y, n_parties, n, total_weight, neg_c, \
-                       step, out, sums, stats);                                                                   \
+#define FBM_AGG_CASE(PC)                                                                                           \
+  case PC:                                                                                                         \
+    hipLaunchKernelGGL((lom_agg_fn<OT, EPT, PC>()), grid, block, 0, s, y, n_parties, n, total_weight, neg_c, step, \
+                       out, sums, stats);                                                                          \
     break;
   switch (n_parties) {
     FBM_AGG_CASE(2) FBM_AGG_CASE(3) FBM_AGG_CASE(4) FBM_AGG_CASE(8) FBM_AGG_CASE(16)
     default:
-      hipLaunchKernelGGL((lom_aggregate_kernel<EPT, 0>), grid, block, 0, s, y, n_parties, n, total_weight, neg_c,
-                         step, out, sums, stats);
+      hipLaunchKernelGGL((lom_agg_fn<OT, EPT, 0>()), grid, block, 0, s, y, n_parties, n, total_weight, neg_c, step,
+                         out, sums, stats);
   }
 #undef FBM_AGG_CASE
   return check_launch("lom_aggregate_kernel");
+}
+
+int launch_lom_aggregate(const uint64_t* y, int n_parties, uint64_t n, uint64_t total_weight, double neg_c, double step,
+                         void* out, int out_dtype, uint64_t* sums, uint32_t* stats, hipStream_t s) {
+  if (n == 0) return FBM_OK;
+  switch (out_dtype) {
+    case FBM_F32:
+      return launch_lom_aggregate_as(y, n_parties, n, total_weight, neg_c, step, (float*)out, sums, stats, s);
+    case FBM_F16:
+      return launch_lom_aggregate_as(y, n_parties, n, total_weight, neg_c, step, (fbm_f16*)out, sums, stats, s);
+    case FBM_BF16:
+      return launch_lom_aggregate_as(y, n_parties, n, total_weight, neg_c, step, (fbm_bf16*)out, sums, stats, s);
+    default:
+      return launch_lom_aggregate_as(y, n_parties, n, total_weight, neg_c, step, (double*)out, sums, stats, s);
+  }
 }
 
 }  // namespace fbm

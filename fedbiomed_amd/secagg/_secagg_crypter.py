@@ -131,7 +131,8 @@ class SecaggCrypter:
                        clipping_range: Union[int, None] = None, weight: Optional[int] = None,
                        target_range: Optional[int] = None, ct_offset: int = 0, defer_exp: bool = False,
                        out: Optional[torch.Tensor] = None, factor: Optional[torch.Tensor] = None):
-        """Device tensor (f32/f64) in HBM -> int32 [n_ct, 64] ciphertext limbs in HBM.
+        """Device tensor (f16/bf16/f32/f64) in HBM -> int32 [n_ct, 64] ciphertext limbs in HBM; a 16-bit
+        tensor encrypts to the ciphertexts of `params.double()`, with no upcast copy made.
         `factor`: this party's H(t_k)^key of these ciphertexts computed ahead (`decrypt_factor_tensor` with
         the party's key, round and ct_offset; `prepare_encrypt` issues it for the list API): the encrypt is
         then one product per ciphertext instead of an exponentiation, with the same ciphertexts.
@@ -157,16 +158,22 @@ class SecaggCrypter:
                          total_sample_size: int, clipping_range: Union[int, None] = None,
                          num_expected_params: int = 1, target_range: Optional[int] = None,
                          want_sums: bool = False, ct_offset: int = 0,
-                         decrypt_factor: Optional[torch.Tensor] = None):
+                         decrypt_factor: Optional[torch.Tensor] = None,
+                         out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None):
         """[P, n_ct, 64] int32 ciphertext limbs in HBM -> float64 [n] averaged parameters.
         `decrypt_factor`: this round's `decrypt_factor_tensor` (computed ahead, e.g. while the
-        nodes encrypt), or None to compute it here."""
+        nodes encrypt), or None to compute it here.
+        `out_dtype`: torch.float32 / float16 / bfloat16 (None: float64) -- the kernel writes that type, bit
+        for bit what `.to(out_dtype)` of the float64 result gives.  `out`: a contiguous 1-D destination of n
+        elements on the ciphertexts' device (e.g. a slice of the flat parameter buffer in the model's dtype);
+        its dtype is the output dtype, and it is returned.  ValueError if it disagrees with `out_dtype` or
+        has another shape, device or layout."""
         if not isinstance(key, int):
             raise TypeError("The key should be type of integer")
         target_range = target_range or SAParameters.TARGET_RANGE
         out, sums = D.jl_aggregate(cts, biprime, key, current_round, num_expected_params, total_sample_size,
                                    clip=clipping_range, target=target_range, want_sums=want_sums,
-                                   ct_offset=ct_offset, factor=decrypt_factor)
+                                   ct_offset=ct_offset, factor=decrypt_factor, out_dtype=out_dtype, out=out)
         return (out, sums) if want_sums else out
 
     def decrypt_factor_tensor(self, current_round: int, num_ciphertexts: int, key: int, biprime: int,
@@ -644,7 +651,8 @@ class SecaggLomCrypter(SecaggCrypter):
                        clipping_range: Union[int, None] = None, weight: Optional[int] = None,
                        target_range: Optional[int] = None, elem_offset: int = 0,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Device tensor (f32/f64) -> masked uint64 vector (int64 tensor) in HBM.
+        """Device tensor (f16/bf16/f32/f64) -> masked uint64 vector (int64 tensor) in HBM; a 16-bit tensor
+        masks to the vector of `params.double()`, with no upcast copy made.
         `elem_offset`: global index of this shard's first element (multiple of 8); `out`: an
         int64 destination (e.g. this party's row of the [P, n] matrix aggregate_tensor takes)."""
         target_range = target_range or SAParameters.TARGET_RANGE
@@ -684,10 +692,13 @@ class SecaggLomCrypter(SecaggCrypter):
         return secrets_, signs
 
     def aggregate_tensor(self, Y: torch.Tensor, total_sample_size: int, clipping_range: Union[int, None] = None,
-                         target_range: Optional[int] = None, want_sums: bool = False):
-        """[P, n] masked vectors in HBM -> float64 [n] averaged parameters."""
+                         target_range: Optional[int] = None, want_sums: bool = False,
+                         out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None):
+        """[P, n] masked vectors in HBM -> float64 [n] averaged parameters.
+        `out_dtype` / `out`: as SecaggCrypter.aggregate_tensor's -- the averaged parameters written by the
+        kernel as float32 / float16 / bfloat16, into a caller's buffer if given."""
         out, sums = D.lom_aggregate(Y, total_sample_size, clipping_range, target_range or SAParameters.TARGET_RANGE,
-                                    want_sums=want_sums)
+                                    want_sums=want_sums, out_dtype=out_dtype, out=out)
         return (out, sums) if want_sums else out
 
     def encrypt(self, current_round: int, node_id: str, params: List[float], pairwise_secrets: Dict[str, bytes],

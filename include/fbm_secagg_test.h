@@ -24,6 +24,13 @@ extern "C" {
 /* host test hook (no GPU): fbm_int_true_div_big's per-value arithmetic on host arrays. */
 int fbm_test_true_div_big(const uint64_t* x, uint64_t n, const uint32_t* k, int k_words, int negative, double* out);
 
+/* host test hooks (no GPU): the conversions of the 16-bit inputs and the narrow outputs, the same
+ * host/device source the kernels run (fedbiomed_amd/csrc/fbm_common.hpp).  fbm_test_widen16: *out = the exact
+ * double of the FBM_F16 / FBM_BF16 element `bits`.  fbm_test_narrow: *bits_out = the bits an *_as entry point
+ * stores for the float64 result v as dtype FBM_F32 (32 bits), FBM_F16 or FBM_BF16 (16 bits, zero-extended). */
+int fbm_test_widen16(uint16_t bits, int dtype, double* out);
+int fbm_test_narrow(double v, int dtype, uint32_t* bits_out);
+
 /* Sliding-window width of the JL exponentiation's table path (odd-power table of 2^(w-1) entries;
  * the short path -- one FDH digest, N > 2^262: every 1024-bit biprime -- needs no table). */
 int fbm_jl_window(void);
