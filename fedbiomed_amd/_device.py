@@ -910,6 +910,27 @@ class jl_short:
         return self._hooks.__exit__(*exc)
 
 
+class jl_chain:
+    """The short path's chain form for the one-lane JL launches this thread issues inside (the test
+    build's fbm_jl_set_chain; the block's calls run through the test build): "body" (the default: one
+    assembly body for the whole binary chain, the running value in registers) or
+    "per_call" (the per-product loop it replaced).  Results are bit-identical -- an A/B and test switch."""
+
+    def __init__(self, form: str):
+        if form not in ("body", "per_call"):
+            raise ValueError("form must be 'body' or 'per_call'")
+        self._percall, self._prev, self._hooks = int(form == "per_call"), None, N.test_hooks()
+
+    def __enter__(self):
+        self._hooks.__enter__()
+        self._prev = N.load_test().fbm_jl_set_chain(self._percall)
+        return self
+
+    def __exit__(self, *exc):
+        N.load_test().fbm_jl_set_chain(self._prev)
+        return self._hooks.__exit__(*exc)
+
+
 _clear_hooks = []  # callables run by jl_clear_caches (SecaggCrypter.drop_prepared registers itself)
 
 

@@ -2235,6 +2235,8 @@ int fbm_jl_set_engine(int mode) {
 
 int fbm_jl_engine_for(uint64_t n_ct) { return jl_engine_for(n_ct); }
 
+int fbm_jl_set_chain(int percall) { return jl_chain_set(percall); }
+
 int fbm_jl_set_short(int on) {
   const int prev = t_short_on;
   t_short_on = on ? 1 : 0;

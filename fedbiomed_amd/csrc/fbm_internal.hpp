@@ -252,6 +252,10 @@ int launch_jl_prod(const uint32_t* cts, int n_parties, uint64_t n_ct, const JlPa
                    const uint32_t* factor, uint32_t* xout, hipStream_t s);
 #define FBM_EXP_DEC 1        // jl_exp mode bits: plain power (no nude product)
 #define FBM_EXP_OUT_NADIC 4  // out rows are the result's N-adic digits (v mod N, v div N)
+#define FBM_EXP_PERCALL 8    // (one-lane engine, short path) the per-product chain loop instead of the chain body
+#ifndef FBM_EXP_PERCALL_CHAIN  // 0: compile the per-product loop out of jl_exp_kernel
+#define FBM_EXP_PERCALL_CHAIN 1
+#endif
 int host_gcd_is_one_r8(const uint32_t* r8, const uint32_t* n32, uint32_t* err);
 // E^-1 mod N^2 (times nude when given: a negative-key encrypt) from E's N-adic digit rows
 // Ed [ct][64] (e0 | e1): y = e0^-1 mod N into Y [ct][32], then the lift -> out [ct][64]
@@ -312,6 +316,7 @@ uint64_t jl_table_slots();
 #define FBM_ENGINE_QUAD 4
 int jl_engine_policy();
 int jl_engine_set(int mode);
+int jl_chain_set(int percall);
 int jl_engine_for(uint64_t n_ct);
 uint64_t jl_table_bytes(uint64_t n_ct);
 // compute units of the calling thread's current device (cached per device)

@@ -29,6 +29,7 @@
 #include "fbm_internal.hpp"
 #include "fbm_mont_asm.hpp"
 #include "fbm_nadic_asm.hpp"
+#include "fbm_nadic_chain_asm.hpp"
 #include "fbm_quad_asm.hpp"
 #include "fbm_tri_asm.hpp"
 #include "fbm_safegcd.hpp"
@@ -1013,7 +1014,8 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_exp_kernel(const uint32_t* __
   // [j < 9] + [j == 0] (fbm_na_ms_reg: the rows' 2^29 - 1 - q_i folded in); words 72..143 the square's
   // (2^29 - 1 + P'_j, 0) (fbm_na_sq_lds)
   const uint32_t doff = lds_addr(lds_a + FBM_NL * FBM_BLOCK);
-  const uint32_t koff = doff + 72u * 4u;
+  const uint32_t koff = doff + 72u * 4u;  // (the chain body reads the square's pairs at doff + 288 too)
+  static_assert(FBM_NA_LIMBS * 8 == 72 * 4, "the square's pairs follow the short product's");
   if (tid < 72) {
     uint32_t v = launder_s(cst)[FBM_CST_QD + tid];
     if (!(tid & 1)) v += ((tid >> 1) < FBM_NA_SHORT_LIMBS ? FBM_QMASK : 0u) + (tid == 0 ? 1u : 0u);
@@ -1080,7 +1082,10 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_exp_kernel(const uint32_t* __
         shortp = sbits >= 0 && !SEG(key_is_zero, key_is_zero_a) && !__any(wide || mid != 0u);
 #pragma unroll
         for (int k = 0; k < FBM_NA_SHORT_LIMBS; ++k) hs[k] = h29[k];
-        if (shortp) lds_store_col(lds, FBM_BLOCK, h29);  // A = (h, 0), raw (no Montgomery form)
+#if FBM_EXP_PERCALL_CHAIN  // (the chain body builds (h, 0) in its registers from hs)
+        if (shortp && (SEG(mode, mode_a) & FBM_EXP_PERCALL))
+          lds_store_col(lds, FBM_BLOCK, h29);  // A = (h, 0), raw (no Montgomery form)
+#endif
         if (wide) {  // FDH retries (small moduli only): h_hi R^2 = (h_hi, 0) * R^3 R^-1 -> entry 1
 #pragma unroll
           for (int k = 0; k < NA; ++k) {
@@ -1096,15 +1101,24 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_exp_kernel(const uint32_t* __
       // product (x h 2^-261) per 1 bit, then C = 2^f R^2 (host-built, ops buffer) turns the
       // chain's h^|key| 2^-f into h^|key| R -- 1 305 multiplies per 1 bit instead of a window
       // table's 31 + ~293 general products of 6 584 and its per-lane table traffic
+      // The whole chain is one asm body (fbm_na_chain_short): the running value stays in the
+      // lane's registers from product to product and reaches the LDS column once, at the end.  The
+      // per-product loop (an asm block per product, operands through the LDS column) stays for the test
+      // build's switch (FBM_EXP_PERCALL: fbm_jl_set_chain) unless compiled out (-DFBM_EXP_PERCALL_CHAIN=0).
       const uint32_t* kw = SEG(ops, ops_a) + FBM_OPS_KW;
-      uint32_t w = 0;
+#if FBM_EXP_PERCALL_CHAIN
+      if (SEG(mode, mode_a) & FBM_EXP_PERCALL) {
+        uint32_t w = 0;
 #pragma unroll 1
-      for (int j = sbits - 1; j >= 0; --j) {
-        if (j == sbits - 1 || (j & 31) == 31)  // one exponent word per 32 bits, loaded ahead of the squaring
-          w = __builtin_amdgcn_readfirstlane(launder_s(kw)[j >> 5]);
-        fbm_na_sq_lds(aoff, koff, NK, np);
-        if ((w >> (j & 31)) & 1u) fbm_na_ms_reg(aoff, hs, doff, NK, np);
-      }
+        for (int j = sbits - 1; j >= 0; --j) {
+          if (j == sbits - 1 || (j & 31) == 31)  // one exponent word per 32 bits, loaded ahead of the squaring
+            w = __builtin_amdgcn_readfirstlane(launder_s(kw)[j >> 5]);
+          fbm_na_sq_lds(aoff, koff, NK, np);
+          if ((w >> (j & 31)) & 1u) fbm_na_ms_reg(aoff, hs, doff, NK, np);
+        }
+      } else
+#endif
+        fbm_na_chain_short(aoff, hs, uniform_val(doff), uniform_val(kw), sbits, NK, np);
       // x C: the chain stays the LDS operand, C (uniform) is the B operand read from its broadcast
       // column in the ops buffer (limb k at word k * 256, every lane the same address)
       fbm_na_mm_glb(aoff, SEG(ops, ops_a) + FBM_OPS_CBC, 0u, NK, np);
@@ -2394,10 +2408,22 @@ __global__ void jl_batch_desc_kernel(JlExpBatch bt, JlExpSeg* __restrict__ segs,
   if (t == 0) ctr[0] = 0u;
 }
 
+// The short path's chain form of the CALLING THREAD's one-lane launches: 0 (the default, the product
+// library's only form) the register-resident chain body, 1 the per-product loop (the test build's
+// fbm_jl_set_chain: an A/B and test switch, bit-identical results).
+static thread_local int t_chain_percall = 0;
+
+int jl_chain_set(int percall) {
+  const int prev = t_chain_percall;
+  t_chain_percall = percall ? 1 : 0;
+  return prev;
+}
+
 int launch_jl_exp(const uint32_t* H, uint64_t n_ct, const JlParams& jp, const JlSched& sc, int mode,
                   const uint32_t* nude, uint32_t* table, uint64_t table_slots, const uint32_t* ops,
                   const uint32_t* cst, uint32_t* out, hipStream_t s, const uint32_t* Hc) {
   if (n_ct == 0) return FBM_OK;
+  if (t_chain_percall) mode |= FBM_EXP_PERCALL;
   if (g_batch.active && g_batch.accept) return jl_batch_record(H, n_ct, jp, sc, mode, nude, ops, cst, out, Hc);
   const int eng = jl_engine_for(n_ct);
   if (eng == FBM_ENGINE_QUAD || eng == FBM_ENGINE_TRIPLE) {

@@ -61,6 +61,12 @@ int fbm_jl_engine_for(uint64_t n_ct);
  * sliding-window table path -- an A/B and test switch; results are bit-identical).  Returns the
  * previous setting. */
 int fbm_jl_set_short(int on);
+/* The short path's chain form for the CALLING THREAD's one-lane launches: 0 (the default) the
+ * register-resident chain body -- one assembly body for the whole binary chain, the running value in
+ * the lane's registers from product to product --, 1 the per-product loop it replaced
+ * (an assembly block per product, operands through the lane's LDS column): an A/B and test switch;
+ * results are bit-identical.  Returns the previous setting. */
+int fbm_jl_set_chain(int percall);
 
 /* ---- host test hook (no GPU): the device modular-inverse routine (Bernstein-Yang divsteps,
  * fedbiomed_amd/csrc/fbm_safegcd.hpp) run on the host, for unit tests.

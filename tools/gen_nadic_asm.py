@@ -52,7 +52,8 @@ workgroup-blocked layout of tables and residue columns) or, for the square, from
 column itself.  The constants block (80 words, FBM_CST_NA29 in fbm_internal.hpp) holds
 N_0..N_9 at words 0..9, N_10..N_35 at words 16..41 and K'_0..K'_35 at words 42..77.
 
-Usage:  python tools/gen_nadic_asm.py   (rewrites the header; the build does not run this)
+Usage:  python tools/gen_nadic_asm.py   (rewrites the header and, beside it, fbm_nadic_chain_asm.hpp: the
+        short path's register-resident chain body, chain_short below; the build does not run this)
 """
 
 import os
@@ -63,6 +64,7 @@ NW = L - 1  # window accumulators per part
 MID = 18    # rows before the mid-product reduction
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "fedbiomed_amd", "csrc", "fbm_nadic_asm.hpp")
+CHAIN_NAME = "fbm_nadic_chain_asm.hpp"  # the short path's chain body (chain_short), written beside OUT
 MASK = hex((1 << LB) - 1)
 AS0 = 2 * NW            # s window of the general product
 B00, B10 = 2 * AS0, 2 * AS0 + L
@@ -730,6 +732,353 @@ def square_unrolled():
     return rotate_carries(body)
 
 
+# ------------------------------------------------------------------------------------------
+# The short path's whole binary chain as ONE body (round 7): the running value X never leaves the
+# lane's registers between products.  Both products use the square's register plan (the short
+# product's At_k / As_k / B are the square's SAt_k / SAs_k / SB, k < 35; its rows take h's limbs
+# from the asm inputs %[h0] .. %[h8]), the square's rows take x0_i from SB0(i) (no LDS row
+# operand), and each product ends in a normalise that writes limb k straight into the B register
+# the next product reads (v_and_b32 B(k), MASK, lo: the instruction that masked the limb before
+# its store) while the next product's initial s pairs -- (K'_j, 0) at %[d] + 288 before a square,
+# (D'_j, 0) at %[d] before a short product, read j into the pair column j starts in: STS, SAs_0 ..
+# SAs_34, for both products -- are read behind the pairs the normalise releases.  Row 0 of either
+# product waits for read j by count (LDS reads return in order; no scalar load is in flight then).
+# The multiplies, their order, the mid-product reduction and the folds are square_unrolled()'s and
+# mul_short_reg()'s: the results are bit-identical (tests/test_nadic_chain_asm.py).
+#   s34 = j (the exponent bit of the current squaring), s35 = the exponent word holding bit j
+#   (one scalar load per 32 bits from %[kw]), s30 / s31 scratch, PADR (= SAADR) the pairs' address.
+# Control:  entry -> [square -> (bit j set: normalise, short product)] -> j == 0 ? exit :
+#           --j, normalise -> square ...;  exit: one normalise-and-store into the LDS column.
+# ------------------------------------------------------------------------------------------
+PADR = SAADR
+KOFF = 2 * L * 4  # the square's pairs follow the short product's 36 pairs in the LDS row
+
+
+def chain_wait(j):
+    """Before row 0's s multiply j consumes the prefetched pair j (of 36, issued in order)."""
+    if j == 0:
+        return ["s_waitcnt lgkmcnt(15)"]
+    return [f"s_waitcnt lgkmcnt({L - 1 - j})"] if L - 1 - j < 15 else []
+
+
+def chain_pair_dst(j):
+    return STS if j == 0 else SAs(j - 1)
+
+
+def chain_prefetch_all():
+    return [f"ds_read_b64 {chain_pair_dst(j)}, {PADR} offset:{8 * j}" for j in range(L)]
+
+
+def chain_sq_row(i):
+    """sq_row_static(i) with the row operand 2 x0_i taken from SB0 (set by the previous row)."""
+    first, last, even = i == 0, i == L - 1, i % 2 == 0
+    out = []
+    if even:
+        out.append(f"v_mad_u64_u32 {SAt(0)}, vcc, {SB0(i // 2)}, {SB0(i // 2)}, {'0' if first else SAt(0)}")
+    out.append(f"v_mul_lo_u32 {SQ}, {SAtLo(0)}, {SNPV}")
+    if first:
+        out += chain_wait(0)
+    out.append(f"v_mad_u64_u32 {STS}, vcc, {SX0D}, {SB1(0)}, {STS if first else SAs(0)}")
+    for j in range(1, L):
+        if first:
+            addend = SAs(j - 1)
+            out += chain_wait(j)
+        else:
+            addend = "0" if j == NW else SAs(j)
+        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {SX0D}, {SB1(j)}, {addend}")
+        if j == 2:
+            out.append(f"v_and_b32 {SQ}, {MASK}, {SQ}")
+        if j == 12:
+            out.append(f"v_mad_i64_i32 {STS}, vcc, {SQ}, -1, {STS}")
+        if j == 20:
+            out.append(f"v_mul_lo_u32 {SQ2}, {STSLO}, {SNPV}")
+        if j == 26:
+            out.append(f"v_and_b32 {SQ2}, {MASK}, {SQ2}")
+    for k in range(i + 1, L):
+        addend = "0" if (first or k == L - 1) else SAt(k)
+        out.append(f"v_mad_u64_u32 {SAt(k)}, vcc, {SX0D}, {SB0(k)}, {addend}")
+    top = "0" if last else SAt(L - 1)
+    out.append(f"v_mad_u64_u32 {STT}, vcc, {SQ}, {Ns(0)}, {SAt(0)}")
+    for k in range(1, L):
+        out.append(f"v_mad_u64_u32 {SAt(k - 1)}, vcc, {SQ}, {Ns(k)}, {SAt(k) if k < L - 1 else top}")
+    out.append(f"v_mad_u64_u32 {STS}, vcc, {SQ2}, {Ns(0)}, {STS}")
+    for j in range(1, L):
+        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {SQ2}, {Ns(j)}, {SAs(j - 1)}")
+    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}",
+            f"v_lshrrev_b64 {STS}, {LB}, {STS}", f"v_lshl_add_u64 {SAs(0)}, {STS}, 0, {SAs(0)}"]
+    if not last:
+        out.append(f"v_lshlrev_b32 {SX0D}, 1, {SB0(i + 1)}")
+    return out
+
+
+def chain_sq_rows():
+    """The unrolled triangular square on the B registers (its s pairs prefetched): window out."""
+    assert SQ_KFOLD and UNROLLED_SQUARE and SQ_MID_KEEP is not None
+    body = [f"v_lshlrev_b32 {SX0D}, 1, {SB0(0)}"]
+    t_regs, s_regs = [SAtLo(k) for k in range(L - 1)], [SAsLo(k) for k in range(NW)]
+    for i in range(L):
+        body += chain_sq_row(i)
+        parts = ([t_regs], [SQ_MID_KEEP[0]]) if i == SQ_MID_T - 1 else ([], [])
+        if i == SQ_MID_S - 1:
+            parts = (parts[0] + [s_regs], parts[1] + [SQ_MID_KEEP[1]])
+        if parts[0]:
+            one = [set() if r is t_regs else sq_one_slots() for r in parts[0]]
+            body += mid_reduce(parts[0], keep=parts[1], one=one)
+    body += [f"v_mad_u64_u32 {SAt(2 * h - L)}, vcc, {SB0(h)}, {SB0(h)}, {SAt(2 * h - L)}" for h in range(L // 2, L)]
+    return body
+
+
+def chain_short_row(i, x=None):
+    """short_row(i) on the square's register plan; row 0's s addends are the prefetched pairs."""
+    assert SHORT_KFOLD
+    x, first = x or f"%[h{i}]", i == 0
+    out = [f"v_mad_u64_u32 {STT}, vcc, {x}, {SB0(0)}, {'0' if first else SAt(0)}"]
+    for j in range(1, L):
+        addend = "0" if (first or j == NW) else SAt(j)
+        out.append(f"v_mad_u64_u32 {SAt(j - 1)}, vcc, {x}, {SB0(j)}, {addend}")
+        if j == 3:
+            out.append(f"v_mul_lo_u32 {SQ}, {STTLO}, {SNPV}")
+        if j == 6:
+            out.append(f"v_and_b32 {SQ}, {MASK}, {SQ}")
+    out.append(f"v_mad_u64_u32 {STT}, vcc, {SQ}, {Ns(0)}, {STT}")
+    for j in range(1, L):
+        out.append(f"v_mad_u64_u32 {SAt(j - 1)}, vcc, {SQ}, {Ns(j)}, {SAt(j - 1)}")
+    if first:
+        out += chain_wait(0)
+    out.append(f"v_mad_u64_u32 {STS}, vcc, {x}, {SB1(0)}, {STS if first else SAs(0)}")
+    for j in range(1, L):
+        if first:
+            addend = SAs(j - 1)
+            out += chain_wait(j)
+        else:
+            addend = "0" if j == NW else SAs(j)
+        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {x}, {SB1(j)}, {addend}")
+        if j == 12:
+            out.append(f"v_mad_i64_i32 {STS}, vcc, {SQ}, -1, {STS}")
+        if j == 20:
+            out.append(f"v_mul_lo_u32 {SQ2}, {STSLO}, {SNPV}")
+        if j == 26:
+            out.append(f"v_and_b32 {SQ2}, {MASK}, {SQ2}")
+    out.append(f"v_mad_u64_u32 {STS}, vcc, {SQ2}, {Ns(0)}, {STS}")
+    for j in range(1, L):
+        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {SQ2}, {Ns(j)}, {SAs(j - 1)}")
+    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}",
+            f"v_lshrrev_b64 {STS}, {LB}, {STS}", f"v_lshl_add_u64 {SAs(0)}, {STS}, 0, {SAs(0)}"]
+    return out
+
+
+# The chain's short rows 1 .. 8 unrolled (11 KB of code beside the square's 35 KB) or, A/B switch
+# (FBM_GEN_CHAIN_SHORT_LOOPED=1), as a loop over one row body that multiplies by %[h1] and then rotates
+# h1 <- h2 <- ... <- h8 <- h1 (9 moves a row; 8 rows restore the asm's input registers exactly).
+CHAIN_SHORT_LOOPED = os.environ.get("FBM_GEN_CHAIN_SHORT_LOOPED", "0") == "1"
+
+
+def chain_short_rows():
+    if not CHAIN_SHORT_LOOPED:
+        return [ln for i in range(KS) for ln in chain_short_row(i)]
+    loop = ".Lfbm_ch_row_%="
+    rot = [f"v_mov_b32 {STMP}, %[h1]"] + [f"v_mov_b32 %[h{i}], %[h{i + 1}]" for i in range(1, KS - 1)]
+    rot.append(f"v_mov_b32 %[h{KS - 1}], {STMP}")
+    return (chain_short_row(0) + [f"s_mov_b32 s31, {KS - 1}", loop + ":"] + chain_short_row(1) + rot +
+            ["s_sub_u32 s31, s31, 1", "s_cmp_lg_u32 s31, 0", f"s_cbranch_scc1 {loop}"])
+
+
+def chain_normalise(prefetch):
+    """Window -> the B registers (limb k of digit d into SB_d(k)); `prefetch`: read the next product's
+    pair j from PADR + 8 j into the pair the s normalise has just released (STS is free throughout:
+    both halves carry in STT)."""
+    out = []
+    for acc, lo, dst, s_part in ((SAt, SAtLo, SB0, False), (SAs, SAsLo, SB1, True)):
+        pf = prefetch and s_part
+        if pf:
+            out.append(f"ds_read_b64 {chain_pair_dst(0)}, {PADR}")
+        out += [f"v_lshrrev_b64 {STT}, {LB}, {acc(0)}", f"v_and_b32 {dst(0)}, {MASK}, {lo(0)}"]
+        if pf:
+            out.append(f"ds_read_b64 {chain_pair_dst(1)}, {PADR} offset:8")
+        for k in range(1, NW):
+            out += [f"v_lshl_add_u64 {acc(k)}, {STT}, 0, {acc(k)}",
+                    f"v_lshrrev_b64 {STT}, {LB}, {acc(k)}",
+                    f"v_and_b32 {dst(k)}, {MASK}, {lo(k)}"]
+            if pf:
+                out.append(f"ds_read_b64 {chain_pair_dst(k + 1)}, {PADR} offset:{8 * (k + 1)}")
+        out.append(f"v_mov_b32 {dst(NW)}, {STTLO}")
+    return out
+
+
+def chain_store():
+    """The chain's exit: the window normalised into the lane's LDS column (square_unrolled's tail)."""
+    out = [f"v_add_u32 {STMP}, 0x10000, %[a]"]
+
+    def st(k, reg):
+        if k < 64:
+            return f"ds_write_b32 %[a], {reg} offset:{k * 1024}"
+        return f"ds_write_b32 {STMP}, {reg} offset:{(k - 64) * 1024}"
+
+    for acc, lo, carry, carry_lo, base in ((SAt, SAtLo, STT, STTLO, 0), (SAs, SAsLo, STS, STSLO, L)):
+        out += [f"v_lshrrev_b64 {carry}, {LB}, {acc(0)}", f"v_and_b32 {lo(0)}, {MASK}, {lo(0)}", st(base, lo(0))]
+        for k in range(1, NW):
+            out += [f"v_lshl_add_u64 {acc(k)}, {carry}, 0, {acc(k)}",
+                    f"v_lshrrev_b64 {carry}, {LB}, {acc(k)}",
+                    f"v_and_b32 {lo(k)}, {MASK}, {lo(k)}",
+                    st(base + k, lo(k))]
+        out.append(st(base + NW, carry_lo))
+    out.append("s_waitcnt lgkmcnt(0)")
+    return out
+
+
+def chain_one(short):
+    """One product of the chain as a body of its own, registers in (X in SB0 / SB1), registers out
+    (tests/test_nadic_chain_asm.py): the pairs from %[p], the rows, the normalise into SB0 / SB1."""
+    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]", f"v_mov_b32 {PADR}, %[p]"] + chain_prefetch_all()
+    body.append("s_waitcnt lgkmcnt(0)")
+    body += chain_short_rows() if short else chain_sq_rows()
+    return rotate_carries(body + chain_normalise(False))
+
+
+def chain_short():
+    """The whole chain: X = (h, 0), then for j = sbits - 1 .. 0 a square and, where bit j of the
+    exponent (%[kw]'s words) is set, a short product; the result normalised into the LDS column."""
+    lbl = {k: f".Lfbm_ch_{k}_%=" for k in ("sq", "next", "exit", "word")}
+    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]"]
+    body += [f"v_mov_b32 {SB0(i)}, " + (f"%[h{i}]" if i < KS else "0") for i in range(L)]
+    body += [f"v_mov_b32 {SB1(i)}, 0" for i in range(L)]
+    # zero iterations (|key| = 1): the store below normalises the window, so X goes through it
+    body += [f"v_mov_b32 {SAtLo(k)}, {SB0(k)}" for k in range(NW)] + [f"v_mov_b32 v{2 * k + 1}, 0" for k in range(NW)]
+    body += [f"v_mov_b32 {SAsLo(k)}, 0" for k in range(NW)] + [f"v_mov_b32 v{SAS0 + 2 * k + 1}, 0" for k in range(NW)]
+    body += ["s_mov_b32 s34, %[sb]", "s_cmp_eq_u32 s34, 0", f"s_cbranch_scc1 {lbl['exit']}",
+             "s_sub_u32 s34, s34, 1", "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2",
+             "s_load_dword s35, %[kw], s30",
+             f"s_add_u32 s31, %[d], {KOFF}", f"v_mov_b32 {PADR}, s31"]
+    body += chain_prefetch_all() + ["s_waitcnt lgkmcnt(0)", lbl["sq"] + ":"]
+    body += chain_sq_rows()
+    # bit j of the exponent: a short product follows the square
+    body += ["s_and_b32 s30, s34, 31", "s_lshr_b32 s30, s35, s30", "s_and_b32 s30, s30, 1",
+             f"s_cbranch_scc0 {lbl['next']}", f"v_mov_b32 {PADR}, %[d]"]
+    body += chain_normalise(True) + chain_short_rows()
+    body += [lbl["next"] + ":", "s_cmp_eq_u32 s34, 0", f"s_cbranch_scc1 {lbl['exit']}",
+             "s_sub_u32 s34, s34, 1", "s_and_b32 s30, s34, 31", "s_cmp_lg_u32 s30, 31",
+             f"s_cbranch_scc1 {lbl['word']}",
+             # the next 32 exponent bits (no LDS read is in flight here: the counted waits stay exact)
+             "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2", "s_load_dword s35, %[kw], s30",
+             "s_waitcnt lgkmcnt(0)", lbl["word"] + ":",
+             f"s_add_u32 s31, %[d], {KOFF}", f"v_mov_b32 {PADR}, s31"]
+    body += chain_normalise(True) + [f"s_branch {lbl['sq']}", lbl["exit"] + ":"]
+    body += chain_store()
+    return rotate_carries(body)
+
+
+def chain_macros(lines, prefix="FBM_CH_R"):
+    """`lines` as C source: preprocessor macros for what repeats, then the asm body that invokes them.
+    The unrolled rows repeat the same instruction runs with three things varying: the multiply-adds'
+    carry-out pair (rotate_carries alternates it over the whole body), the short rows' multiplier %[h_i],
+    and where a run starts (the triangle's suffixes).  A line becomes a template with the carry pair (A)
+    and the multiplier (X) as parameters; adjacent templates that recur are paired into a macro
+    R(A, B, X) = first(A, B, X) second(A, B, X) -- (B, A) when `first` holds an odd number of
+    multiply-adds -- most frequent pair first (Re-Pair), and a macro used once is written out where it
+    is used.  The preprocessor's expansion is `lines` exactly (tests/test_nadic_chain_asm.py expands
+    the shipped header and compares).  Returns (macro definitions, body)."""
+    import re
+    from collections import Counter
+    text, odd, rule, seq = [], [], {}, []
+    ids = {}
+    for ln in lines:
+        x, t = None, ln
+        if ln.startswith("v_mad"):
+            m = re.search(r"%\[h\d\]", ln)
+            if m:
+                x, t = m.group(0), t.replace(m.group(0), "@X@")
+            for c in CARRY_PAIRS:
+                if f", {c}," in t:
+                    t = t.replace(f", {c},", ", @A@,", 1)
+                    break
+        if t not in ids:
+            ids[t] = len(text)
+            text.append(t)
+            odd.append("@A@" in t)
+        seq.append((ids[t], x))
+
+    def fits(a, b):
+        return a[1] is None or b[1] is None or a[1] == b[1]
+
+    while True:
+        cnt = Counter((seq[i][0], seq[i + 1][0]) for i in range(len(seq) - 1) if fits(seq[i], seq[i + 1]))
+        if not cnt:
+            break
+        pair, c = cnt.most_common(1)[0]
+        if c < 2:
+            break
+        nid = len(text)
+        text.append(None)
+        odd.append(odd[pair[0]] != odd[pair[1]])
+        rule[nid] = pair
+        out, i = [], 0
+        while i < len(seq):
+            if i + 1 < len(seq) and (seq[i][0], seq[i + 1][0]) == pair and fits(seq[i], seq[i + 1]):
+                out.append((nid, seq[i][1] or seq[i + 1][1]))
+                i += 2
+            else:
+                out.append(seq[i])
+                i += 1
+        seq = out
+    uses = Counter(e for pr in rule.values() for e in pr) + Counter(e for e, _ in seq)
+
+    def flat(e):  # a macro's elements: terminals and the macros that stay (used more than once)
+        if e not in rule or uses[e] > 1:
+            return [e]
+        return flat(rule[e][0]) + flat(rule[e][1])
+
+    def emit(elems, xs, a, b, end, width=150):  # the elements in order, packed into source lines
+        out, par, cur = [], False, ""
+        for e, x in zip(elems, xs):
+            pa, pb = (b, a) if par else (a, b)
+            if e in rule:
+                item = f"{prefix}{e}({pa}, {pb}, {x})"
+            else:
+                item = '"' + text[e].replace("@A@", f'" {pa} "').replace("@X@", f'" {x} "') + '\\n"'
+            if cur and len(cur) + 1 + len(item) > width:
+                out.append("  " + cur + end)
+                cur = ""
+            cur += (" " if cur else "") + item
+            par ^= odd[e]
+        return out + ["  " + cur + end]
+
+    defs = []
+    for nid in sorted(rule):
+        if uses[nid] > 1:
+            els = flat(rule[nid][0]) + flat(rule[nid][1])
+            body = emit(els, ["X"] * len(els), "A", "B", " \\")
+            body[-1] = body[-1][:-2]
+            defs += [f"#define {prefix}{nid}(A, B, X) \\"] + body
+    els, xs = [], []
+    for e, x in seq:
+        f = flat(e)
+        els += f
+        xs += [f'"{x}"' if x else '""'] * len(f)
+    return defs, emit(els, xs, *(f'"{c}"' for c in CARRY_PAIRS), "")
+
+
+def chain_defines():
+    return "\n".join(f"#define FBM_NA_{k}_{kind} {v}" for k, c in chain_counts().items()
+                     for kind, v in zip(("VALU", "DS", "SLOAD"), c))
+
+
+def count_kinds(lines):
+    """(VALU, DS, scalar-load) instructions among `lines` (straight-line code: emitted = executed)."""
+    valu = sum(1 for ln in lines if ln.startswith("v_"))
+    return valu, sum(1 for ln in lines if ln.startswith("ds_")), sum(1 for ln in lines if ln.startswith("s_load"))
+
+
+def chain_counts():
+    """What one square / one short product executes inside the chain (its normalise with the
+    prefetch included), and what fbm_na_sq_lds / fbm_na_ms_reg execute per call."""
+    ms_rows = [ln for i in range(KS) for ln in chain_short_row(i)]
+    if CHAIN_SHORT_LOOPED:
+        ms_rows += ["v_mov_b32"] * (KS * (KS - 1))
+    return {"CHAIN_SQ": count_kinds(chain_normalise(True) + chain_sq_rows()),
+            "CHAIN_SHORT": count_kinds(chain_normalise(True) + ms_rows),
+            "CALL_SQ": count_kinds(square_unrolled()), "CALL_SHORT": count_kinds(mul_short_reg())}
+
+
 def sq_mads():
     """64-bit multiply-adds per square: triangular t part (cross products + diagonals), the s part's
     (2 x0) x1 and - q (K' - q), the two q N passes, the mid-product reduction (its kept slots)."""
@@ -760,7 +1109,7 @@ def count_mads(lines):
 
 def main():
     mm, sq, ms = product(False), (square_unrolled() if UNROLLED_SQUARE else square_tri()), mul_short_reg()
-    sq_looped = square_tri()
+    sq_looped, chain = square_tri(), chain_short()
     mm_row, sq_body = row(False, False), sq_row("odd")
     hdr = f"""// GENERATED by tools/gen_nadic_asm.py -- do not edit by hand.
 //
@@ -866,6 +1215,42 @@ __device__ __forceinline__ void fbm_na_sq_lds_looped(uint32_t a_off, const uint3
 """
     with open(OUT, "w") as f:
         f.write(hdr)
+    ch_defs, ch_body = chain_macros(chain)
+    nl = "\n"
+    chain_hdr = f"""// GENERATED by tools/gen_nadic_asm.py -- do not edit by hand.
+//
+// The register-resident chain body of the JL exponentiation's short path (a header of its own: the
+// products of fbm_nadic_asm.hpp, whose register plan, constants block and clobbers it shares).
+#pragma once
+#include "fbm_nadic_asm.hpp"
+
+// VALU / DS / scalar-load instructions one square and one short product execute inside the chain body
+// (the normalise into the next product's B registers with its 36 pair reads, then the rows) and per call
+// of fbm_na_sq_lds / fbm_na_ms_reg
+{chain_defines()}
+
+// The short path's whole binary chain, the running value in registers from product to product
+// ({len(chain)} instructions): X = (h, 0), then for j = sbits - 1 .. 0 a square and, where bit j of the exponent
+// words at kw is set, a short product; the result (h^e 2^-f, as the per-call chain's) normalised into the lane's
+// LDS column a.  d: LDS byte address of the short product's pairs (D'_j, 0), followed by the square's
+// (2^29 - 1 + P'_j, 0) at d + {KOFF}.
+// The body's recurring instruction runs are the macros below (A, B: the multiply-adds' alternating carry-out
+// pairs, X: a short row's limb of h; chain_macros in the generator): the preprocessor expands them to
+// chain_short()'s instruction list, which is what the simulator tests run.
+{nl.join(ch_defs)}
+
+__device__ __forceinline__ void fbm_na_chain_short(uint32_t a_off, const uint32_t (&h)[{KS}], uint32_t d_off,
+                                                   const uint32_t* kw, int sbits, const uint32_t* NK, uint32_t np) {{
+  asm volatile(
+{nl.join(ch_body)}
+      :
+      : [a] "v"(a_off), {", ".join(f'[h{i}] "v"(h[{i}])' for i in range(KS))}, [d] "s"(d_off), [kw] "s"(kw),
+        [sb] "s"(sbits), [NK] "s"(NK), [np] "s"(np)
+      : "memory", "vcc", "scc", FBM_NA_CLOBBERS);
+}}
+"""
+    with open(os.path.join(os.path.dirname(OUT), CHAIN_NAME), "w") as f:  # beside OUT, wherever a caller points it
+        f.write(chain_hdr)
     print(f"wrote {OUT}: general {len(mm)} / square {len(sq)} instructions; "
           f"mads/product {mm_mads()} / {sq_mads()}")
 
