@@ -931,6 +931,25 @@ class jl_chain:
         return self._hooks.__exit__(*exc)
 
 
+class jl_split:
+    """The short path's split exponentiation (for |key| >= N the key's multiple-of-N part worked modulo N;
+    DESIGN.md 5.7) on or off for the one-lane JL launches this thread issues inside (the test build's
+    fbm_jl_set_split; the block's calls run through the test build): off, every key runs the unsplit chain.
+    Results are bit-identical either way -- an A/B and test switch."""
+
+    def __init__(self, on: bool):
+        self._on, self._prev, self._hooks = 1 if on else 0, None, N.test_hooks()
+
+    def __enter__(self):
+        self._hooks.__enter__()
+        self._prev = N.load_test().fbm_jl_set_split(self._on)
+        return self
+
+    def __exit__(self, *exc):
+        N.load_test().fbm_jl_set_split(self._prev)
+        return self._hooks.__exit__(*exc)
+
+
 _clear_hooks = []  # callables run by jl_clear_caches (SecaggCrypter.drop_prepared registers itself)
 
 

@@ -147,6 +147,8 @@ TEST_SIGNATURES = {
     "fbm_jl_set_engine": (c_int, [c_int]),
     "fbm_jl_set_short": (c_int, [c_int]),
     "fbm_jl_set_chain": (c_int, [c_int]),
+    "fbm_jl_set_split": (c_int, [c_int]),
+    "fbm_test_split_consts": (c_int, [c_vp] * 11),
     "fbm_jl_engine_for": (c_int, [c_u64]),
     "fbm_test_true_div_big": (c_int, [c_vp, c_u64, c_vp, c_int, c_int, c_vp]),
     "fbm_test_widen16": (c_int, [ctypes.c_uint16, c_int, c_vp]),

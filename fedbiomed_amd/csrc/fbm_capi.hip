@@ -669,7 +669,7 @@ static void jl_rk_for(const uint32_t* n32, int n_parties, JlRk& r) {
 // Left-to-right sliding window (width FBM_WIN) over |key|, odd-power table.
 static int build_schedule(const uint32_t* key, JlSched& sc, int& is_zero) {
   memset(&sc, 0, sizeof(sc));
-  sc.sbits = -1;  // (build_short)
+  sc.sbits = sc.sb1 = -1;  // (build_short)
   Big K(key, key + 64);
   const int nb = big_bits(K);
   is_zero = nb == 0;
@@ -838,53 +838,31 @@ static void sha256_words(const uint32_t* w, int nw, uint32_t out[8]) {
   wipe(W, sizeof(W));
 }
 
+// The split exponentiation's constants per (N, |key|) (JlShort: c1, cp, one), cached beside C under the same
+// digest and on the same terms: public functions of the key, zeroed when evicted or cleared.
+struct JlSplitCacheEntry {
+  uint32_t digest[8];
+  uint32_t c1[36];
+  uint32_t cp[72];
+  uint32_t one[72];
+};
+static std::vector<JlSplitCacheEntry> g_split_cache;  // guarded by g_jp_mu, at most 32
+
 static void short_cache_clear() {
   std::lock_guard<std::mutex> lk(g_jp_mu);
   for (JlShortCacheEntry& e : g_short_cache) wipe(&e, sizeof(e));
   g_short_cache.clear();
+  for (JlSplitCacheEntry& e : g_split_cache) wipe(&e, sizeof(e));
+  g_split_cache.clear();
 }
 
-// The short path (jl_exp_kernel): possible for N > 2^262 (D = N - 2^261 > the product's quotient
-// m < 2^261); used with a nonzero key.  Returns whether N qualifies (then sh.d is valid and the
-// constants block gets it); sets sc.sbits and sh.kw / sh.corr when the key does too.
-static bool build_short(const uint32_t* biprime, const uint32_t* key, int is_zero, JlSched& sc, JlShort& sh,
-                        bool short_on) {
-  memset(&sh, 0, sizeof(sh));
-  sc.sbits = -1;
-  if (!short_on) return false;
-  Big N(biprime, biprime + 32);
-  big_trim(N);
+// E = L (2^s + 1) + 261 (e - 2^s), L = 1044, s = bit length of e - 1: a binary chain over e (squares that
+// drop R, short products that drop 2^261) leaves h^e 2^-(E - 2L), so 2^E = 2^f R^2 brings it to h^e R
+static Big chain_exponent(const Big& K) {
   const int KSB = FBM_QA_LB * FBM_NA_SHORT_LIMBS;  // 261
-  if (big_bits(N) < KSB + 2 || !(N[0] & 1u)) return false;
-  {  // D = N - 2^261
-    Big D(N.begin(), N.end());
-    Big p(KSB / 32 + 1, 0u);
-    p[KSB / 32] = 1u << (KSB % 32);
-    big_sub_inplace(D, p);
-    to_limbs_host(D, sh.d, FBM_QA_L, FBM_QA_LB);
-  }
-  if (is_zero) return true;
-  Big K(key, key + 64);
-  const int nb = big_bits(K);
-  for (int i = 0; i < 64; ++i) sh.kw[i] = key[i];
-  sc.sbits = nb - 1;
-  uint32_t dg[8];
-  {
-    uint32_t msg[96];
-    memcpy(msg, biprime, 32 * 4);
-    memcpy(msg + 32, key, 64 * 4);
-    sha256_words(msg, 96, dg);
-    wipe(msg, sizeof(msg));
-    std::lock_guard<std::mutex> lk(g_jp_mu);
-    for (const JlShortCacheEntry& e : g_short_cache)
-      if (memcmp(e.digest, dg, sizeof(dg)) == 0) {
-        memcpy(sh.corr, e.corr, sizeof(sh.corr));
-        return true;
-      }
-  }
-  // E = L (2^s + 1) + 261 (|key| - 2^s), L = 1044, s = nb - 1: the chain leaves h^|key| 2^-(E - 2L)
-  const int s = nb - 1;
+  const int s = big_bits(K) - 1;
   Big v(K.begin(), K.end());
+  v.resize(64, 0u);
   v[s >> 5] &= ~(1u << (s & 31));
   Big E(66, 0u);
   uint64_t c = 0;
@@ -909,6 +887,158 @@ static bool build_short(const uint32_t* biprime, const uint32_t* key, int is_zer
   const int Lb = FBM_QA_L * FBM_QA_LB;  // 1044
   add_at((uint64_t)Lb, s);
   add_at((uint64_t)Lb, 0);
+  wipe(v.data(), v.size() * 4);
+  return E;
+}
+
+// N's sliding-window schedule (width FBM_WIN_N) from the accumulator 1: every window, the leading one
+// included, is an op (squarings << FBM_OP_SHIFT | table index + 1).  Returns the op count, or -1.
+static int build_n_schedule(const Big& N, uint16_t* op) {
+  auto bit = [&](int i) -> int { return (N[i >> 5] >> (i & 31)) & 1; };
+  int n = 0, pending = 0;
+  for (int i = big_bits(N) - 1; i >= 0;) {
+    if (!bit(i)) {
+      ++pending;
+      --i;
+      continue;
+    }
+    int l = i - FBM_WIN_N + 1;
+    if (l < 0) l = 0;
+    while (!bit(l)) ++l;
+    int val = 0;
+    for (int j = i; j >= l; --j) val = (val << 1) | bit(j);
+    int nsq = pending + i - l + 1;
+    for (; nsq > FBM_OP_MAXSQ; nsq -= FBM_OP_MAXSQ) {
+      if (n >= FBM_MAX_OPS) return -1;
+      op[n++] = (uint16_t)(FBM_OP_MAXSQ << FBM_OP_SHIFT);
+    }
+    if (n >= FBM_MAX_OPS) return -1;
+    op[n++] = (uint16_t)((nsq << FBM_OP_SHIFT) | ((val - 1) / 2 + 1));
+    pending = 0;
+    i = l - 1;
+  }
+  if (pending > 0) {  // (an even N: outside the short path, kept for completeness)
+    if (n >= FBM_MAX_OPS || pending > FBM_OP_MAXSQ) return -1;
+    op[n++] = (uint16_t)(pending << FBM_OP_SHIFT);
+  }
+  return n;
+}
+
+// The split exponentiation's half of JlShort / JlSched (fbm_internal.hpp) for a key with |key| >= N on the
+// short path's domain; keys below N leave sc.sb1 = -1 (the unsplit chain).  dg: the digest of (N, |key|).
+static void build_split(const Big& N, const uint32_t* key, const uint32_t dg[8], JlSched& sc, JlShort& sh) {
+  Big K(key, key + 64);
+  if (big_cmp(K, N) < 0) return;
+  Big k1, k0;
+  big_divmod(K, N, k1, k0);
+  k1.resize(64, 0u);
+  k0.resize(32, 0u);
+  const int n_nops = build_n_schedule(N, sh.nop);
+  if (n_nops >= 0) {
+    memcpy(sh.k1w, k1.data(), sizeof(sh.k1w));
+    memcpy(sh.k0w, k0.data(), sizeof(sh.k0w));
+    bool hit = false;
+    {
+      std::lock_guard<std::mutex> lk(g_jp_mu);
+      for (const JlSplitCacheEntry& e : g_split_cache)
+        if (memcmp(e.digest, dg, sizeof(e.digest)) == 0) {
+          memcpy(sh.c1, e.c1, sizeof(sh.c1));
+          memcpy(sh.cp, e.cp, sizeof(sh.cp));
+          memcpy(sh.one, e.one, sizeof(sh.one));
+          hit = true;
+          break;
+        }
+    }
+    if (!hit) {
+      Big M = big_mul(N, N);
+      big_trim(M);
+      auto digits = [&](const Big& v, uint32_t* dst) {  // v mod N^2 as the digit pair (v mod N, v div N)
+        Big q, r;
+        big_divmod(v, N, q, r);
+        to_limbs_host(r, dst, FBM_QA_L, FBM_QA_LB);
+        to_limbs_host(q, dst + FBM_QA_L, FBM_QA_L, FBM_QA_LB);
+      };
+      Big E1 = chain_exponent(k1);  // C1 = 2^f1 R^2 mod N
+      to_limbs_host(pow2_mod_big(E1, N), sh.c1, FBM_QA_L, FBM_QA_LB);
+      Big Ep(34, 0u);  // C' = 2^(261 k0 + 1044) mod N^2
+      uint64_t c = (uint64_t)(FBM_QA_L * FBM_QA_LB);
+      for (int i = 0; i < 32; ++i) {
+        c += (uint64_t)k0[i] * (uint64_t)(FBM_QA_LB * FBM_NA_SHORT_LIMBS);
+        Ep[i] = (uint32_t)c;
+        c >>= 32;
+      }
+      Ep[32] = (uint32_t)c;
+      digits(pow2_mod_big(Ep, M), sh.cp);
+      Big Eo(1, (uint32_t)(FBM_QA_L * FBM_QA_LB));  // the Montgomery one, R mod N^2
+      digits(pow2_mod_big(Eo, M), sh.one);
+      wipe(E1.data(), E1.size() * 4);
+      wipe(Ep.data(), Ep.size() * 4);
+      JlSplitCacheEntry e;
+      memcpy(e.digest, dg, sizeof(e.digest));
+      memcpy(e.c1, sh.c1, sizeof(e.c1));
+      memcpy(e.cp, sh.cp, sizeof(e.cp));
+      memcpy(e.one, sh.one, sizeof(e.one));
+      std::lock_guard<std::mutex> lk(g_jp_mu);
+      if (g_split_cache.size() >= 32) {
+        wipe(&g_split_cache.front(), sizeof(JlSplitCacheEntry));
+        g_split_cache.erase(g_split_cache.begin());
+      }
+      g_split_cache.push_back(e);
+      wipe(&e, sizeof(e));
+    }
+    sc.sb1 = big_bits(k1) - 1;
+    sc.n_nops = n_nops;
+    sc.nbn = big_bits(N);
+  }
+  wipe(K.data(), K.size() * 4);
+  wipe(k1.data(), k1.size() * 4);
+  wipe(k0.data(), k0.size() * 4);
+}
+
+// The short path (jl_exp_kernel): possible for N > 2^262 (D = N - 2^261 > the product's quotient
+// m < 2^261); used with a nonzero key.  Returns whether N qualifies (then sh.d is valid and the
+// constants block gets it); sets sc.sbits and sh.kw / sh.corr when the key does too.
+static bool build_short(const uint32_t* biprime, const uint32_t* key, int is_zero, JlSched& sc, JlShort& sh,
+                        bool short_on) {
+  memset(&sh, 0, sizeof(sh));
+  sc.sbits = sc.sb1 = -1;
+  sc.n_nops = sc.nbn = 0;
+  if (!short_on) return false;
+  Big N(biprime, biprime + 32);
+  big_trim(N);
+  const int KSB = FBM_QA_LB * FBM_NA_SHORT_LIMBS;  // 261
+  if (big_bits(N) < KSB + 2 || !(N[0] & 1u)) return false;
+  {  // D = N - 2^261
+    Big D(N.begin(), N.end());
+    Big p(KSB / 32 + 1, 0u);
+    p[KSB / 32] = 1u << (KSB % 32);
+    big_sub_inplace(D, p);
+    to_limbs_host(D, sh.d, FBM_QA_L, FBM_QA_LB);
+  }
+  if (is_zero) return true;
+  Big K(key, key + 64);
+  const int nb = big_bits(K);
+  for (int i = 0; i < 64; ++i) sh.kw[i] = key[i];
+  sc.sbits = nb - 1;
+  uint32_t dg[8];
+  {
+    uint32_t msg[96];
+    memcpy(msg, biprime, 32 * 4);
+    memcpy(msg + 32, key, 64 * 4);
+    sha256_words(msg, 96, dg);
+    wipe(msg, sizeof(msg));
+  }
+  build_split(N, key, dg, sc, sh);
+  {
+    std::lock_guard<std::mutex> lk(g_jp_mu);
+    for (const JlShortCacheEntry& e : g_short_cache)
+      if (memcmp(e.digest, dg, sizeof(dg)) == 0) {
+        memcpy(sh.corr, e.corr, sizeof(sh.corr));
+        return true;
+      }
+  }
+  // E = L (2^s + 1) + 261 (|key| - 2^s), L = 1044, s = nb - 1: the chain leaves h^|key| 2^-(E - 2L)
+  Big E = chain_exponent(K);
   Big M = big_mul(N, N);
   big_trim(M);
   const Big C = pow2_mod_big(E, M);
@@ -916,8 +1046,7 @@ static bool build_short(const uint32_t* biprime, const uint32_t* key, int is_zer
   big_divmod(C, N, q, r);
   to_limbs_host(r, sh.corr, FBM_QA_L, FBM_QA_LB);
   to_limbs_host(q, sh.corr + FBM_QA_L, FBM_QA_L, FBM_QA_LB);
-  wipe(v.data(), v.size() * 4);  // (K, v, E: the key and its exponent -- not kept)
-  wipe(K.data(), K.size() * 4);
+  wipe(K.data(), K.size() * 4);  // (K, E: the key and its exponent -- not kept)
   wipe(E.data(), E.size() * 4);
   JlShortCacheEntry e;
   memcpy(e.digest, dg, sizeof(dg));
@@ -2237,6 +2366,8 @@ int fbm_jl_engine_for(uint64_t n_ct) { return jl_engine_for(n_ct); }
 
 int fbm_jl_set_chain(int percall) { return jl_chain_set(percall); }
 
+int fbm_jl_set_split(int on) { return jl_split_set(on); }
+
 int fbm_jl_set_short(int on) {
   const int prev = t_short_on;
   t_short_on = on ? 1 : 0;
@@ -2356,6 +2487,31 @@ int fbm_test_short_consts(const uint32_t* n32, const uint32_t* key, uint32_t* kw
   memcpy(corr, sh.corr, sizeof(sh.corr));
   memcpy(d, sh.d, sizeof(sh.d));
   return q ? sc.sbits : -2;
+}
+
+int fbm_test_split_consts(const uint32_t* n32, const uint32_t* key, uint32_t* k1w, uint32_t* k0w, uint32_t* c1,
+                          uint32_t* cp, uint32_t* one, uint16_t* nops512, int* n_nops, int* nbn, int* win) {
+  if (!n32 || !key || !k1w || !k0w || !c1 || !cp || !one || !nops512 || !n_nops || !nbn || !win) {
+    set_error("fbm_test_split_consts: null pointer");
+    return FBM_E_ARG;
+  }
+  JlSched sc;
+  int is_zero = 0;
+  int rc = build_schedule(key, sc, is_zero);
+  if (rc) return rc;
+  JlShort sh;
+  const bool q = build_short(n32, key, is_zero, sc, sh, true);
+  memcpy(k1w, sh.k1w, sizeof(sh.k1w));
+  memcpy(k0w, sh.k0w, sizeof(sh.k0w));
+  memcpy(c1, sh.c1, sizeof(sh.c1));
+  memcpy(cp, sh.cp, sizeof(sh.cp));
+  memcpy(one, sh.one, sizeof(sh.one));
+  memcpy(nops512, sh.nop, sizeof(sh.nop));
+  *n_nops = sc.n_nops;
+  *nbn = sc.nbn;
+  *win = FBM_WIN_N;
+  wipe(&sh, sizeof(sh));
+  return q ? sc.sb1 : -2;
 }
 
 int fbm_test_schedule(const uint32_t* key64, uint16_t* ops512, int* n_ops, int* first) {

@@ -76,7 +76,24 @@ int launch_lom_aggregate(const uint64_t* y, int n_parties, uint64_t n, uint64_t 
 // C's broadcast column: limb k at word FBM_OPS_CBC + 256 k (the one-lane engine reads it as a B operand
 // with a zero lane offset: every lane the same address)
 #define FBM_OPS_CBC (((FBM_MAX_OPS + 64 + 128) + 255) / 256 * 256)
-#define FBM_OPS_WORDS (FBM_OPS_CBC + 72 * 256)
+// the split exponentiation's per-call words (JlShort below), after C's column: k1's and k0's
+// words, the Montgomery one R mod N^2 (N-adic digits), N's window schedule, and the broadcast columns of
+// C1 (digit 1 zero) and C'
+#define FBM_OPS_K1W (FBM_OPS_CBC + 72 * 256)
+#define FBM_OPS_K0W (FBM_OPS_K1W + 64)
+#define FBM_OPS_ONE (FBM_OPS_K0W + 64)
+#define FBM_OPS_NOPS (FBM_OPS_ONE + 128)
+#define FBM_OPS_C1BC (FBM_OPS_NOPS + FBM_MAX_OPS)
+#define FBM_OPS_CPBC (FBM_OPS_C1BC + 72 * 256)
+#define FBM_OPS_WORDS (FBM_OPS_CPBC + 72 * 256)
+// window width of N's schedule (phase 2 of the split exponentiation): 2^(w-1) odd powers of g1 per lane
+// in the table buffer (which holds FBM_TABLE).  A/B on MI355X, the 10M x 8 step (profiles/r8_window_ab.jsonl):
+// 860.7 / 830.4 / 814.8 / 809.3 ms at widths 3 / 4 / 5 / 6 (the parent's unsplit chain: 958.1)
+#ifndef FBM_WIN_N
+#define FBM_WIN_N 6
+#endif
+#define FBM_TABLE_N (1 << (FBM_WIN_N - 1))
+static_assert(FBM_WIN_N >= 1 && FBM_WIN_N <= FBM_WIN, "N's window table lives in the key's table buffer");
 
 // per-call device constants (words): M, R^2 (74 limbs, padded to 128), the broadcast
 // column 1 (limb k at word k*256) and R^(P+1) mod M (the aggregate's uniform first operand,
@@ -126,6 +143,9 @@ struct JlSched {
   int first;       // table index of the leading window
   uint16_t op[FBM_MAX_OPS];
   int sbits;
+  // the SPLIT short path (JlShort's second half): sb1 = bit length of k1 - 1 (-1: no split), n_nops ops
+  // in N's schedule, nbn = bit length of N
+  int sb1, n_nops, nbn;
 };
 // The SHORT path (one FDH digest h < 2^261, N > 2^262): left-to-right binary over |key| with the
 // short-base product (fbm_na_ms_glb) -- kw = |key|'s words, corr = C = 2^(1044 (2^sbits + 1) +
@@ -136,6 +156,20 @@ struct JlShort {
   uint32_t kw[64];
   uint32_t corr[72];
   uint32_t d[36];
+  // The SPLIT exponentiation (|key| >= N): |key| = k1 N + k0 and
+  //   h^|key| = (h^k1 mod N)^N h^k0 (mod N^2).
+  // Phase 1 is the binary chain over k1 modulo N (fbm_na_chain_modn), which leaves h^k1 2^-f1 with
+  // f1 = 1044 (2^sb1 - 1) + 261 (k1 - 2^sb1); c1 = 2^f1 R^2 mod N turns it into g1 R.  Phase 2 runs nop,
+  // N's sliding-window schedule from the accumulator `one` = R mod N^2 (the leading window an op like the
+  // others), each op's squarings as a chain segment over the same bits of k0 (a short product by h where
+  // k0's bit is set: they leave 2^(-261 k0)), then its product by an odd power of g1; cp = C' =
+  // 2^(261 k0) R mod N^2 ends it at h^|key| R.
+  uint32_t k1w[64];
+  uint32_t k0w[32];
+  uint32_t c1[36];
+  uint32_t cp[72];
+  uint32_t one[72];
+  uint16_t nop[FBM_MAX_OPS];
 };
 
 // N-adic constants.  nk: N's 28-bit limbs, words 0..9 = N_0..N_9, 16..42 = N_10..N_36 (the
@@ -221,6 +255,7 @@ struct JlExpSeg {
   uint32_t chunk0;  // first chunk of this segment in the launch's chunk sequence
   int n_ops, first, mode, key_is_zero;
   int sbits;        // JlSched::sbits (the short path's exponent bits - 1, or -1)
+  int sb1, n_nops, nbn;  // JlSched's: the split short path (sb1 = -1: the unsplit chain)
 };
 struct JlExpBatch {
   int nseg;
@@ -317,6 +352,7 @@ uint64_t jl_table_slots();
 int jl_engine_policy();
 int jl_engine_set(int mode);
 int jl_chain_set(int percall);
+int jl_split_set(int on);
 int jl_engine_for(uint64_t n_ct);
 uint64_t jl_table_bytes(uint64_t n_ct);
 // compute units of the calling thread's current device (cached per device)

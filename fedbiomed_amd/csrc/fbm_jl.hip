@@ -1002,7 +1002,8 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_exp_kernel(const uint32_t* __
                                                              uint32_t* __restrict__ out_a,
                                                              const JlExpSeg* __restrict__ segs, int nseg,
                                                              uint32_t total_chunks, uint32_t* __restrict__ ctr,
-                                                             const uint32_t* __restrict__ Hc_a) {
+                                                             const uint32_t* __restrict__ Hc_a, int sb1_a,
+                                                             int n_nops_a, int nbn_a) {
   __shared__ uint32_t lds_a[(FBM_NL + 1) * FBM_BLOCK];
   __shared__ uint32_t chunk_s;
   const int tid = threadIdx.x;
@@ -1106,6 +1107,45 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_exp_kernel(const uint32_t* __
       // per-product loop (an asm block per product, operands through the LDS column) stays for the test
       // build's switch (FBM_EXP_PERCALL: fbm_jl_set_chain) unless compiled out (-DFBM_EXP_PERCALL_CHAIN=0).
       const uint32_t* kw = SEG(ops, ops_a) + FBM_OPS_KW;
+      const int sb1 = SEG(sb1, sb1_a);
+      if (sb1 >= 0 && !(SEG(mode, mode_a) & FBM_EXP_PERCALL)) {
+        // The SPLIT path (|key| = k1 N + k0 >= N): h^|key| = (h^k1 mod N)^N h^k0 (mod N^2).
+        // Phase 1, modulo N: the binary chain over k1 with the t half of either product only, then C1
+        // (= 2^f1 R^2 mod N, digit 1 zero) -> g1 R; the s digit that product leaves is a multiple of N
+        // beside g1, which the N-th power does not see.
+        const uint32_t* sops = SEG(ops, ops_a);
+        fbm_na_chain_modn(aoff, hs, uniform_val(sops + FBM_OPS_K1W), sb1, NK, np);
+        fbm_na_mm_glb(aoff, sops + FBM_OPS_C1BC, 0u, NK, np);
+        // g1's odd powers, as the window path's table of h's
+        lds_to_glb(lds, table + tb0 / 4);
+        if (FBM_TABLE_N > 1) {
+          fbm_na_sq_lds_looped(aoff, NK, np);  // g1^2 R
+          lds_to_glb(lds, table + (tb0 + FBM_TSCRATCH * tstride) / 4);
+          glb_to_lds(table + tb0 / 4, lds);
+#pragma unroll 1
+          for (int t = 1; t < FBM_TABLE_N; ++t) {
+            fbm_na_mm_glb(aoff, table, tb0 + FBM_TSCRATCH * tstride, NK, np);
+            lds_to_glb(lds, table + (tb0 + (uint32_t)t * tstride) / 4);
+          }
+        }
+        // Phase 2: N's window schedule from the Montgomery one; each op's squarings are a segment of the
+        // chain over the same bits of k0 (a short product by h where k0's bit is set), then the product by
+        // the op's power of g1.  C' = 2^(261 k0) R takes back what the short products left.
+        lds_store_uniform<2 * NA>(lds, FBM_BLOCK, sops + FBM_OPS_ONE);
+        const uint32_t* k0w = sops + FBM_OPS_K0W;
+        const int n_nops = SEG(n_nops, n_nops_a);
+        int j = SEG(nbn, nbn_a);
+#pragma unroll 1
+        for (int k = 0; k < n_nops; ++k) {
+          const uint32_t op = __builtin_amdgcn_readfirstlane(launder_s(sops)[FBM_OPS_NOPS + k]);
+          const int nsq = (int)(op >> FBM_OP_SHIFT);
+          const int idx = (int)(op & ((1u << FBM_OP_SHIFT) - 1u)) - 1;
+          fbm_na_chain_seg(aoff, hs, uniform_val(doff), uniform_val(k0w), j, j - nsq, NK, np);
+          j -= nsq;
+          if (idx >= 0) fbm_na_mm_glb(aoff, table, tb0 + (uint32_t)idx * tstride, NK, np);
+        }
+        fbm_na_mm_glb(aoff, sops + FBM_OPS_CPBC, 0u, NK, np);
+      } else {
 #if FBM_EXP_PERCALL_CHAIN
       if (SEG(mode, mode_a) & FBM_EXP_PERCALL) {
         uint32_t w = 0;
@@ -1122,6 +1162,7 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_exp_kernel(const uint32_t* __
       // x C: the chain stays the LDS operand, C (uniform) is the B operand read from its broadcast
       // column in the ops buffer (limb k at word k * 256, every lane the same address)
       fbm_na_mm_glb(aoff, SEG(ops, ops_a) + FBM_OPS_CBC, 0u, NK, np);
+      }  // (the unsplit chain)
     } else {
 #ifndef FBM_EXP_SHORT_ONLY  // (a measurement variant: the launch's code without the table path)
     if (__any(wide)) {  // wave-uniform: lanes with a narrow h multiply 0 and add nothing
@@ -2235,6 +2276,15 @@ __global__ void jl_short_setup_kernel(JlShort sh, uint32_t* __restrict__ ops, ui
   if (t < 72) ops[FBM_OPS_CORR + t] = sh.corr[t];
   if (t < 72) ops[FBM_OPS_CBC + t * 256] = sh.corr[t];  // C's broadcast column (the one-lane engine's B)
   if (t < 72) cst[FBM_CST_QD + t] = (t & 1) ? 0u : sh.d[t >> 1];
+  // the split exponentiation's words (JlShort; unread when the schedule has no split)
+  if (t < 64) ops[FBM_OPS_K1W + t] = sh.k1w[t];
+  if (t < 64) ops[FBM_OPS_K0W + t] = t < 32 ? sh.k0w[t] : 0u;
+  if (t < 72) {
+    ops[FBM_OPS_ONE + t] = sh.one[t];
+    ops[FBM_OPS_C1BC + t * 256] = t < FBM_QA_L ? sh.c1[t] : 0u;
+    ops[FBM_OPS_CPBC + t * 256] = sh.cp[t];
+  }
+  for (int i = t; i < FBM_MAX_OPS; i += blockDim.x) ops[FBM_OPS_NOPS + i] = sh.nop[i];
 }
 
 int launch_jl_setup(const JlParams& jp, const JlSched& sc, uint32_t* ops, uint32_t* cst, hipStream_t s,
@@ -2338,6 +2388,7 @@ struct JlBatchState {
   uint32_t np = 0;
 };
 static thread_local JlBatchState g_batch;
+static thread_local int t_unsplit = 0;  // jl_split_set
 
 bool jl_batch_active() { return g_batch.active; }
 
@@ -2393,7 +2444,8 @@ static int jl_batch_record(const uint32_t* H, uint64_t n_ct, const JlParams& jp,
     return FBM_E_UNSUPPORTED;
   }
   bt.seg[bt.nseg++] =
-      JlExpSeg{H, Hc, nude, out, ops, n_ct, bt.total_chunks, sc.n_ops, sc.first, mode, jp.key_is_zero, sc.sbits};
+      JlExpSeg{H, Hc, nude, out, ops, n_ct, bt.total_chunks, sc.n_ops, sc.first, mode, jp.key_is_zero, sc.sbits,
+               t_unsplit ? -1 : sc.sb1, sc.n_nops, sc.nbn};
   bt.total_chunks += (uint32_t)chunks;
   return FBM_OK;
 }
@@ -2416,6 +2468,15 @@ static thread_local int t_chain_percall = 0;
 int jl_chain_set(int percall) {
   const int prev = t_chain_percall;
   t_chain_percall = percall ? 1 : 0;
+  return prev;
+}
+
+// The split exponentiation of the CALLING THREAD's one-lane launches: taken whenever the
+// schedule has one (the default, the product library's only form), or 0: the unsplit chain (the test build's
+// fbm_jl_set_split: an A/B and test switch, bit-identical results).
+int jl_split_set(int on) {
+  const int prev = t_unsplit ? 0 : 1;
+  t_unsplit = on ? 0 : 1;
   return prev;
 }
 
@@ -2468,7 +2529,7 @@ int launch_jl_exp(const uint32_t* H, uint64_t n_ct, const JlParams& jp, const Jl
 #endif
   hipLaunchKernelGGL(jl_exp_kernel<false>, dim3((unsigned)g), dim3(FBM_BLOCK), lds_pad, s, H, n_ct, (uint32_t*)cst, jp.qa.np,
                      ops, sc.n_ops, sc.first, mode, jp.key_is_zero, sc.sbits, nude, table, out, (const JlExpSeg*)nullptr,
-                     0, 0u, (uint32_t*)nullptr, Hc);
+                     0, 0u, (uint32_t*)nullptr, Hc, t_unsplit ? -1 : sc.sb1, sc.n_nops, sc.nbn);
   return check_launch("jl_exp_kernel");
 }
 
@@ -2496,7 +2557,8 @@ int jl_batch_flush(void* workspace, uint64_t ws_bytes, hipStream_t s) {
   if (g > gmax) g = gmax;
   hipLaunchKernelGGL(jl_exp_kernel<true>, dim3((unsigned)g), dim3(FBM_BLOCK), 0, s, (const uint32_t*)nullptr, (uint64_t)0,
                      (uint32_t*)g_batch.cst, g_batch.np, (const uint32_t*)nullptr, 0, 0, 0, 0, -1, (const uint32_t*)nullptr,
-                     table, (uint32_t*)nullptr, (const JlExpSeg*)segs, bt.nseg, bt.total_chunks, ctr, (const uint32_t*)nullptr);
+                     table, (uint32_t*)nullptr, (const JlExpSeg*)segs, bt.nseg, bt.total_chunks, ctr, (const uint32_t*)nullptr,
+                     -1, 0, 0);
   return check_launch("jl_exp_kernel (batch)");
 }
 

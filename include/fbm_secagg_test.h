@@ -67,6 +67,12 @@ int fbm_jl_set_short(int on);
  * (an assembly block per product, operands through the lane's LDS column): an A/B and test switch;
  * results are bit-identical.  Returns the previous setting. */
 int fbm_jl_set_chain(int percall);
+/* The short path's split exponentiation for the CALLING THREAD's one-lane launches (for
+ * |key| = k1 N + k0 >= N, h^|key| = (h^k1 mod N)^N h^k0 mod N^2 -- the key's upper half worked modulo N):
+ * 1 (the default) taken whenever the key's schedule has a split, 0 the unsplit chain for every key: an A/B
+ * and test switch; results are bit-identical.  The per-product chain (fbm_jl_set_chain(1)) is always
+ * unsplit.  Returns the previous setting. */
+int fbm_jl_set_split(int on);
 
 /* ---- host test hook (no GPU): the device modular-inverse routine (Bernstein-Yang divsteps,
  * fedbiomed_amd/csrc/fbm_safegcd.hpp) run on the host, for unit tests.
@@ -96,6 +102,15 @@ int fbm_test_nadic_consts(const uint32_t* n32, uint32_t* nk, uint32_t* r2na, uin
  * mod N^2), d: 36 limbs of N - 2^261.  Returns s = bit length of |key| - 1 (-1 for a zero key), or
  * -2 when N is outside the path's domain (N <= 2^262 or even). */
 int fbm_test_short_consts(const uint32_t* n32, const uint32_t* key, uint32_t* kw, uint32_t* corr, uint32_t* d);
+/* host test hook (no GPU): the split exponentiation's per-call words as the library builds them for
+ * |key| = k1 N + k0 (key: 64 words) -- k1w: k1's 64 words, k0w: k0's 32, c1: 36 29-bit limbs of
+ * C1 = 2^f1 R^2 mod N (f1 = 1044 (2^s1 - 1) + 261 (k1 - 2^s1), R = 2^1044), cp / one: 72 limbs each, the
+ * N-adic digits of C' = 2^(261 k0) R mod N^2 and of R mod N^2, nops512: N's window schedule from the
+ * accumulator 1 (ops as fbm_test_schedule's, the leading window included), *n_nops of them valid; *nbn: the
+ * bit length of N; *win: the schedule's window width.  Returns s1 = bit length of k1 - 1, -1 when the key has
+ * no split (|key| < N), or -2 when N is outside the short path's domain. */
+int fbm_test_split_consts(const uint32_t* n32, const uint32_t* key, uint32_t* k1w, uint32_t* k0w, uint32_t* c1,
+                          uint32_t* cp, uint32_t* one, uint16_t* nops512, int* n_nops, int* nbn, int* win);
 /* host test hook (no GPU): the table path's sliding-window schedule of |key| (64 words) as the library
  * builds it (build_schedule) -- ops512: FBM_MAX_OPS = 512 u16 ops, op k = (squarings before the multiply)
  * << 6 | (table index + 1, 0 = no multiply), the first *n_ops of them valid; *first: the table index of

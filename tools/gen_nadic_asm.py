@@ -53,7 +53,8 @@ column itself.  The constants block (80 words, FBM_CST_NA29 in fbm_internal.hpp)
 N_0..N_9 at words 0..9, N_10..N_35 at words 16..41 and K'_0..K'_35 at words 42..77.
 
 Usage:  python tools/gen_nadic_asm.py   (rewrites the header and, beside it, fbm_nadic_chain_asm.hpp: the
-        short path's register-resident chain body, chain_short below; the build does not run this)
+        short path's register-resident chain body, chain_short below, and the split exponentiation's two
+        bodies, chain_modn and chain_seg; the build does not run this)
 """
 
 import os
@@ -967,6 +968,183 @@ def chain_short():
     return rotate_carries(body)
 
 
+# ------------------------------------------------------------------------------------------
+# The split exponentiation (round 8): |key| = k1 N + k0 and
+#     h^|key| = (h^k1 mod N)^N h^k0   (mod N^2)
+# (y = y' mod N gives y^N = y'^N mod N^2).  Two more bodies on the chain's register plan:
+#
+# chain_modn(): PHASE 1, h^k1 modulo N -- chain_short()'s binary chain with only the t half of the
+#   square and of the short product: x0 only, one quotient per row, no s window, no LDS pairs.  The t
+#   part of either product never reads the s part, so its multiplies, their order, the t slots of the
+#   mid-product reduction and the column bounds are square_unrolled()'s / mul_short_reg()'s t half, and
+#   its limbs are theirs whatever the s digit (tests/test_nadic_split_asm.py).  It exits by storing
+#   (x0, 0) into the lane's LDS column.
+# chain_seg(): a SEGMENT of the modulo-N^2 chain for phase 2 -- X enters from the lane's LDS column,
+#   the exponent bits %[hi] - 1 .. %[lo] of the words at %[kw] are run (a square per bit, a short
+#   product where the bit is set) and the result leaves through the normalise-and-store; between two
+#   segments the kernel multiplies the column by a window-table entry (fbm_na_mm_glb).
+# ------------------------------------------------------------------------------------------
+def modn_sq_row(i):
+    """The t half of chain_sq_row(i)."""
+    first, last, even = i == 0, i == L - 1, i % 2 == 0
+    out = []
+    if even:
+        out.append(f"v_mad_u64_u32 {SAt(0)}, vcc, {SB0(i // 2)}, {SB0(i // 2)}, {'0' if first else SAt(0)}")
+    out.append(f"v_mul_lo_u32 {SQ}, {SAtLo(0)}, {SNPV}")
+    cross = []
+    for k in range(i + 1, L):
+        addend = "0" if (first or k == L - 1) else SAt(k)
+        cross.append(f"v_mad_u64_u32 {SAt(k)}, vcc, {SX0D}, {SB0(k)}, {addend}")
+    out += cross[:2] + [f"v_and_b32 {SQ}, {MASK}, {SQ}"] + cross[2:]
+    top = "0" if last else SAt(L - 1)
+    out.append(f"v_mad_u64_u32 {STT}, vcc, {SQ}, {Ns(0)}, {SAt(0)}")
+    for k in range(1, L):
+        out.append(f"v_mad_u64_u32 {SAt(k - 1)}, vcc, {SQ}, {Ns(k)}, {SAt(k) if k < L - 1 else top}")
+    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}"]
+    if not last:
+        out.append(f"v_lshlrev_b32 {SX0D}, 1, {SB0(i + 1)}")
+    return out
+
+
+def modn_sq_rows():
+    """The unrolled triangular square modulo N on SB0: window out (the t half of chain_sq_rows())."""
+    assert SQ_KFOLD and UNROLLED_SQUARE and SQ_MID_KEEP is not None
+    body = [f"v_lshlrev_b32 {SX0D}, 1, {SB0(0)}"]
+    t_regs = [SAtLo(k) for k in range(L - 1)]
+    for i in range(L):
+        body += modn_sq_row(i)
+        if i == SQ_MID_T - 1:
+            body += mid_reduce([t_regs], keep=[SQ_MID_KEEP[0]], one=[set()])
+    body += [f"v_mad_u64_u32 {SAt(2 * h - L)}, vcc, {SB0(h)}, {SB0(h)}, {SAt(2 * h - L)}" for h in range(L // 2, L)]
+    return body
+
+
+def modn_short_row(i):
+    """The t half of chain_short_row(i)."""
+    x, first = f"%[h{i}]", i == 0
+    out = [f"v_mad_u64_u32 {STT}, vcc, {x}, {SB0(0)}, {'0' if first else SAt(0)}"]
+    for j in range(1, L):
+        addend = "0" if (first or j == NW) else SAt(j)
+        out.append(f"v_mad_u64_u32 {SAt(j - 1)}, vcc, {x}, {SB0(j)}, {addend}")
+        if j == 3:
+            out.append(f"v_mul_lo_u32 {SQ}, {STTLO}, {SNPV}")
+        if j == 6:
+            out.append(f"v_and_b32 {SQ}, {MASK}, {SQ}")
+    out.append(f"v_mad_u64_u32 {STT}, vcc, {SQ}, {Ns(0)}, {STT}")
+    for j in range(1, L):
+        out.append(f"v_mad_u64_u32 {SAt(j - 1)}, vcc, {SQ}, {Ns(j)}, {SAt(j - 1)}")
+    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}"]
+    return out
+
+
+def modn_short_rows():
+    return [ln for i in range(KS) for ln in modn_short_row(i)]
+
+
+def modn_normalise():
+    """The t window -> SB0 (the t half of chain_normalise)."""
+    out = [f"v_lshrrev_b64 {STT}, {LB}, {SAt(0)}", f"v_and_b32 {SB0(0)}, {MASK}, {SAtLo(0)}"]
+    for k in range(1, NW):
+        out += [f"v_lshl_add_u64 {SAt(k)}, {STT}, 0, {SAt(k)}",
+                f"v_lshrrev_b64 {STT}, {LB}, {SAt(k)}",
+                f"v_and_b32 {SB0(k)}, {MASK}, {SAtLo(k)}"]
+    out.append(f"v_mov_b32 {SB0(NW)}, {STTLO}")
+    return out
+
+
+def modn_store():
+    """Phase 1's exit: the t window normalised into digit 0 of the lane's LDS column, digit 1 = 0."""
+    out = [f"v_add_u32 {STMP}, 0x10000, %[a]"]
+
+    def st(k, reg):
+        if k < 64:
+            return f"ds_write_b32 %[a], {reg} offset:{k * 1024}"
+        return f"ds_write_b32 {STMP}, {reg} offset:{(k - 64) * 1024}"
+
+    out += [f"v_lshrrev_b64 {STT}, {LB}, {SAt(0)}", f"v_and_b32 {SAtLo(0)}, {MASK}, {SAtLo(0)}", st(0, SAtLo(0))]
+    for k in range(1, NW):
+        out += [f"v_lshl_add_u64 {SAt(k)}, {STT}, 0, {SAt(k)}",
+                f"v_lshrrev_b64 {STT}, {LB}, {SAt(k)}",
+                f"v_and_b32 {SAtLo(k)}, {MASK}, {SAtLo(k)}",
+                st(k, SAtLo(k))]
+    out += [st(NW, STTLO), f"v_mov_b32 {STSLO}, 0"]
+    out += [st(L + k, STSLO) for k in range(L)]
+    out.append("s_waitcnt lgkmcnt(0)")
+    return out
+
+
+def modn_one(short):
+    """One product of phase 1 as a body of its own, x0 in SB0 and out in SB0 (the simulator tests)."""
+    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]", "s_waitcnt lgkmcnt(0)"]
+    body += modn_short_rows() if short else modn_sq_rows()
+    return rotate_carries(body + modn_normalise())
+
+
+def chain_modn():
+    """Phase 1: x0 = h, then for j = sbits - 1 .. 0 a square modulo N and, where bit j of the exponent
+    (%[kw]'s words: k1) is set, a short product; (x0, 0) stored into the LDS column."""
+    lbl = {k: f".Lfbm_cn_{k}_%=" for k in ("sq", "next", "exit", "word")}
+    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]"]
+    body += [f"v_mov_b32 {SB0(i)}, " + (f"%[h{i}]" if i < KS else "0") for i in range(L)]
+    # zero iterations (k1 = 1): the store below normalises the window, so x0 goes through it
+    body += [f"v_mov_b32 {SAtLo(k)}, {SB0(k)}" for k in range(NW)] + [f"v_mov_b32 v{2 * k + 1}, 0" for k in range(NW)]
+    body += ["s_mov_b32 s34, %[sb]", "s_cmp_eq_u32 s34, 0", f"s_cbranch_scc1 {lbl['exit']}",
+             "s_sub_u32 s34, s34, 1", "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2",
+             "s_load_dword s35, %[kw], s30", "s_waitcnt lgkmcnt(0)", lbl["sq"] + ":"]
+    body += modn_sq_rows()
+    body += ["s_and_b32 s30, s34, 31", "s_lshr_b32 s30, s35, s30", "s_and_b32 s30, s30, 1",
+             f"s_cbranch_scc0 {lbl['next']}"]
+    body += modn_normalise() + modn_short_rows()
+    body += [lbl["next"] + ":", "s_cmp_eq_u32 s34, 0", f"s_cbranch_scc1 {lbl['exit']}",
+             "s_sub_u32 s34, s34, 1", "s_and_b32 s30, s34, 31", "s_cmp_lg_u32 s30, 31",
+             f"s_cbranch_scc1 {lbl['word']}",
+             "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2", "s_load_dword s35, %[kw], s30",
+             "s_waitcnt lgkmcnt(0)", lbl["word"] + ":"]
+    body += modn_normalise() + [f"s_branch {lbl['sq']}", lbl["exit"] + ":"]
+    body += ["s_waitcnt lgkmcnt(0)"] + modn_store()
+    return rotate_carries(body)
+
+
+def chain_seg():
+    """A segment of the modulo-N^2 chain: X from the lane's LDS column, then for j = %[hi] - 1 .. %[lo] a
+    square and, where bit j of the words at %[kw] is set, a short product; X back into the column.
+    %[hi] == %[lo]: nothing is run and the column stays as it is."""
+    lbl = {k: f".Lfbm_cs_{k}_%=" for k in ("sq", "next", "exit", "word", "done")}
+    body = ["s_cmp_eq_u32 %[hi], %[lo]", f"s_cbranch_scc1 {lbl['done']}"]
+    body += load_consts() + [f"v_mov_b32 {SNPV}, %[np]", f"v_add_u32 {STMP}, 0x10000, %[a]"]
+    for j in range(2 * L):
+        reg = SB0(j) if j < L else SB1(j - L)
+        if j < 64:
+            body.append(f"ds_read_b32 {reg}, %[a] offset:{j * 1024}")
+        else:
+            body.append(f"ds_read_b32 {reg}, {STMP} offset:{(j - 64) * 1024}")
+    body += ["s_sub_u32 s34, %[hi], 1", "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2",
+             "s_load_dword s35, %[kw], s30",
+             f"s_add_u32 s31, %[d], {KOFF}", f"v_mov_b32 {PADR}, s31"]
+    body += chain_prefetch_all() + ["s_waitcnt lgkmcnt(0)", lbl["sq"] + ":"]
+    body += chain_sq_rows()
+    body += ["s_and_b32 s30, s34, 31", "s_lshr_b32 s30, s35, s30", "s_and_b32 s30, s30, 1",
+             f"s_cbranch_scc0 {lbl['next']}", f"v_mov_b32 {PADR}, %[d]"]
+    body += chain_normalise(True) + chain_short_rows()
+    body += [lbl["next"] + ":", "s_cmp_eq_u32 s34, %[lo]", f"s_cbranch_scc1 {lbl['exit']}",
+             "s_sub_u32 s34, s34, 1", "s_and_b32 s30, s34, 31", "s_cmp_lg_u32 s30, 31",
+             f"s_cbranch_scc1 {lbl['word']}",
+             "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2", "s_load_dword s35, %[kw], s30",
+             "s_waitcnt lgkmcnt(0)", lbl["word"] + ":",
+             f"s_add_u32 s31, %[d], {KOFF}", f"v_mov_b32 {PADR}, s31"]
+    body += chain_normalise(True) + [f"s_branch {lbl['sq']}", lbl["exit"] + ":"]
+    body += chain_store() + [lbl["done"] + ":"]
+    return rotate_carries(body)
+
+
+def modn_sq_mads():
+    return count_mads(modn_sq_rows())
+
+
+def modn_short_mads():
+    return count_mads(modn_short_rows())
+
+
 def chain_macros(lines, prefix="FBM_CH_R"):
     """`lines` as C source: preprocessor macros for what repeats, then the asm body that invokes them.
     The unrolled rows repeat the same instruction runs with three things varying: the multiply-adds'
@@ -1216,6 +1394,9 @@ __device__ __forceinline__ void fbm_na_sq_lds_looped(uint32_t a_off, const uint3
     with open(OUT, "w") as f:
         f.write(hdr)
     ch_defs, ch_body = chain_macros(chain)
+    modn, seg = chain_modn(), chain_seg()
+    cn_defs, cn_body = chain_macros(modn, prefix="FBM_CN_R")
+    cs_defs, cs_body = chain_macros(seg, prefix="FBM_CS_R")
     nl = "\n"
     chain_hdr = f"""// GENERATED by tools/gen_nadic_asm.py -- do not edit by hand.
 //
@@ -1246,6 +1427,42 @@ __device__ __forceinline__ void fbm_na_chain_short(uint32_t a_off, const uint32_
       :
       : [a] "v"(a_off), {", ".join(f'[h{i}] "v"(h[{i}])' for i in range(KS))}, [d] "s"(d_off), [kw] "s"(kw),
         [sb] "s"(sbits), [NK] "s"(NK), [np] "s"(np)
+      : "memory", "vcc", "scc", FBM_NA_CLOBBERS);
+}}
+
+// ---- the split exponentiation (DESIGN.md 5.7): h^|key| = (h^k1 mod N)^N h^k0 (mod N^2), |key| = k1 N + k0 ----
+// multiply-adds of one square / one short product modulo N (the t half of the products above)
+#define FBM_NA_MADS_SQR_MODN {modn_sq_mads()}
+#define FBM_NA_MADS_SHORT_MODN {modn_short_mads()}
+
+// Phase 1: the binary chain modulo N ({len(modn)} instructions) -- only the t half of the square and of the short
+// product, x0 in registers throughout, no LDS pairs: x0 = h, then for j = sbits - 1 .. 0 a square and, where bit j
+// of the words at kw (k1) is set, a short product; (x0, 0) -- h^k1 2^-f1 modulo N, digit 1 zero -- stored into the
+// lane's LDS column a.
+{nl.join(cn_defs)}
+
+__device__ __forceinline__ void fbm_na_chain_modn(uint32_t a_off, const uint32_t (&h)[{KS}], const uint32_t* kw,
+                                                  int sbits, const uint32_t* NK, uint32_t np) {{
+  asm volatile(
+{nl.join(cn_body)}
+      :
+      : [a] "v"(a_off), {", ".join(f'[h{i}] "v"(h[{i}])' for i in range(KS))}, [kw] "s"(kw), [sb] "s"(sbits),
+        [NK] "s"(NK), [np] "s"(np)
+      : "memory", "vcc", "scc", FBM_NA_CLOBBERS);
+}}
+
+// Phase 2's segments of the chain modulo N^2 ({len(seg)} instructions): X from the lane's LDS column a, then for
+// j = hi - 1 .. lo a square and, where bit j of the words at kw (k0) is set, a short product; X back into the
+// column.  hi == lo: nothing runs.  d as fbm_na_chain_short's.
+{nl.join(cs_defs)}
+
+__device__ __forceinline__ void fbm_na_chain_seg(uint32_t a_off, const uint32_t (&h)[{KS}], uint32_t d_off,
+                                                 const uint32_t* kw, int hi, int lo, const uint32_t* NK, uint32_t np) {{
+  asm volatile(
+{nl.join(cs_body)}
+      :
+      : [a] "v"(a_off), {", ".join(f'[h{i}] "v"(h[{i}])' for i in range(KS))}, [d] "s"(d_off), [kw] "s"(kw),
+        [hi] "s"(hi), [lo] "s"(lo), [NK] "s"(NK), [np] "s"(np)
       : "memory", "vcc", "scc", FBM_NA_CLOBBERS);
 }}
 """
