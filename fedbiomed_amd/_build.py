@@ -6,7 +6,8 @@
                                             device routines, per-thread engine switches, the per-kernel
                                             event timer) -- for tests/ and bench.py
 
-Both link the SAME kernel objects (fbm_lom / fbm_jl / fbm_gen / fbm_ass, compiled once); only the
+Both link the SAME kernel objects (fbm_lom / fbm_jl / fbm_gen / fbm_ass) and the same host setup
+(fbm_setup.hip: per-modulus and per-key constants on fbm_bigint.hpp), compiled once; only the
 host-side C ABI (fbm_capi.hip) is compiled twice, the second time with -DFBM_TEST_HOOKS.  A linker
 version script made from each library's header(s) keeps every other symbol local.
 
@@ -30,8 +31,9 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "_lib", "libfbm_secagg.so")
 TEST_OUT = os.path.join(HERE, "_lib", "libfbm_secagg_test.so")
 KERNEL_SOURCES = ["fbm_lom.hip", "fbm_jl.hip", "fbm_gen.hip", "fbm_ass.hip"]
+SETUP_SOURCE = "fbm_setup.hip"  # host only, no test hooks: compiled once, like the kernels
 CAPI_SOURCE = "fbm_capi.hip"
-SOURCES = KERNEL_SOURCES + [CAPI_SOURCE]
+SOURCES = KERNEL_SOURCES + [SETUP_SOURCE, CAPI_SOURCE]
 HEADER = os.path.join(ROOT, "include", "fbm_secagg.h")
 TEST_HEADER = os.path.join(ROOT, "include", "fbm_secagg_test.h")
 # host-side list <-> buffer conversions of the list API (a CPython extension, plain gcc)
@@ -139,12 +141,12 @@ def _compile_all(jobs, verbose: bool) -> None:
 
 
 def _build_libs(targets, defines, verbose: bool) -> None:
-    """targets: [(out, test_hooks)] linked from one set of kernel objects."""
+    """targets: [(out, test_hooks)] linked from one set of kernel and host-setup objects."""
     base = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
             "-I" + os.path.join(ROOT, "include")] + ["-D" + d for d in defines]
     with tempfile.TemporaryDirectory(prefix="fbm_build_") as tmpd:
         jobs, kobjs = [], []
-        for f in KERNEL_SOURCES:
+        for f in KERNEL_SOURCES + [SETUP_SOURCE]:
             o = os.path.join(tmpd, f.replace(".hip", ".o"))
             kobjs.append(o)
             jobs.append((base + ["-c", os.path.join(CSRC, f), "-o", o], f))

@@ -1,6 +1,7 @@
-// fedbiomed_amd -- C ABI (include/fbm_secagg.h): argument validation, per-call uniform
-// parameter setup (Montgomery constants, SHA-256 midstate, sliding-window schedule,
-// ChaCha20 IV words) and kernel launches.  All device memory belongs to the caller.
+// fedbiomed_amd -- C ABI (include/fbm_secagg.h): argument validation, call policy (engine and
+// path of a call), workspace layouts and kernel launches, and the test build's hooks.  The
+// per-modulus and per-key constants the launches take are built in fbm_setup.hip.  All device
+// memory belongs to the caller.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -66,338 +67,6 @@ static int quant_params(double clip, double two_clip, double target_f, uint64_t 
   return FBM_OK;
 }
 
-// ---------------------------------------------------------------------------------------
-// host big-integer helpers (tiny, per call)
-// ---------------------------------------------------------------------------------------
-typedef std::vector<uint32_t> Big;  // little-endian 32-bit limbs
-
-static int big_bits(const Big& a) {
-  for (int i = (int)a.size() - 1; i >= 0; --i)
-    if (a[i]) return 32 * i + 32 - __builtin_clz(a[i]);
-  return 0;
-}
-
-static Big big_mul(const Big& a, const Big& b) {
-  Big r(a.size() + b.size(), 0u);
-  for (size_t i = 0; i < a.size(); ++i) {
-    uint64_t c = 0;
-    for (size_t j = 0; j < b.size(); ++j) {
-      const uint64_t t = (uint64_t)a[i] * b[j] + r[i + j] + c;
-      r[i + j] = (uint32_t)t;
-      c = t >> 32;
-    }
-    r[i + b.size()] = (uint32_t)c;
-  }
-  return r;
-}
-
-static int big_cmp(const Big& a, const Big& b) {
-  const size_t n = a.size() > b.size() ? a.size() : b.size();
-  for (size_t k = n; k-- > 0;) {
-    const uint32_t x = k < a.size() ? a[k] : 0u, y = k < b.size() ? b[k] : 0u;
-    if (x != y) return x > y ? 1 : -1;
-  }
-  return 0;
-}
-
-static void big_sub_inplace(Big& a, const Big& b) {  // a >= b
-  int64_t br = 0;
-  for (size_t k = 0; k < a.size(); ++k) {
-    const int64_t d = (int64_t)a[k] - (int64_t)(k < b.size() ? b[k] : 0u) + br;
-    a[k] = (uint32_t)d;
-    br = d < 0 ? -1 : 0;
-  }
-}
-
-// 2^e mod m by repeated doubling (m odd, > 1)
-static Big big_pow2_mod(int e, const Big& m) {
-  Big x(m.size() + 1, 0u);
-  x[0] = 1u;
-  for (int i = 0; i < e; ++i) {
-    uint32_t c = 0;
-    for (size_t k = 0; k < x.size(); ++k) {
-      const uint32_t nc = x[k] >> 31;
-      x[k] = (x[k] << 1) | c;
-      c = nc;
-    }
-    if (big_cmp(x, m) >= 0) big_sub_inplace(x, m);
-  }
-  return x;
-}
-
-// a b 2^-32n mod m (CIOS over n = m.size() 32-bit words; m odd, a, b < m)
-static Big host_mont(const Big& a, const Big& b, const Big& m, uint32_t mi) {
-  const size_t n = m.size();
-  std::vector<uint32_t> t(n + 2, 0u);
-  for (size_t i = 0; i < n; ++i) {
-    uint64_t c = 0;
-    for (size_t j = 0; j < n; ++j) {
-      const uint64_t v = (uint64_t)a[j] * b[i] + t[j] + c;
-      t[j] = (uint32_t)v;
-      c = v >> 32;
-    }
-    uint64_t v = (uint64_t)t[n] + c;
-    t[n] = (uint32_t)v;
-    t[n + 1] = (uint32_t)(v >> 32);
-    const uint32_t q = t[0] * mi;
-    c = ((uint64_t)q * m[0] + t[0]) >> 32;
-    for (size_t j = 1; j < n; ++j) {
-      const uint64_t w = (uint64_t)q * m[j] + t[j] + c;
-      t[j - 1] = (uint32_t)w;
-      c = w >> 32;
-    }
-    v = (uint64_t)t[n] + c;
-    t[n - 1] = (uint32_t)v;
-    t[n] = t[n + 1] + (uint32_t)(v >> 32);
-  }
-  Big r(t.begin(), t.begin() + n + 1);
-  if (big_cmp(r, m) >= 0) big_sub_inplace(r, m);
-  r.resize(n);
-  return r;
-}
-
-// 2^e mod m (m odd, > 1, top word nonzero or not): left-to-right, Montgomery squarings and
-// plain modular doublings -- log2(e) products instead of e doublings (big_pow2_mod)
-static Big big_pow2_mod_mont(uint64_t e, Big m) {
-  while (m.size() > 1 && m.back() == 0u) m.pop_back();
-  const size_t n = m.size();
-  uint32_t inv = m[0];  // Newton: m^-1 mod 2^32
-  for (int i = 0; i < 5; ++i) inv *= 2u - m[0] * inv;
-  const uint32_t mi = 0u - inv;
-  Big x = big_pow2_mod((int)(32 * n), m);  // 1 in Montgomery form
-  x.resize(n);
-  auto dbl = [&](Big& y) {
-    Big z(y.begin(), y.end());
-    z.push_back(0u);
-    uint32_t c = 0;
-    for (size_t k = 0; k < z.size(); ++k) {
-      const uint32_t nc = z[k] >> 31;
-      z[k] = (z[k] << 1) | c;
-      c = nc;
-    }
-    if (big_cmp(z, m) >= 0) big_sub_inplace(z, m);
-    z.resize(n);
-    y = z;
-  };
-  for (int b = 63; b >= 0; --b) {
-    x = host_mont(x, x, m, mi);
-    if ((e >> b) & 1u) dbl(x);
-  }
-  Big one(n, 0u);
-  one[0] = 1u;
-  return host_mont(x, one, m, mi);
-}
-
-static void to_limbs_host(const Big& a, uint32_t* o, int nl, int lb) {
-  for (int k = 0; k < nl; ++k) {
-    const int bit = k * lb, wi = bit >> 5, sh = bit & 31;
-    const uint64_t lo = wi < (int)a.size() ? a[wi] : 0u;
-    const uint64_t hi = wi + 1 < (int)a.size() ? a[wi + 1] : 0u;
-    o[k] = (uint32_t)(((hi << 32) | lo) >> sh) & ((1u << lb) - 1u);
-  }
-}
-
-static void to28_host(const Big& a, uint32_t* o, int nl) { to_limbs_host(a, o, nl, FBM_LB); }
-
-template <int NL>
-static void build_mont(const Big& m, MontCtxT<NL>& c) {
-  to28_host(m, c.M, NL);
-  const Big R2 = big_pow2_mod(2 * NL * FBM_LB, m);
-  to28_host(R2, c.R2, NL);
-  uint32_t inv = m[0];  // Newton: inv = m^-1 mod 2^32
-  for (int i = 0; i < 5; ++i) inv *= 2u - m[0] * inv;
-  c.mp = (0u - inv) & FBM_LMASK;
-}
-
-// (q, r) = (a div m, a mod m) by binary long division (host, per call; a < 2^2080, m odd)
-static void big_divmod(const Big& a, const Big& m, Big& q, Big& r) {
-  const int nb = big_bits(a);
-  q.assign(a.size(), 0u);
-  r.assign(m.size() + 1, 0u);
-  for (int i = nb - 1; i >= 0; --i) {
-    uint32_t c = (a[i >> 5] >> (i & 31)) & 1u;
-    for (size_t k = 0; k < r.size(); ++k) {
-      const uint32_t nc = r[k] >> 31;
-      r[k] = (r[k] << 1) | c;
-      c = nc;
-    }
-    if (big_cmp(r, m) >= 0) {
-      big_sub_inplace(r, m);
-      q[i >> 5] |= 1u << (i & 31);
-    }
-  }
-}
-
-
-// Constants of the quad engine (tools/gen_quad_asm.py): 29-bit limbs, R = 2^(36*29) = 2^1044.
-static void build_quad(const Big& N, const Big& M, QuadCtx& qa) {
-  memset(&qa, 0, sizeof(qa));
-  const int LB = FBM_QA_LB, L = FBM_QA_L;
-  Big Rm = big_pow2_mod(L * LB, N);  // R mod N
-  Big K(N.size() + 1, 0u);
-  K[0] = 1u;
-  if (big_cmp(Rm, K) > 0) {  // K = N + 1 - Rm
-    Big t(N.begin(), N.end());
-    t.push_back(0u);
-    uint64_t c = 1;
-    for (size_t k = 0; k < t.size(); ++k) {
-      c += t[k];
-      t[k] = (uint32_t)c;
-      c >>= 32;
-    }
-    big_sub_inplace(t, Rm);
-    K = t;
-  } else {
-    K.assign(1, 0u);
-  }
-  uint32_t k29[FBM_QA_L];
-  to_limbs_host(K, k29, L, LB);
-  for (int j = 0; j < L; ++j) qa.kp[j] = ((1u << LB) - 1u) + k29[j];
-  {  // the one-lane square's initial s window: 2^29 - 1 + P'_j, P' = (K - E) mod N (fbm_nadic_asm.hpp)
-    Big E(40, 0u);
-    for (int c = 0; c < 64; ++c)
-      if ((FBM_NA_SQ_ONE_MASK >> c) & 1ull) {
-        const int bit = 32 + LB * c;
-        E[bit >> 5] |= 1u << (bit & 31);
-      }
-    Big q, r;
-    big_divmod(E, N, q, r);  // E mod N
-    Big P(K.begin(), K.end());
-    P.resize(N.size() + 1, 0u);
-    if (big_cmp(P, r) < 0) {  // P' = K - r (+ N)
-      uint64_t c = 0;
-      for (size_t k = 0; k < P.size(); ++k) {
-        c += (uint64_t)P[k] + (k < N.size() ? N[k] : 0u);
-        P[k] = (uint32_t)c;
-        c >>= 32;
-      }
-    }
-    big_sub_inplace(P, r);
-    uint32_t p29[FBM_QA_L];
-    to_limbs_host(P, p29, L, LB);
-    for (int j = 0; j < L; ++j) qa.sqp[j] = ((1u << LB) - 1u) + p29[j];
-  }
-  to_limbs_host(N, qa.n, L, LB);
-  for (int e = 2; e <= 3; ++e) {
-    const Big u = big_pow2_mod(e * L * LB, M);
-    Big q, r;
-    big_divmod(u, N, q, r);
-    uint32_t* dst = e == 2 ? qa.r2 : qa.r3;
-    to_limbs_host(r, dst, L, LB);
-    to_limbs_host(q, dst + L, L, LB);
-  }
-  uint32_t inv = N[0];  // Newton: N^-1 mod 2^32
-  for (int i = 0; i < 5; ++i) inv *= 2u - N[0] * inv;
-  qa.np = (0u - inv) & ((1u << LB) - 1u);
-}
-
-// Constants of the one-lane N-adic engine (tools/gen_nadic_asm.py): the group engines' 29-bit
-// N and K'_i (the same R = 2^1044) in the layout of its scalar loads, and N's 28-bit limbs
-// for the final step shared by all N-adic engines (na_final_digits).
-static void build_nadic(const MontCtxN& mn, const QuadCtx& qa, NadicCtx& na) {
-  static_assert(FBM_NA_LIMBS == FBM_QA_L && FBM_NA_LIMB_BITS == FBM_QA_LB, "one R for all N-adic engines");
-  memset(&na, 0, sizeof(na));
-  for (int j = 0; j < FBM_NLN; ++j) na.nk[j < 10 ? j : 6 + j] = mn.M[j];
-  for (int j = 0; j < FBM_QA_L; ++j) na.nk29[j < 10 ? j : 6 + j] = qa.n[j];
-  for (int j = 0; j < FBM_QA_L; ++j) na.nk29[42 + j] = qa.kp[j];
-}
-
-// SHA-256 midstate over the 14 leading blocks of t.to_bytes(1024,'big') (FDH.H), t = (k << 512) | tau:
-// bytes 0..895 = t's bits 1024..8191 = tau's words 32..255 (k < 2^64 never reaches them).  Block b's
-// SHA word j is t's little-endian word 255 - 16 b - j.  All-zero for a round below 2^1024.
-static void fdh_midstate(uint32_t mid[8], const uint32_t* tau = nullptr) {
-  static uint32_t zero_mid[8];
-  static std::once_flag once;
-  std::call_once(once, [] {
-    uint32_t st[8], W[16];
-    fbm_sha256_init(st);
-    memset(W, 0, sizeof(W));
-    for (int b = 0; b < 14; ++b) fbm_sha256_compress(st, W);
-    memcpy(zero_mid, st, sizeof(st));
-  });
-  bool hi = false;
-  for (int i = 32; tau && i < FBM_TAU_LIMBS; ++i) hi |= tau[i] != 0u;
-  if (!hi) {
-    memcpy(mid, zero_mid, sizeof(zero_mid));
-    return;
-  }
-  uint32_t st[8], W[16];
-  fbm_sha256_init(st);
-  for (int b = 0; b < 14; ++b) {
-    for (int j = 0; j < 16; ++j) W[j] = tau[255 - 16 * b - j];
-    fbm_sha256_compress(st, W);
-  }
-  memcpy(mid, st, sizeof(st));
-}
-
-// the round tau (FBM_TAU_LIMBS little-endian words, < 2^8192) -> FDH's message blocks: block 15 = tau's
-// words 0..15, block 14 = words 16..31 (the kernel ORs k into its last two words), blocks 0..13 into the
-// midstate -- t.to_bytes(1024, 'big') of t = (k << 512) | tau (_jls.py:451-467, 744-748) for any round
-static void set_tau(JlParams& jp, const uint32_t* tau) {
-  for (int i = 0; i < 16; ++i) jp.tau_w[i] = tau ? tau[15 - i] : 0u;
-  for (int i = 0; i < 16; ++i) jp.tau14_w[i] = tau ? tau[31 - i] : 0u;
-  fdh_midstate(jp.mid, tau);
-}
-
-static void big_trim(Big& a) {
-  while (a.size() > 1 && a.back() == 0u) a.pop_back();
-}
-
-static int big_ctz(const Big& a) {
-  for (size_t i = 0; i < a.size(); ++i)
-    if (a[i]) return 32 * (int)i + __builtin_ctz(a[i]);
-  return 0;
-}
-
-static Big big_shr(const Big& a, int s) {
-  Big r(a.size(), 0u);
-  const int w = s >> 5, b = s & 31;
-  for (size_t i = 0; i + w < a.size(); ++i) {
-    const uint64_t lo = a[i + w], hi = i + w + 1 < a.size() ? a[i + w + 1] : 0u;
-    r[i] = (uint32_t)((((hi << 32) | lo) >> b));
-  }
-  big_trim(r);
-  return r;
-}
-
-// a b mod 2^(32 n)
-static Big big_mullo(const Big& a, const Big& b, size_t n) {
-  Big r(n, 0u);
-  for (size_t i = 0; i < n && i < a.size(); ++i) {
-    uint64_t c = 0;
-    for (size_t j = 0; i + j < n; ++j) {
-      const uint64_t t = (uint64_t)a[i] * (j < b.size() ? b[j] : 0u) + r[i + j] + c;
-      r[i + j] = (uint32_t)t;
-      c = t >> 32;
-    }
-  }
-  return r;
-}
-
-// FDH.H's parameters only (fbm_jl_fdh and the generic engine): the gcd modulus' odd part
-// (>= 1; 1: every odd r is coprime) and whether r must be odd as well
-static int fdh_params(const uint32_t* n_odd, int even, const uint32_t* tau, uint64_t ct_offset, JlParams& jp) {
-  if (!(n_odd[0] & 1u)) {
-    set_error("FDH: the gcd modulus' odd part must be odd");
-    return FBM_E_ARG;
-  }
-  memset(&jp, 0, sizeof(jp));
-  for (int i = 0; i < 32; ++i) jp.N32[i] = n_odd[i];
-  jp.fdh_even = even ? 1 : 0;
-  set_tau(jp, tau);
-  jp.ct_offset = ct_offset;
-  return FBM_OK;
-}
-
-// FDH(2048, N^2): gcd(r, N^2) == 1 iff r is coprime to N's odd part (and odd, for an even N)
-static int fdh_params_for_biprime(const uint32_t* biprime, const uint32_t* tau, uint64_t ct_offset, JlParams& jp) {
-  Big N(biprime, biprime + 32);
-  const int s = big_ctz(N);
-  Big m = big_shr(N, s);
-  m.resize(32, 0u);
-  return fdh_params(m.data(), s > 0, tau, ct_offset, jp);
-}
-
 // N = 1: the reference computes everything modulo N^2 = 1 (every ciphertext 0) and its decryption's
 // invert(delta^2, N^2) raises; only the generic engine's Barrett products take a modulus of 1
 static bool jl_is_one(const uint32_t* biprime) {
@@ -456,609 +125,6 @@ static int jl_path_for(const void* ws, int phase, int full, const uint32_t* bipr
     g_path_recs.push_back(JlPathRec{ws, generic, short_on});
   }
   return FBM_OK;
-}
-
-// GenCtx of (N, key): M = N^2, Barrett constants of M and N, M = 2^e m2 with m2 odd, m2^-1 mod 2^e
-static int build_gen_ctx(const uint32_t* biprime, const uint32_t* key, int key_negative, GenCtx& g) {
-  memset(&g, 0, sizeof(g));
-  Big N(biprime, biprime + 32);
-  big_trim(N);
-  if (big_bits(N) < 1) {
-    set_error("biprime must be >= 1");
-    return FBM_E_UNSUPPORTED;
-  }
-  Big M = big_mul(N, N);
-  big_trim(M);
-  auto mu = [](const Big& m) {  // floor(2^(64 k) / m), k = words of m
-    Big a(2 * m.size() + 1, 0u), q, r;
-    a.back() = 1u;
-    big_divmod(a, m, q, r);
-    big_trim(q);
-    return q;
-  };
-  const Big muM = mu(M), muN = mu(N);
-  g.kM = (int)M.size();
-  g.kN = (int)N.size();
-  for (size_t i = 0; i < M.size(); ++i) g.M[i] = M[i];
-  for (size_t i = 0; i < muM.size() && i < 68; ++i) g.muM[i] = muM[i];
-  for (size_t i = 0; i < N.size(); ++i) g.N[i] = N[i];
-  for (size_t i = 0; i < muN.size() && i < 36; ++i) g.muN[i] = muN[i];
-  const int s = big_ctz(N);
-  const Big m = big_shr(N, s);
-  Big m2 = big_mul(m, m);
-  big_trim(m2);
-  g.km2 = (int)m2.size();
-  g.e = 2 * s;
-  for (size_t i = 0; i < m2.size(); ++i) g.m2[i] = m2[i];
-  if (g.e > 0) {  // m2^-1 mod 2^e by Newton (m2 odd): y <- y (2 - m2 y), 32 -> 64 -> ... bits
-    const size_t W = (size_t)((g.e + 31) / 32);
-    uint32_t y0 = m2[0];
-    for (int i = 0; i < 5; ++i) y0 *= 2u - m2[0] * y0;
-    Big y(W, 0u);
-    y[0] = y0;
-    for (size_t prec = 32; prec < 32 * W; prec *= 2) {
-      Big t = big_mullo(m2, y, W);
-      uint64_t c = 3;  // 2 - t = ~t + 3 (mod 2^(32 W))
-      for (size_t i = 0; i < W; ++i) {
-        c += (uint32_t)~t[i];
-        t[i] = (uint32_t)c;
-        c >>= 32;
-      }
-      y = big_mullo(y, t, W);
-    }
-    if (g.e & 31) y[W - 1] &= (1u << (g.e & 31)) - 1u;
-    for (size_t i = 0; i < W; ++i) g.m2inv[i] = y[i];
-  }
-  if (key) {
-    Big K(key, key + 64);
-    g.key_bits = big_bits(K);
-    for (int i = 0; i < 64; ++i) g.key[i] = key[i];
-    g.key_negative = key_negative ? 1 : 0;
-  }
-  return FBM_OK;
-}
-
-// The modulus-dependent part of JlParams (Montgomery / N-adic / group-engine constants, N^-1
-// mod 2^1024, the FDH midstate): ~0.3 ms of host big-integer work per call, so it is built once
-// per biprime and kept in a small process-wide cache (a round's encrypts and aggregate, and
-// every round of an experiment, share one biprime).
-static int build_jl_params_uncached(const uint32_t* biprime, int es, int cr, const uint32_t* tau, uint64_t ct_offset,
-                                    JlParams& jp) {
-  memset(&jp, 0, sizeof(jp));
-  Big N(biprime, biprime + 32);
-  const int nb = big_bits(N);
-  if (nb < 2 || (N[0] & 1u) == 0u) {  // an even N takes the generic engine before this (jl_generic)
-    set_error("biprime must be >= 2 (the Montgomery engines take an odd N >= 3); got %d bits, %s", nb,
-              (N[0] & 1u) ? "odd" : "even");
-    return FBM_E_UNSUPPORTED;
-  }
-  if (es < 1 || cr < 1 || es > 100 || (int64_t)es * cr > 1024) {
-    set_error("invalid VES parameters es=%d cr=%d", es, cr);
-    return FBM_E_ARG;
-  }
-  Big M = big_mul(N, N);  // 64 limbs
-  while (M.size() > 64) M.pop_back();
-  build_mont<FBM_NL>(M, jp.mc);
-  build_mont<FBM_NLN>(N, jp.mn);
-  build_quad(N, M, jp.qa);
-  build_nadic(jp.mn, jp.qa, jp.na);
-  for (int i = 0; i < 32; ++i) jp.N32[i] = biprime[i];
-  {  // N^-1 mod 2^1024 by Newton: y <- y (2 - N y); y = N is correct to 3 bits for odd N
-    uint32_t y[32], t[32];
-    for (int i = 0; i < 32; ++i) y[i] = biprime[i];
-    auto mullo = [](const uint32_t* a, const uint32_t* b, uint32_t* r) {  // r = a*b mod 2^1024
-      uint32_t acc[32] = {0};
-      for (int i = 0; i < 32; ++i) {
-        uint64_t c = 0;
-        for (int j = 0; i + j < 32; ++j) {
-          const uint64_t v = (uint64_t)a[i] * b[j] + acc[i + j] + c;
-          acc[i + j] = (uint32_t)v;
-          c = v >> 32;
-        }
-      }
-      memcpy(r, acc, sizeof(acc));
-    };
-    for (int it = 0; it < 9; ++it) {  // 3 -> 6 -> ... -> 1536 bits
-      mullo(biprime, y, t);           // t = N y
-      uint64_t br = 0;                // t = 2 - t  (mod 2^1024)
-      for (int i = 0; i < 32; ++i) {
-        const uint64_t d = (uint64_t)(i == 0 ? 2u : 0u) - t[i] - br;
-        t[i] = (uint32_t)d;
-        br = (d >> 63) & 1u;
-      }
-      mullo(y, t, y);
-    }
-    memcpy(jp.Ninv32, y, sizeof(y));
-  }
-  jp.n_bits = nb;
-  {  // M = N << (1036 - nb): 0 mod N, in [2^1035, 2^1036) (negative-weight nude digit)
-    Big m(N.begin(), N.end());
-    m.resize(34, 0u);
-    const int sh = FBM_NLN * FBM_LB - nb;
-    for (int i = 0; i < sh; ++i) {
-      uint32_t c = 0;
-      for (size_t k = 0; k < m.size(); ++k) {
-        const uint32_t nc = m[k] >> 31;
-        m[k] = (m[k] << 1) | c;
-        c = nc;
-      }
-    }
-    to28_host(m, jp.mneg, FBM_NLN);
-  }
-  fbm_n30_setup(jp.N32, jp.n30);
-  jp.es = es;
-  jp.cr = cr;
-  set_tau(jp, tau);
-  jp.ct_offset = ct_offset;
-  return FBM_OK;
-}
-
-struct JlParamsCacheEntry {
-  uint32_t n32[32];
-  JlParams jp;
-};
-static std::mutex g_jp_mu;
-static std::vector<JlParamsCacheEntry> g_jp_cache;  // most recently used last, at most 8
-
-static int build_jl_params(const uint32_t* biprime, int es, int cr, const uint32_t* tau, uint64_t ct_offset,
-                           JlParams& jp) {
-  if (es < 1 || cr < 1 || es > 100 || (int64_t)es * cr > 1024) {
-    set_error("invalid VES parameters es=%d cr=%d", es, cr);
-    return FBM_E_ARG;
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_jp_mu);
-    for (size_t i = 0; i < g_jp_cache.size(); ++i) {
-      if (memcmp(g_jp_cache[i].n32, biprime, sizeof(g_jp_cache[i].n32)) == 0) {
-        JlParamsCacheEntry e = g_jp_cache[i];
-        g_jp_cache.erase(g_jp_cache.begin() + i);
-        g_jp_cache.push_back(e);
-        jp = e.jp;
-        jp.es = es;
-        jp.cr = cr;
-        set_tau(jp, tau);
-        jp.ct_offset = ct_offset;
-        jp.key_is_zero = 0;
-        return FBM_OK;
-      }
-    }
-  }
-  const int rc = build_jl_params_uncached(biprime, es, cr, tau, ct_offset, jp);
-  if (rc) return rc;
-  JlParamsCacheEntry e;
-  memcpy(e.n32, biprime, sizeof(e.n32));
-  e.jp = jp;
-  std::lock_guard<std::mutex> lk(g_jp_mu);
-  if (g_jp_cache.size() >= 8) g_jp_cache.erase(g_jp_cache.begin());
-  g_jp_cache.push_back(e);
-  return FBM_OK;
-}
-
-// R^(P+1) mod N^2 in 28-bit limbs (the ciphertext product's first operand), cached per (N, P)
-struct JlRkCacheEntry {
-  uint32_t n32[32];
-  int parties;
-  JlRk rk;
-};
-static std::vector<JlRkCacheEntry> g_rk_cache;  // guarded by g_jp_mu, at most 16
-
-static void jl_rk_for(const uint32_t* n32, int n_parties, JlRk& r) {
-  {
-    std::lock_guard<std::mutex> lk(g_jp_mu);
-    for (const JlRkCacheEntry& e : g_rk_cache)
-      if (e.parties == n_parties && memcmp(e.n32, n32, sizeof(e.n32)) == 0) {
-        r = e.rk;
-        return;
-      }
-  }
-  Big M(n32, n32 + 32);
-  M = big_mul(M, M);
-  M.resize(64);
-  const Big rk = big_pow2_mod_mont((uint64_t)(n_parties + 1) * FBM_NL * FBM_LB, M);
-  memset(&r, 0, sizeof(r));
-  to28_host(rk, r.w, FBM_NL);
-  JlRkCacheEntry e;
-  memcpy(e.n32, n32, sizeof(e.n32));
-  e.parties = n_parties;
-  e.rk = r;
-  std::lock_guard<std::mutex> lk(g_jp_mu);
-  if (g_rk_cache.size() >= 16) g_rk_cache.erase(g_rk_cache.begin());
-  g_rk_cache.push_back(e);
-}
-
-// Left-to-right sliding window (width FBM_WIN) over |key|, odd-power table.
-static int build_schedule(const uint32_t* key, JlSched& sc, int& is_zero) {
-  memset(&sc, 0, sizeof(sc));
-  sc.sbits = sc.sb1 = -1;  // (build_short)
-  Big K(key, key + 64);
-  const int nb = big_bits(K);
-  is_zero = nb == 0;
-  if (is_zero) return FBM_OK;
-  auto bit = [&](int i) -> int { return (K[i >> 5] >> (i & 31)) & 1; };
-  int i = nb - 1;
-  int pending_sq = 0;
-  bool first = true;
-  while (i >= 0) {
-    if (!bit(i)) {
-      ++pending_sq;
-      --i;
-      continue;
-    }
-    int l = i - FBM_WIN + 1;
-    if (l < 0) l = 0;
-    while (!bit(l)) ++l;
-    int val = 0;
-    for (int j = i; j >= l; --j) val = (val << 1) | bit(j);
-    const int width = i - l + 1;
-    const int idx = (val - 1) / 2;
-    if (first) {
-      sc.first = idx;
-      first = false;
-    } else {
-      int nsq = pending_sq + width;
-      while (nsq > FBM_OP_MAXSQ) {
-        if (sc.n_ops >= FBM_MAX_OPS) return FBM_E_ARG;
-        sc.op[sc.n_ops++] = (uint16_t)(FBM_OP_MAXSQ << FBM_OP_SHIFT);
-        nsq -= FBM_OP_MAXSQ;
-      }
-      if (sc.n_ops >= FBM_MAX_OPS) return FBM_E_ARG;
-      sc.op[sc.n_ops++] = (uint16_t)((nsq << FBM_OP_SHIFT) | (idx + 1));
-    }
-    pending_sq = 0;
-    i = l - 1;
-  }
-  while (pending_sq > 0) {
-    const int nsq = pending_sq > FBM_OP_MAXSQ ? FBM_OP_MAXSQ : pending_sq;
-    if (sc.n_ops >= FBM_MAX_OPS) return FBM_E_ARG;
-    sc.op[sc.n_ops++] = (uint16_t)(nsq << FBM_OP_SHIFT);
-    pending_sq -= nsq;
-  }
-  return FBM_OK;
-}
-
-// ---- the short path's constants (JlShort, fbm_internal.hpp) ------------------------------
-// 2^E mod m for an odd m of at most 2048 bits and any E: left-to-right, Montgomery squarings
-// (64-bit limbs) and modular doublings -- ~2 050 products for the ~2 050-bit E of a 2 040-bit key
-static Big pow2_mod_big(const Big& E, Big m) {
-  big_trim(m);
-  const int n = (int)((m.size() + 1) / 2);
-  uint64_t M[32] = {0};
-  for (size_t i = 0; i < m.size(); ++i) M[i / 2] |= (uint64_t)m[i] << (32 * (i & 1));
-  uint64_t inv = M[0];  // Newton: M^-1 mod 2^64
-  for (int i = 0; i < 6; ++i) inv *= 2u - M[0] * inv;
-  const uint64_t mi = 0u - inv;
-  auto ge_sub = [&](uint64_t* a, uint64_t top) {  // a <- a - M if (top:a) >= M
-    bool ge = top != 0;
-    if (!ge) {
-      ge = true;
-      for (int k = n - 1; k >= 0; --k)
-        if (a[k] != M[k]) {
-          ge = a[k] > M[k];
-          break;
-        }
-    }
-    if (!ge) return;
-    unsigned __int128 br = 0;
-    for (int k = 0; k < n; ++k) {
-      const unsigned __int128 d = (unsigned __int128)a[k] - M[k] - br;
-      a[k] = (uint64_t)d;
-      br = (d >> 64) & 1u;
-    }
-  };
-  auto mul = [&](const uint64_t* a, const uint64_t* b, uint64_t* r) {  // a b 2^-64n mod M (CIOS)
-    uint64_t t[34] = {0};
-    for (int i = 0; i < n; ++i) {
-      unsigned __int128 c = 0;
-      for (int j = 0; j < n; ++j) {
-        c += (unsigned __int128)a[j] * b[i] + t[j];
-        t[j] = (uint64_t)c;
-        c >>= 64;
-      }
-      c += t[n];
-      t[n] = (uint64_t)c;
-      t[n + 1] = (uint64_t)(c >> 64);
-      const uint64_t q = t[0] * mi;
-      c = ((unsigned __int128)q * M[0] + t[0]) >> 64;
-      for (int j = 1; j < n; ++j) {
-        c += (unsigned __int128)q * M[j] + t[j];
-        t[j - 1] = (uint64_t)c;
-        c >>= 64;
-      }
-      c += t[n];
-      t[n - 1] = (uint64_t)c;
-      t[n] = t[n + 1] + (uint64_t)(c >> 64);
-    }
-    ge_sub(t, t[n]);
-    for (int k = 0; k < n; ++k) r[k] = t[k];
-  };
-  auto dbl = [&](uint64_t* a) {
-    uint64_t c = 0;
-    for (int k = 0; k < n; ++k) {
-      const uint64_t nc = a[k] >> 63;
-      a[k] = (a[k] << 1) | c;
-      c = nc;
-    }
-    ge_sub(a, c);
-  };
-  uint64_t x[32] = {0};
-  x[0] = 1;
-  for (int i = 0; i < 64 * n; ++i) dbl(x);  // 1 in Montgomery form
-  for (int b = big_bits(E) - 1; b >= 0; --b) {
-    mul(x, x, x);
-    if ((E[b >> 5] >> (b & 31)) & 1u) dbl(x);
-  }
-  uint64_t one[32] = {0};
-  one[0] = 1;
-  mul(x, one, x);
-  Big r(2 * (size_t)n, 0u);
-  for (int k = 0; k < n; ++k) {
-    r[2 * k] = (uint32_t)x[k];
-    r[2 * k + 1] = (uint32_t)(x[k] >> 32);
-  }
-  return r;
-}
-
-// The short path's constant C per (N, |key|), cached so a round's repeated calls skip the ~2 050
-// host squarings.  An entry holds no key material: it is found by a SHA-256 digest of (N, |key|)
-// and holds only C (a public function of the key, like the ciphertexts it is used for); entries
-// are zeroed when evicted or cleared (fbm_jl_clear_caches).  The reference keeps nothing between
-// calls (a fresh SecaggCrypter per call: fedbiomed/node/secagg/_secagg_round.py:142).
-struct JlShortCacheEntry {
-  uint32_t digest[8];  // SHA-256(N's 32 words || |key|'s 64 words, little-endian bytes)
-  uint32_t corr[72];
-};
-static std::vector<JlShortCacheEntry> g_short_cache;  // guarded by g_jp_mu, at most 32
-
-static void wipe(void* p, size_t n) {  // a zeroing the optimiser keeps
-  volatile uint8_t* v = (volatile uint8_t*)p;
-  while (n--) *v++ = 0;
-}
-
-// SHA-256 of a little-endian word message (host; the FDH kernel's compression function)
-static void sha256_words(const uint32_t* w, int nw, uint32_t out[8]) {
-  uint32_t st[8], W[16];
-  fbm_sha256_init(st);
-  const uint64_t nbytes = (uint64_t)nw * 4;
-  const int nblocks = (int)((nbytes + 9 + 63) / 64);
-  auto byte_at = [&](uint64_t i) -> uint32_t {
-    if (i < nbytes) return (w[i / 4] >> (8 * (i % 4))) & 0xffu;  // little-endian words
-    if (i == nbytes) return 0x80u;
-    const uint64_t tail = (uint64_t)nblocks * 64 - i;  // the 8-byte big-endian bit length
-    if (tail <= 8) return (uint32_t)(((nbytes * 8) >> (8 * (tail - 1))) & 0xffu);
-    return 0u;
-  };
-  for (int b = 0; b < nblocks; ++b) {
-    for (int j = 0; j < 16; ++j) {
-      const uint64_t i = (uint64_t)b * 64 + 4 * j;
-      W[j] = (byte_at(i) << 24) | (byte_at(i + 1) << 16) | (byte_at(i + 2) << 8) | byte_at(i + 3);
-    }
-    fbm_sha256_compress(st, W);
-  }
-  memcpy(out, st, sizeof(st));
-  wipe(W, sizeof(W));
-}
-
-// The split exponentiation's constants per (N, |key|) (JlShort: c1, cp, one), cached beside C under the same
-// digest and on the same terms: public functions of the key, zeroed when evicted or cleared.
-struct JlSplitCacheEntry {
-  uint32_t digest[8];
-  uint32_t c1[36];
-  uint32_t cp[72];
-  uint32_t one[72];
-};
-static std::vector<JlSplitCacheEntry> g_split_cache;  // guarded by g_jp_mu, at most 32
-
-static void short_cache_clear() {
-  std::lock_guard<std::mutex> lk(g_jp_mu);
-  for (JlShortCacheEntry& e : g_short_cache) wipe(&e, sizeof(e));
-  g_short_cache.clear();
-  for (JlSplitCacheEntry& e : g_split_cache) wipe(&e, sizeof(e));
-  g_split_cache.clear();
-}
-
-// E = L (2^s + 1) + 261 (e - 2^s), L = 1044, s = bit length of e - 1: a binary chain over e (squares that
-// drop R, short products that drop 2^261) leaves h^e 2^-(E - 2L), so 2^E = 2^f R^2 brings it to h^e R
-static Big chain_exponent(const Big& K) {
-  const int KSB = FBM_QA_LB * FBM_NA_SHORT_LIMBS;  // 261
-  const int s = big_bits(K) - 1;
-  Big v(K.begin(), K.end());
-  v.resize(64, 0u);
-  v[s >> 5] &= ~(1u << (s & 31));
-  Big E(66, 0u);
-  uint64_t c = 0;
-  for (int i = 0; i < 64; ++i) {  // 261 v
-    c += (uint64_t)v[i] * (uint64_t)KSB;
-    E[i] = (uint32_t)c;
-    c >>= 32;
-  }
-  E[64] = (uint32_t)c;
-  auto add_at = [&](uint64_t val, int bit) {  // E += val << bit
-    const int w = bit >> 5, sh2 = bit & 31;
-    unsigned __int128 add = (unsigned __int128)val << sh2;
-    uint64_t cy = 0;
-    for (int i = w; i < (int)E.size(); ++i) {
-      const uint64_t t = (uint64_t)E[i] + (uint64_t)(uint32_t)add + cy;
-      E[i] = (uint32_t)t;
-      cy = t >> 32;
-      add >>= 32;
-      if (!add && !cy) break;
-    }
-  };
-  const int Lb = FBM_QA_L * FBM_QA_LB;  // 1044
-  add_at((uint64_t)Lb, s);
-  add_at((uint64_t)Lb, 0);
-  wipe(v.data(), v.size() * 4);
-  return E;
-}
-
-// N's sliding-window schedule (width FBM_WIN_N) from the accumulator 1: every window, the leading one
-// included, is an op (squarings << FBM_OP_SHIFT | table index + 1).  Returns the op count, or -1.
-static int build_n_schedule(const Big& N, uint16_t* op) {
-  auto bit = [&](int i) -> int { return (N[i >> 5] >> (i & 31)) & 1; };
-  int n = 0, pending = 0;
-  for (int i = big_bits(N) - 1; i >= 0;) {
-    if (!bit(i)) {
-      ++pending;
-      --i;
-      continue;
-    }
-    int l = i - FBM_WIN_N + 1;
-    if (l < 0) l = 0;
-    while (!bit(l)) ++l;
-    int val = 0;
-    for (int j = i; j >= l; --j) val = (val << 1) | bit(j);
-    int nsq = pending + i - l + 1;
-    for (; nsq > FBM_OP_MAXSQ; nsq -= FBM_OP_MAXSQ) {
-      if (n >= FBM_MAX_OPS) return -1;
-      op[n++] = (uint16_t)(FBM_OP_MAXSQ << FBM_OP_SHIFT);
-    }
-    if (n >= FBM_MAX_OPS) return -1;
-    op[n++] = (uint16_t)((nsq << FBM_OP_SHIFT) | ((val - 1) / 2 + 1));
-    pending = 0;
-    i = l - 1;
-  }
-  if (pending > 0) {  // (an even N: outside the short path, kept for completeness)
-    if (n >= FBM_MAX_OPS || pending > FBM_OP_MAXSQ) return -1;
-    op[n++] = (uint16_t)(pending << FBM_OP_SHIFT);
-  }
-  return n;
-}
-
-// The split exponentiation's half of JlShort / JlSched (fbm_internal.hpp) for a key with |key| >= N on the
-// short path's domain; keys below N leave sc.sb1 = -1 (the unsplit chain).  dg: the digest of (N, |key|).
-static void build_split(const Big& N, const uint32_t* key, const uint32_t dg[8], JlSched& sc, JlShort& sh) {
-  Big K(key, key + 64);
-  if (big_cmp(K, N) < 0) return;
-  Big k1, k0;
-  big_divmod(K, N, k1, k0);
-  k1.resize(64, 0u);
-  k0.resize(32, 0u);
-  const int n_nops = build_n_schedule(N, sh.nop);
-  if (n_nops >= 0) {
-    memcpy(sh.k1w, k1.data(), sizeof(sh.k1w));
-    memcpy(sh.k0w, k0.data(), sizeof(sh.k0w));
-    bool hit = false;
-    {
-      std::lock_guard<std::mutex> lk(g_jp_mu);
-      for (const JlSplitCacheEntry& e : g_split_cache)
-        if (memcmp(e.digest, dg, sizeof(e.digest)) == 0) {
-          memcpy(sh.c1, e.c1, sizeof(sh.c1));
-          memcpy(sh.cp, e.cp, sizeof(sh.cp));
-          memcpy(sh.one, e.one, sizeof(sh.one));
-          hit = true;
-          break;
-        }
-    }
-    if (!hit) {
-      Big M = big_mul(N, N);
-      big_trim(M);
-      auto digits = [&](const Big& v, uint32_t* dst) {  // v mod N^2 as the digit pair (v mod N, v div N)
-        Big q, r;
-        big_divmod(v, N, q, r);
-        to_limbs_host(r, dst, FBM_QA_L, FBM_QA_LB);
-        to_limbs_host(q, dst + FBM_QA_L, FBM_QA_L, FBM_QA_LB);
-      };
-      Big E1 = chain_exponent(k1);  // C1 = 2^f1 R^2 mod N
-      to_limbs_host(pow2_mod_big(E1, N), sh.c1, FBM_QA_L, FBM_QA_LB);
-      Big Ep(34, 0u);  // C' = 2^(261 k0 + 1044) mod N^2
-      uint64_t c = (uint64_t)(FBM_QA_L * FBM_QA_LB);
-      for (int i = 0; i < 32; ++i) {
-        c += (uint64_t)k0[i] * (uint64_t)(FBM_QA_LB * FBM_NA_SHORT_LIMBS);
-        Ep[i] = (uint32_t)c;
-        c >>= 32;
-      }
-      Ep[32] = (uint32_t)c;
-      digits(pow2_mod_big(Ep, M), sh.cp);
-      Big Eo(1, (uint32_t)(FBM_QA_L * FBM_QA_LB));  // the Montgomery one, R mod N^2
-      digits(pow2_mod_big(Eo, M), sh.one);
-      wipe(E1.data(), E1.size() * 4);
-      wipe(Ep.data(), Ep.size() * 4);
-      JlSplitCacheEntry e;
-      memcpy(e.digest, dg, sizeof(e.digest));
-      memcpy(e.c1, sh.c1, sizeof(e.c1));
-      memcpy(e.cp, sh.cp, sizeof(e.cp));
-      memcpy(e.one, sh.one, sizeof(e.one));
-      std::lock_guard<std::mutex> lk(g_jp_mu);
-      if (g_split_cache.size() >= 32) {
-        wipe(&g_split_cache.front(), sizeof(JlSplitCacheEntry));
-        g_split_cache.erase(g_split_cache.begin());
-      }
-      g_split_cache.push_back(e);
-      wipe(&e, sizeof(e));
-    }
-    sc.sb1 = big_bits(k1) - 1;
-    sc.n_nops = n_nops;
-    sc.nbn = big_bits(N);
-  }
-  wipe(K.data(), K.size() * 4);
-  wipe(k1.data(), k1.size() * 4);
-  wipe(k0.data(), k0.size() * 4);
-}
-
-// The short path (jl_exp_kernel): possible for N > 2^262 (D = N - 2^261 > the product's quotient
-// m < 2^261); used with a nonzero key.  Returns whether N qualifies (then sh.d is valid and the
-// constants block gets it); sets sc.sbits and sh.kw / sh.corr when the key does too.
-static bool build_short(const uint32_t* biprime, const uint32_t* key, int is_zero, JlSched& sc, JlShort& sh,
-                        bool short_on) {
-  memset(&sh, 0, sizeof(sh));
-  sc.sbits = sc.sb1 = -1;
-  sc.n_nops = sc.nbn = 0;
-  if (!short_on) return false;
-  Big N(biprime, biprime + 32);
-  big_trim(N);
-  const int KSB = FBM_QA_LB * FBM_NA_SHORT_LIMBS;  // 261
-  if (big_bits(N) < KSB + 2 || !(N[0] & 1u)) return false;
-  {  // D = N - 2^261
-    Big D(N.begin(), N.end());
-    Big p(KSB / 32 + 1, 0u);
-    p[KSB / 32] = 1u << (KSB % 32);
-    big_sub_inplace(D, p);
-    to_limbs_host(D, sh.d, FBM_QA_L, FBM_QA_LB);
-  }
-  if (is_zero) return true;
-  Big K(key, key + 64);
-  const int nb = big_bits(K);
-  for (int i = 0; i < 64; ++i) sh.kw[i] = key[i];
-  sc.sbits = nb - 1;
-  uint32_t dg[8];
-  {
-    uint32_t msg[96];
-    memcpy(msg, biprime, 32 * 4);
-    memcpy(msg + 32, key, 64 * 4);
-    sha256_words(msg, 96, dg);
-    wipe(msg, sizeof(msg));
-  }
-  build_split(N, key, dg, sc, sh);
-  {
-    std::lock_guard<std::mutex> lk(g_jp_mu);
-    for (const JlShortCacheEntry& e : g_short_cache)
-      if (memcmp(e.digest, dg, sizeof(dg)) == 0) {
-        memcpy(sh.corr, e.corr, sizeof(sh.corr));
-        return true;
-      }
-  }
-  // E = L (2^s + 1) + 261 (|key| - 2^s), L = 1044, s = nb - 1: the chain leaves h^|key| 2^-(E - 2L)
-  Big E = chain_exponent(K);
-  Big M = big_mul(N, N);
-  big_trim(M);
-  const Big C = pow2_mod_big(E, M);
-  Big q, r;
-  big_divmod(C, N, q, r);
-  to_limbs_host(r, sh.corr, FBM_QA_L, FBM_QA_LB);
-  to_limbs_host(q, sh.corr + FBM_QA_L, FBM_QA_L, FBM_QA_LB);
-  wipe(K.data(), K.size() * 4);  // (K, E: the key and its exponent -- not kept)
-  wipe(E.data(), E.size() * 4);
-  JlShortCacheEntry e;
-  memcpy(e.digest, dg, sizeof(dg));
-  memcpy(e.corr, sh.corr, sizeof(e.corr));
-  std::lock_guard<std::mutex> lk(g_jp_mu);
-  if (g_short_cache.size() >= 32) {
-    wipe(&g_short_cache.front(), sizeof(JlShortCacheEntry));
-    g_short_cache.erase(g_short_cache.begin());
-  }
-  g_short_cache.push_back(e);
-  wipe(&e, sizeof(e));
-  return true;
 }
 
 static uint64_t table_slots_for(uint64_t n_ct) {
@@ -1140,14 +206,7 @@ extern "C" {
 
 int fbm_abi_version(void) { return FBM_ABI_VERSION; }
 
-void fbm_jl_clear_caches(void) {
-  short_cache_clear();  // the only one derived from a key (zeroed)
-  {
-    std::lock_guard<std::mutex> lk(g_jp_mu);
-    g_jp_cache.clear();  // per-N public parameters
-    g_rk_cache.clear();
-  }
-}
+void fbm_jl_clear_caches(void) { setup_clear_caches(); }
 
 const char* fbm_last_error(void) { return g_err; }
 
@@ -1409,34 +468,82 @@ static bool jl_compact_h() {
 #endif
 }
 
+// A workspace as its members in order, each 256-byte aligned; `off` after the last one is its size, so
+// a layout and the size its *_workspace function reports come from the same walk.
+struct WsWalk {
+  uintptr_t base;
+  uint64_t off;
+  uint32_t* take(uint64_t bytes) {
+    uint32_t* p = (uint32_t*)(base + off);
+    off += align256(bytes);
+    return p;
+  }
+};
+static uint64_t blocked_bytes(uint64_t n_ct) { return ((n_ct + 255) / 256) * 256 * FBM_NL * 4; }
+
 // encrypt workspace: ops | cst | pt [n_ct][32] | nude (blocked) | H [n_ct][64] | table |
 //                    H^-1 [n_ct][64] + y [n_ct][32] (negative keys) | Hc [n_ct][8] (compact H rows)
-uint64_t fbm_jl_encrypt_workspace(uint64_t n_ct) {
-  const uint64_t slots = table_slots_for(n_ct);
-  (void)slots;
-  return align256(FBM_OPS_WORDS * 4) + align256(FBM_CST_WORDS * 4) + align256(n_ct * 32 * 4) +
-         align256(((n_ct + 255) / 256) * 256 * FBM_NL * 4) + 2 * align256(n_ct * 64 * 4) + align256(n_ct * 32 * 4) +
-         align256(jl_table_bytes(n_ct)) + align256(n_ct * 8 * 4);
+struct JlEncWs {
+  uint32_t *ops, *cst, *pt, *nude, *H, *table, *Hinv, *Y, *Hc;
+  uint64_t slots, bytes;
+};
+static JlEncWs enc_ws(void* workspace, uint64_t n_ct) {
+  WsWalk k{(uintptr_t)workspace, 0};
+  JlEncWs w;
+  w.slots = table_slots_for(n_ct);
+  w.ops = k.take(FBM_OPS_WORDS * 4);
+  w.cst = k.take(FBM_CST_WORDS * 4);
+  w.pt = k.take(n_ct * 32 * 4);
+  w.nude = k.take(blocked_bytes(n_ct));
+  w.H = k.take(n_ct * 64 * 4);
+  w.table = k.take(jl_table_bytes(n_ct));
+  w.Hinv = k.take(n_ct * 64 * 4);  // negative keys only: H^|key| digits (after the table)
+  w.Y = k.take(n_ct * 32 * 4);
+  w.Hc = k.take(n_ct * 8 * 4);  // compact H rows: 32 B per ciphertext
+  if (!jl_compact_h()) w.Hc = nullptr;
+  w.bytes = k.off;
+  return w;
 }
 
-uint64_t fbm_jl_aggregate_workspace(uint64_t n_ct) {
-  const uint64_t slots = table_slots_for(n_ct);
-  (void)slots;
-  return align256(FBM_OPS_WORDS * 4) + align256(FBM_CST_WORDS * 4) + align256(((n_ct + 255) / 256) * 256 * FBM_NL * 4) +
-         3 * align256(n_ct * 64 * 4) + align256(n_ct * 32 * 4) + align256(jl_table_bytes(n_ct)) + align256(n_ct * 8 * 4);
+// aggregate workspace: ops | cst | X (blocked) | H [n_ct][64] | E [n_ct][64] | F [n_ct][64] |
+//                      xs [n_ct][32] | table | Hc [n_ct][8]
+struct JlAggWs {
+  uint32_t *ops, *cst, *X, *H, *E, *F, *xs, *table, *Hc;
+  uint64_t slots, bytes;
+};
+static JlAggWs agg_ws(void* workspace, uint64_t n_ct) {
+  WsWalk k{(uintptr_t)workspace, 0};
+  JlAggWs w;
+  w.slots = table_slots_for(n_ct);
+  w.ops = k.take(FBM_OPS_WORDS * 4);
+  w.cst = k.take(FBM_CST_WORDS * 4);
+  w.X = k.take(blocked_bytes(n_ct));
+  w.H = k.take(n_ct * 64 * 4);
+  w.E = k.take(n_ct * 64 * 4);
+  w.F = k.take(n_ct * 64 * 4);
+  w.xs = k.take(n_ct * 32 * 4);
+  w.table = k.take(jl_table_bytes(n_ct));
+  w.Hc = k.take(n_ct * 8 * 4);
+  if (!jl_compact_h()) w.Hc = nullptr;
+  w.bytes = k.off;
+  return w;
 }
 
-// phase bit 1: the prologue (status word, constants, pack, nude, FDH, and the inverse of H
-// for a negative key); bit 2: the exponentiation.  Both phases rebuild the same host
-// parameters from the same arguments and use the same workspace, so (1 then 2) == 3.
-static int jl_encrypt_impl(const void* x, int x_dtype, uint64_t n, double clip, double two_clip, double target_f,
-                           uint64_t target_m1, uint64_t weight, int es, int cr, const uint32_t* biprime,
-                           const uint32_t* key, int key_negative, const uint32_t* tau, uint64_t ct_offset, uint32_t* ct_out,
-                           void* workspace, uint32_t* stats, void* stream, int phase) {
-  hipStream_t s = (hipStream_t)stream;
+uint64_t fbm_jl_encrypt_workspace(uint64_t n_ct) { return enc_ws(nullptr, n_ct).bytes; }
+
+uint64_t fbm_jl_aggregate_workspace(uint64_t n_ct) { return agg_ws(nullptr, n_ct).bytes; }
+
+// The argument checks fbm_jl_encrypt (its phases) and fbm_jl_encrypt_factor share, in the order both report
+// them.  by_factor: the caller brings the factor rows instead of key and round.  zero: zero the status words
+// first.  n_ct = 0 with FBM_OK: an empty call, nothing to launch.
+static int jl_encrypt_checks(const void* x, int x_dtype, uint64_t n, double clip, double two_clip, double target_f,
+                             uint64_t target_m1, uint64_t weight, int cr, const uint32_t* biprime, const uint32_t* key,
+                             const uint32_t* tau, bool by_factor, const uint32_t* factor, const uint32_t* ct_out,
+                             const void* workspace, uint32_t* stats, hipStream_t s, bool zero, QuantParams& qp,
+                             uint64_t& n_ct) {
   int rc;
-  if ((phase & 1) && (rc = zero_stats(stats, s))) return rc;
-  QuantParams qp;
+  n_ct = 0;
+  if (zero && (rc = zero_stats(stats, s))) return rc;
   if ((rc = quant_params(clip, two_clip, target_f, target_m1, qp))) return rc;
   if (!float_dtype(x_dtype) && x_dtype != FBM_U64 && x_dtype != FBM_U128 && x_dtype != FBM_PT) {
     set_error("x_dtype must be FBM_F16, FBM_BF16, FBM_F32, FBM_F64, FBM_U64, FBM_U128 or FBM_PT");
@@ -1450,11 +557,11 @@ static int jl_encrypt_impl(const void* x, int x_dtype, uint64_t n, double clip, 
     set_error("plaintext input (FBM_PT) takes cr = 1");
     return FBM_E_ARG;
   }
-  if (!biprime || !key) {
-    set_error("null biprime/key");
+  if (!biprime || (!by_factor && !key)) {
+    set_error(by_factor ? "null biprime" : "null biprime/key");
     return FBM_E_ARG;
   }
-  if (!tau) {  // the round is FDH's input: never defaulted (a NULL would silently mean round 0)
+  if (!by_factor && !tau) {  // the round is FDH's input: never defaulted (a NULL would silently mean round 0)
     set_error("null tau (the round's %d limbs)", FBM_TAU_LIMBS);
     return FBM_E_ARG;
   }
@@ -1463,22 +570,48 @@ static int jl_encrypt_impl(const void* x, int x_dtype, uint64_t n, double clip, 
     set_error("invalid cr=%d", cr);
     return FBM_E_ARG;
   }
-  const uint64_t n_ct = (n + (uint64_t)cr - 1) / (uint64_t)cr;
-  if (n_ct > FBM_JL_MAX_CT) {
+  const uint64_t cts = (n + (uint64_t)cr - 1) / (uint64_t)cr;
+  if (cts > FBM_JL_MAX_CT) {
     set_error("%llu ciphertexts exceed FBM_JL_MAX_CT per call; split the range with ct_offset",
-              (unsigned long long)n_ct);
+              (unsigned long long)cts);
     return FBM_E_UNSUPPORTED;
   }
-  if (!x || !ct_out || !workspace) {
+  if (!x || (by_factor && !factor) || !ct_out || !workspace) {
     set_error("null pointer argument");
     return FBM_E_ARG;
+  }
+  if (by_factor) {  // jl_encf_kernel stages N pt + 1 in the output rows before it reads the factor rows
+    const uintptr_t o0 = (uintptr_t)ct_out, o1 = o0 + cts * 256, f0 = (uintptr_t)factor, f1 = f0 + cts * 256;
+    if (o0 < f1 && f0 < o1) {
+      set_error("fbm_jl_encrypt_factor: ct_out must not overlap factor");
+      return FBM_E_ARG;
+    }
   }
   if ((int64_t)weight <= -(int64_t)(1 << 17)) {  // negative: the two's complement of a weight > -2^17
     set_error("negative weight %lld outside (-2^17, 0)", (long long)(int64_t)weight);
     return FBM_E_ARG;
   }
+  n_ct = cts;
+  return FBM_OK;
+}
+
+// phase bit 1: the prologue (status word, constants, pack, nude, FDH, and the inverse of H
+// for a negative key); bit 2: the exponentiation.  Both phases rebuild the same host
+// parameters from the same arguments and use the same workspace, so (1 then 2) == 3.
+static int jl_encrypt_impl(const void* x, int x_dtype, uint64_t n, double clip, double two_clip, double target_f,
+                           uint64_t target_m1, uint64_t weight, int es, int cr, const uint32_t* biprime,
+                           const uint32_t* key, int key_negative, const uint32_t* tau, uint64_t ct_offset, uint32_t* ct_out,
+                           void* workspace, uint32_t* stats, void* stream, int phase) {
+  hipStream_t s = (hipStream_t)stream;
+  QuantParams qp;
+  uint64_t n_ct;
+  int rc = jl_encrypt_checks(x, x_dtype, n, clip, two_clip, target_f, target_m1, weight, cr, biprime, key, tau, false,
+                             nullptr, ct_out, workspace, stats, s, (phase & 1) != 0, qp, n_ct);
+  if (rc || !n_ct) return rc;
   bool generic, short_on;
   if ((rc = jl_path_for(workspace, phase, 3, biprime, generic, short_on))) return rc;
+  const JlEncWs w = enc_ws(workspace, n_ct);
+  uint32_t *const cst = w.cst, *const pt = w.pt, *const H = w.H;
   if (generic) {  // any N (fbm_gen.hip): pack -> FDH -> H^key (N pt + 1) mod N^2
     if (es < 1 || es > 100 || (int64_t)es * cr > 1024) {
       set_error("invalid VES parameters es=%d cr=%d", es, cr);
@@ -1488,10 +621,6 @@ static int jl_encrypt_impl(const void* x, int x_dtype, uint64_t n, double clip, 
     JlParams fp;
     if ((rc = build_gen_ctx(biprime, key, key_negative, g)) || (rc = fdh_params_for_biprime(biprime, tau, ct_offset, fp)))
       return rc;
-    uint8_t* ws = (uint8_t*)workspace;  // the encrypt workspace's cst | pt | (nude) | H
-    uint32_t* cst = (uint32_t*)(ws + align256(FBM_OPS_WORDS * 4));
-    uint32_t* pt = (uint32_t*)(ws + align256(FBM_OPS_WORDS * 4) + align256(FBM_CST_WORDS * 4));
-    uint32_t* H = (uint32_t*)((uint8_t*)pt + align256(n_ct * 32 * 4) + align256(((n_ct + 255) / 256) * 256 * FBM_NL * 4));
     const uint32_t* ptp = x_dtype == FBM_PT ? (const uint32_t*)x : pt;
     if (phase & 1) {
       if ((rc = launch_jl_gen_setup(g, cst, s))) return rc;
@@ -1515,36 +644,17 @@ static int jl_encrypt_impl(const void* x, int x_dtype, uint64_t n, double clip, 
   jp.key_is_zero = is_zero;
   JlShort sh;
   const bool shq = build_short(biprime, key, is_zero, sc, sh, short_on);
-  const uint64_t slots = table_slots_for(n_ct);
-  uint8_t* ws = (uint8_t*)workspace;
-  uint32_t* ops = (uint32_t*)ws;
-  uint64_t off = align256(FBM_OPS_WORDS * 4);
-  uint32_t* cst = (uint32_t*)(ws + off);
-  off += align256(FBM_CST_WORDS * 4);
-  uint32_t* pt = (uint32_t*)(ws + off);
-  off += align256(n_ct * 32 * 4);
-  uint32_t* nude = (uint32_t*)(ws + off);
-  off += align256(((n_ct + 255) / 256) * 256 * FBM_NL * 4);
-  uint32_t* H = (uint32_t*)(ws + off);
-  off += align256(n_ct * 64 * 4);
-  uint32_t* table = (uint32_t*)(ws + off);
-  off += align256(jl_table_bytes(n_ct));
-  uint32_t* Hinv = (uint32_t*)(ws + off);  // negative keys only: H^|key| digits (after the table)
-  off += align256(n_ct * 64 * 4);
-  uint32_t* Y = (uint32_t*)(ws + off);
-  off += align256(n_ct * 32 * 4);
-  uint32_t* Hc = jl_compact_h() ? (uint32_t*)(ws + off) : nullptr;  // compact H rows: 32 B per ciphertext
   const bool inverse = key_negative && !is_zero;
   if (phase & 1) {
-    if ((rc = timed("jl_setup", s, [&] { return launch_jl_setup(jp, sc, ops, cst, s, shq ? &sh : nullptr); })))
+    if ((rc = timed("jl_setup", s, [&] { return launch_jl_setup(jp, sc, w.ops, cst, s, shq ? &sh : nullptr); })))
       return rc;
     if (x_dtype != FBM_PT &&
         (rc = timed("jl_pack", s, [&] { return launch_jl_pack(x, x_dtype, n, qp, weight, es, cr, n_ct, pt, stats, s); })))
       return rc;
     const uint32_t* ptp = x_dtype == FBM_PT ? (const uint32_t*)x : pt;  // UserKey.encrypt: packed already
     const int negw = (int64_t)weight < 0 ? 1 : 0;
-    if ((rc = timed("jl_nude", s, [&] { return launch_jl_nude(ptp, n_ct, jp, negw, nude, s); }))) return rc;
-    if (!is_zero && (rc = timed("jl_fdh", s, [&] { return launch_jl_fdh(n_ct, jp, H, stats, s, Hc); }))) return rc;
+    if ((rc = timed("jl_nude", s, [&] { return launch_jl_nude(ptp, n_ct, jp, negw, w.nude, s); }))) return rc;
+    if (!is_zero && (rc = timed("jl_fdh", s, [&] { return launch_jl_fdh(n_ct, jp, H, stats, s, w.Hc); }))) return rc;
   }
   if (!(phase & 2)) return FBM_OK;
   if (inverse) {
@@ -1552,15 +662,15 @@ static int jl_encrypt_impl(const void* x, int x_dtype, uint64_t n, double clip, 
     // the power's N-adic digits (any H < 2^2048), then the lift inverts it and multiplies
     // by nude in the same pass
     if ((rc = timed("jl_exp", s, [&] {
-           return launch_jl_exp(H, n_ct, jp, sc, FBM_EXP_DEC | FBM_EXP_OUT_NADIC, nullptr, table, slots, ops, cst, Hinv,
-                                s, Hc);
+           return launch_jl_exp(H, n_ct, jp, sc, FBM_EXP_DEC | FBM_EXP_OUT_NADIC, nullptr, w.table, w.slots, w.ops, cst,
+                                w.Hinv, s, w.Hc);
          })))
       return rc;
-    return timed("jl_inv", s, [&] { return launch_jl_inv(n_ct, jp, cst, Hinv, Y, nude, ct_out, stats, s); });
+    return timed("jl_inv", s, [&] { return launch_jl_inv(n_ct, jp, cst, w.Hinv, w.Y, w.nude, ct_out, stats, s); });
   }
   // a phase-2-only call inside an open batch (fbm_jl_batch_begin) is recorded, not launched
   // (and not timed: the batch's one launch is, at the flush)
-  auto go = [&] { return launch_jl_exp(H, n_ct, jp, sc, 0, nude, table, slots, ops, cst, ct_out, s, Hc); };
+  auto go = [&] { return launch_jl_exp(H, n_ct, jp, sc, 0, w.nude, w.table, w.slots, w.ops, cst, ct_out, s, w.Hc); };
   const bool rec = phase == 2 && jl_batch_active();
   const bool acc = jl_batch_accept(rec);
   rc = rec ? go() : timed("jl_exp", s, go);
@@ -1584,52 +694,11 @@ int fbm_jl_encrypt_factor(const void* x, int x_dtype, uint64_t n, double clip, d
                           uint64_t target_m1, uint64_t weight, int es, int cr, const uint32_t* biprime,
                           const uint32_t* factor, uint32_t* ct_out, void* workspace, uint32_t* stats, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  int rc = zero_stats(stats, s);
-  if (rc) return rc;
   QuantParams qp;
-  if ((rc = quant_params(clip, two_clip, target_f, target_m1, qp))) return rc;
-  if (!float_dtype(x_dtype) && x_dtype != FBM_U64 && x_dtype != FBM_U128 && x_dtype != FBM_PT) {
-    set_error("x_dtype must be FBM_F16, FBM_BF16, FBM_F32, FBM_F64, FBM_U64, FBM_U128 or FBM_PT");
-    return FBM_E_ARG;
-  }
-  if ((x_dtype == FBM_U128 || x_dtype == FBM_PT) && weight != 1) {
-    set_error("raw-integer / plaintext inputs take weight 1");
-    return FBM_E_ARG;
-  }
-  if (x_dtype == FBM_PT && cr != 1) {
-    set_error("plaintext input (FBM_PT) takes cr = 1");
-    return FBM_E_ARG;
-  }
-  if (!biprime) {
-    set_error("null biprime");
-    return FBM_E_ARG;
-  }
-  if (n == 0) return FBM_OK;
-  if (cr < 1) {
-    set_error("invalid cr=%d", cr);
-    return FBM_E_ARG;
-  }
-  const uint64_t n_ct = (n + (uint64_t)cr - 1) / (uint64_t)cr;
-  if (n_ct > FBM_JL_MAX_CT) {
-    set_error("%llu ciphertexts exceed FBM_JL_MAX_CT per call; split the range with ct_offset",
-              (unsigned long long)n_ct);
-    return FBM_E_UNSUPPORTED;
-  }
-  if (!x || !factor || !ct_out || !workspace) {
-    set_error("null pointer argument");
-    return FBM_E_ARG;
-  }
-  {  // jl_encf_kernel stages N pt + 1 in the output rows before it reads the factor rows
-    const uintptr_t o0 = (uintptr_t)ct_out, o1 = o0 + n_ct * 256, f0 = (uintptr_t)factor, f1 = f0 + n_ct * 256;
-    if (o0 < f1 && f0 < o1) {
-      set_error("fbm_jl_encrypt_factor: ct_out must not overlap factor");
-      return FBM_E_ARG;
-    }
-  }
-  if ((int64_t)weight <= -(int64_t)(1 << 17)) {
-    set_error("negative weight %lld outside (-2^17, 0)", (long long)(int64_t)weight);
-    return FBM_E_ARG;
-  }
+  uint64_t n_ct;
+  int rc = jl_encrypt_checks(x, x_dtype, n, clip, two_clip, target_f, target_m1, weight, cr, biprime, nullptr, nullptr,
+                             true, factor, ct_out, workspace, stats, s, true, qp, n_ct);
+  if (rc || !n_ct) return rc;
   if ((biprime[0] & 1u) == 0u || jl_is_one(biprime)) {
     set_error("fbm_jl_encrypt_factor takes an odd N >= 3 (fbm_jl_encrypt takes any N)");
     return FBM_E_UNSUPPORTED;
@@ -1638,11 +707,9 @@ int fbm_jl_encrypt_factor(const void* x, int x_dtype, uint64_t n, double clip, d
   if ((rc = build_jl_params(biprime, es, cr, nullptr, 0, jp))) return rc;
   JlSched none;
   memset(&none, 0, sizeof(none));
-  uint8_t* ws = (uint8_t*)workspace;  // the encrypt workspace's ops | cst | pt
-  uint32_t* ops = (uint32_t*)ws;
-  uint32_t* cst = (uint32_t*)(ws + align256(FBM_OPS_WORDS * 4));
-  uint32_t* pt = (uint32_t*)(ws + align256(FBM_OPS_WORDS * 4) + align256(FBM_CST_WORDS * 4));
-  if ((rc = timed("jl_setup", s, [&] { return launch_jl_setup(jp, none, ops, cst, s); }))) return rc;
+  const JlEncWs w = enc_ws(workspace, n_ct);  // of the encrypt workspace: ops | cst | pt
+  uint32_t *const cst = w.cst, *const pt = w.pt;
+  if ((rc = timed("jl_setup", s, [&] { return launch_jl_setup(jp, none, w.ops, cst, s); }))) return rc;
   {  // R^2 mod N^2: two products, each dropping one R
     JlRk r;
     jl_rk_for(jp.N32, 1, r);
@@ -1666,37 +733,6 @@ int fbm_jl_encrypt_phase(const void* x, int x_dtype, uint64_t n, double clip, do
   }
   return jl_encrypt_impl(x, x_dtype, n, clip, two_clip, target_f, target_m1, weight, es, cr, biprime, key,
                          key_negative, tau, ct_offset, ct_out, workspace, stats, stream, phase);
-}
-
-// aggregate workspace: ops | cst | X (blocked) | H [n_ct][64] | E [n_ct][64] | F [n_ct][64] |
-//                      xs [n_ct][32] | table    (fbm_jl_aggregate_workspace)
-struct JlAggWs {
-  uint32_t *ops, *cst, *X, *H, *E, *F, *xs, *table, *Hc;
-  uint64_t slots;
-};
-static JlAggWs agg_ws(void* workspace, uint64_t n_ct) {
-  JlAggWs w;
-  uint8_t* ws = (uint8_t*)workspace;
-  w.slots = table_slots_for(n_ct);
-  uint64_t off = 0;
-  w.ops = (uint32_t*)ws;
-  off += align256(FBM_OPS_WORDS * 4);
-  w.cst = (uint32_t*)(ws + off);
-  off += align256(FBM_CST_WORDS * 4);
-  w.X = (uint32_t*)(ws + off);
-  off += align256(((n_ct + 255) / 256) * 256 * FBM_NL * 4);
-  w.H = (uint32_t*)(ws + off);
-  off += align256(n_ct * 64 * 4);
-  w.E = (uint32_t*)(ws + off);
-  off += align256(n_ct * 64 * 4);
-  w.F = (uint32_t*)(ws + off);
-  off += align256(n_ct * 64 * 4);
-  w.xs = (uint32_t*)(ws + off);
-  off += align256(n_ct * 32 * 4);
-  w.table = (uint32_t*)(ws + off);
-  off += align256(jl_table_bytes(n_ct));
-  w.Hc = jl_compact_h() ? (uint32_t*)(ws + off) : nullptr;
-  return w;
 }
 
 // ServerKey's factor H(t_k)^sk0 mod N^2 (inverse first for sk0 < 0): depends on the round,
@@ -2020,15 +1056,11 @@ int fbm_jl_fdh_msg(uint64_t n, const uint32_t* t, int t_words, int bits_size, co
     });
   }
   // r of up to 255 digests: the incremental Montgomery residue of the wide kernel (fbm_jl.hip)
-  Big m(modulus_odd, modulus_odd + 32);
-  uint32_t inv = m[0];  // Newton: m^-1 mod 2^32
-  for (int i = 0; i < 5; ++i) inv *= 2u - m[0] * inv;
-  Big k1 = big_pow2_mod(1024 + 256, m), k2 = big_pow2_mod(2048, m);
-  k1.resize(32, 0u);
-  k2.resize(32, 0u);
+  uint32_t k1[32], k2[32], mp;
+  fdh_wide_consts(modulus_odd, k1, k2, mp);
   return timed("jl_fdh", s, [&] {
-    return launch_jl_fdh_msg_wide(n, t, t_words, msg_bytes, kmax, m.data(), k1.data(), k2.data(), 0u - inv,
-                                  modulus_even ? 1 : 0, h, h_words, stats, s);
+    return launch_jl_fdh_msg_wide(n, t, t_words, msg_bytes, kmax, modulus_odd, k1, k2, mp, modulus_even ? 1 : 0, h,
+                                  h_words, stats, s);
   });
 }
 
@@ -2110,18 +1142,8 @@ int fbm_jl_powmod(const uint32_t* h, const uint32_t* pt, uint64_t n_ct, const ui
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
-  uint8_t* ws = (uint8_t*)workspace;  // fbm_jl_encrypt_workspace: ops | cst | pt | nude | H | table | H^-1 | y
-  uint32_t* ops = (uint32_t*)ws;
-  uint64_t off = align256(FBM_OPS_WORDS * 4);
-  uint32_t* cst = (uint32_t*)(ws + off);
-  off += align256(FBM_CST_WORDS * 4) + align256(n_ct * 32 * 4);
-  uint32_t* nude = (uint32_t*)(ws + off);
-  off += align256(((n_ct + 255) / 256) * 256 * FBM_NL * 4) + align256(n_ct * 64 * 4);
-  uint32_t* table = (uint32_t*)(ws + off);
-  off += align256(jl_table_bytes(n_ct));
-  uint32_t* Hinv = (uint32_t*)(ws + off);
-  off += align256(n_ct * 64 * 4);
-  uint32_t* Y = (uint32_t*)(ws + off);
+  const JlEncWs w = enc_ws(workspace, n_ct);  // (its pt, H and Hc rows unused: h and pt are the caller's)
+  uint32_t *const ops = w.ops, *const cst = w.cst, *const nude = w.nude, *const table = w.table;
   if (jl_generic(biprime)) {
     GenCtx g;
     if ((rc = build_gen_ctx(biprime, key, key_negative, g)) || (rc = launch_jl_gen_setup(g, cst, s))) return rc;
@@ -2138,21 +1160,20 @@ int fbm_jl_powmod(const uint32_t* h, const uint32_t* pt, uint64_t n_ct, const ui
   jp.key_is_zero = is_zero;
   JlShort sh;
   const bool shq = build_short(biprime, key, is_zero, sc, sh, t_short_on != 0);
-  const uint64_t slots = table_slots_for(n_ct);
   if ((rc = timed("jl_setup", s, [&] { return launch_jl_setup(jp, sc, ops, cst, s, shq ? &sh : nullptr); })))
     return rc;
   const int mode = pt ? 0 : FBM_EXP_DEC;
   if (pt && (rc = timed("jl_nude", s, [&] { return launch_jl_nude(pt, n_ct, jp, 0, nude, s); }))) return rc;
   if (key_negative && !is_zero) {  // powmod with a negative exponent: (h^|key|)^-1, then * nude
     if ((rc = timed("jl_exp", s, [&] {
-           return launch_jl_exp(h, n_ct, jp, sc, FBM_EXP_DEC | FBM_EXP_OUT_NADIC, nullptr, table, slots, ops, cst, Hinv,
+           return launch_jl_exp(h, n_ct, jp, sc, FBM_EXP_DEC | FBM_EXP_OUT_NADIC, nullptr, table, w.slots, ops, cst, w.Hinv,
                                 s);
          })))
       return rc;
-    return timed("jl_inv", s, [&] { return launch_jl_inv(n_ct, jp, cst, Hinv, Y, pt ? nude : nullptr, out, stats, s); });
+    return timed("jl_inv", s, [&] { return launch_jl_inv(n_ct, jp, cst, w.Hinv, w.Y, pt ? nude : nullptr, out, stats, s); });
   }
   return timed("jl_exp", s, [&] {
-    return launch_jl_exp(h, n_ct, jp, sc, mode, pt ? nude : nullptr, table, slots, ops, cst, out, s);
+    return launch_jl_exp(h, n_ct, jp, sc, mode, pt ? nude : nullptr, table, w.slots, ops, cst, out, s);
   });
 }
 
@@ -2375,17 +1396,12 @@ int fbm_jl_set_short(int on) {
 }
 
 int fbm_test_short_cache(uint32_t* out, int cap_words) {
-  std::lock_guard<std::mutex> lk(g_jp_mu);
-  const int per = (int)(sizeof(JlShortCacheEntry) / 4);
-  const int n = (int)g_short_cache.size();
-  if (out) {
-    if (cap_words < n * per) {
-      set_error("fbm_test_short_cache: %d words needed", n * per);
-      return FBM_E_ARG;
-    }
-    for (int i = 0; i < n; ++i) memcpy(out + i * per, &g_short_cache[i], sizeof(JlShortCacheEntry));
+  const int need = short_cache_dump(out, cap_words);
+  if (out && cap_words < need) {
+    set_error("fbm_test_short_cache: %d words needed", need);
+    return FBM_E_ARG;
   }
-  return n * per;
+  return need;
 }
 
 int fbm_test_true_div_big(const uint64_t* x, uint64_t n, const uint32_t* k, int k_words, int negative, double* out) {

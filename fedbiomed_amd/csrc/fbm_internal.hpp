@@ -300,7 +300,7 @@ int launch_jl_decode(const uint32_t* xs, int es, int cr, uint64_t n_out, uint64_
                      double step, void* out, int out_dtype, uint64_t* sums, uint32_t* stats, hipStream_t s);
 
 // ---- the generic JL engine (fbm_gen.hip): any biprime N, even ones included ------------
-// Constants of one (N, key), host-built (fbm_capi.hip build_gen_ctx), copied into the call's
+// Constants of one (N, key), host-built (fbm_setup.hip build_gen_ctx), copied into the call's
 // constants block by jl_gen_setup_kernel.  32-bit limbs, little-endian; M = N^2 = 2^e m2 with
 // m2 odd; muX = floor(2^(64 kX) / X) (Barrett: kX + 1 words, or kX + 2 when X = 2^(32(kX-1)),
 // zero-padded); m2inv = m2^-1 mod 2^e.
@@ -357,5 +357,33 @@ int jl_engine_for(uint64_t n_ct);
 uint64_t jl_table_bytes(uint64_t n_ct);
 // compute units of the calling thread's current device (cached per device)
 int device_num_cu();
+
+// ---- host setup (fbm_setup.hip): per-modulus and per-key constants, and their caches ----------
+void wipe(void* p, size_t n);  // a zeroing the optimiser keeps (key-derived temporaries)
+// FDH.H's parameters only (fbm_jl_fdh and the generic engine): the gcd modulus' odd part
+// (>= 1; 1: every odd r is coprime) and whether r must be odd as well
+int fdh_params(const uint32_t* n_odd, int even, const uint32_t* tau, uint64_t ct_offset, JlParams& jp);
+// FDH(2048, N^2): gcd(r, N^2) == 1 iff r is coprime to N's odd part (and odd, for an even N)
+int fdh_params_for_biprime(const uint32_t* biprime, const uint32_t* tau, uint64_t ct_offset, JlParams& jp);
+// the wide fbm_jl_fdh_msg kernel's incremental Montgomery residue modulo the odd m (32 words, >= 1):
+// k1 = 2^1280 mod m, k2 = 2^2048 mod m, mp = -m^-1 mod 2^32
+void fdh_wide_consts(const uint32_t* modulus_odd, uint32_t k1[32], uint32_t k2[32], uint32_t& mp);
+// GenCtx of (N, key), any N >= 1; key may be NULL (the combine kernels)
+int build_gen_ctx(const uint32_t* biprime, const uint32_t* key, int key_negative, GenCtx& g);
+// JlParams of an odd N >= 3 (cached per N), with this call's VES shape, round and offset
+int build_jl_params(const uint32_t* biprime, int es, int cr, const uint32_t* tau, uint64_t ct_offset, JlParams& jp);
+// R^(P+1) mod N^2 (cached per (N, P)); n32: a modulus build_jl_params took
+void jl_rk_for(const uint32_t* n32, int n_parties, JlRk& r);
+// The table path's schedule: left-to-right sliding window (width FBM_WIN) over |key|, odd-power table.
+// FBM_E_ARG where the ops would pass FBM_MAX_OPS (sc holds those written so far).
+int build_schedule(const uint32_t* key, JlSched& sc, int& is_zero);
+// The short path (jl_exp_kernel): possible for N > 2^262 (D = N - 2^261 > the product's quotient
+// m < 2^261); used with a nonzero key.  Returns whether N qualifies (then sh.d is valid and the
+// constants block gets it); sets sc.sbits and sh.kw / sh.corr when the key does too, and the split
+// exponentiation's half of sc / sh for |key| >= N.
+bool build_short(const uint32_t* biprime, const uint32_t* key, int is_zero, JlSched& sc, JlShort& sh, bool short_on);
+void setup_clear_caches();  // fbm_jl_clear_caches: all four, the key-derived ones zeroed
+// the short path's cache entries (80 words each: digest, C) into out when cap_words holds them; returns the words
+int short_cache_dump(uint32_t* out, int cap_words);
 
 }  // namespace fbm

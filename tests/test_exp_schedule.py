@@ -1,4 +1,4 @@
-"""The table path's exponent schedule as the library builds it (fbm_capi.hip build_schedule, read through
+"""The table path's exponent schedule as the library builds it (fbm_setup.hip build_schedule, read through
 the test build's fbm_test_schedule hook), replayed in Python.  Host-only (no GPU).
 
 The kernels run the schedule blindly: table[first], then per op `nsq` squarings and one product with

@@ -3,7 +3,7 @@ path's per-(N, |key|) constant C is cached under a SHA-256 digest of (N, |key|),
 the digest and C, entries are zeroed on eviction, and fbm_jl_clear_caches() empties the cache.  The
 reference keeps nothing (a fresh SecaggCrypter per call: fedbiomed/node/secagg/_secagg_round.py:142).
 Host-only (no GPU): the cache is filled through the fbm_test_short_consts hook, which runs the same
-build_short the JL entry points call."""
+build_short (fbm_setup.hip) the JL entry points call."""
 
 import hashlib
 import random

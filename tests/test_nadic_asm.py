@@ -35,7 +35,7 @@ def limbs(x, n=L):
 
 def consts(N):
     """80-word constants block: N_0..N_9 at words 0..9, N_10..N_35 at 16..41, K'_0..K'_35 at
-    42..77 (the layout fbm_capi.hip's host setup writes)."""
+    42..77 (the layout the host setup, fbm_setup.hip, writes)."""
     K = (1 - R) % N
     kp = [MASK + v for v in limbs(K)]
     nl = limbs(N)

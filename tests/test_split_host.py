@@ -1,4 +1,4 @@
-"""The split exponentiation's host schedule (fbm_capi.hip build_split, through the test build's
+"""The split exponentiation's host schedule (fbm_setup.hip build_split, through the test build's
 fbm_test_split_consts; no GPU): for |key| = k1 N + k0 >= N the words of k1 and k0, C1 = 2^f1 R^2 mod N,
 C' = 2^(261 k0) R mod N^2, the Montgomery one and N's window schedule, against Python integers -- keys at
 the edges (N - 1 has no split; N: k0 = 0, C' = R; N + 1 and 2N - 1: k1 = 1, an empty phase-1 chain, f1 = 0;
