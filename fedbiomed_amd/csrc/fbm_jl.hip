@@ -262,10 +262,6 @@ __global__ void __launch_bounds__(256) jl_nude_kernel(const uint32_t* __restrict
   uint32_t p29[FBM_QA_L];
   relimb_28_29(p28, p29);
   uint32_t* dst = launder_v(nude + (ct >> 8) * (FBM_NUDE_ROWS * 256) + (ct & 255));
-#ifdef FBM_NUDE_BOTH_DIGITS
-#pragma unroll
-  for (int k = 0; k < FBM_QA_L; ++k) dst[k * 256] = k == 0 ? 1u : 0u;
-#endif
 #pragma unroll
   for (int k = 0; k < FBM_QA_L; ++k) dst[(FBM_NUDE_D1 + k) * 256] = p29[k];
 }
@@ -822,14 +818,6 @@ __device__ __forceinline__ void tbl_store(uint32_t* tb, int e, const uint32_t (&
 __device__ __forceinline__ void tbl_load(const uint32_t* tb, int e, uint32_t (&v)[FBM_NL]) {
   col_load(tb + e * (FBM_NL * 256), v);
 }
-__device__ __forceinline__ void load_row64(const uint32_t* p, uint32_t (&w)[64]) {
-  const uint4* s = reinterpret_cast<const uint4*>(launder_v(p));
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const uint4 v = s[i];
-    w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-  }
-}
 __device__ __forceinline__ void load_row32(const uint4* s, uint32_t (&w)[32]) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -1063,11 +1051,7 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_exp_kernel(const uint32_t* __
 #pragma unroll
         for (int i = 0; i < 64; ++i) h[i] = i == 0 ? 1u : 0u;
       } else {
-#ifdef FBM_EXP_FULL_H_LOAD  // (A/B variant: the round-3 whole-row load)
-        load_row64(SEG(H, H_a) + ct * 64, h);
-#else
         load_h(SEG(H, H_a), SEG(Hc, Hc_a), ct, h);
-#endif
       }
       uint32_t h29[2 * NA];
       {  // h = h_lo + h_hi R: the 72-limb decomposition is (h_lo, h_hi)
@@ -1163,75 +1147,65 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_exp_kernel(const uint32_t* __
       // column in the ops buffer (limb k at word k * 256, every lane the same address)
       fbm_na_mm_glb(aoff, SEG(ops, ops_a) + FBM_OPS_CBC, 0u, NK, np);
       }  // (the unsplit chain)
-    } else {
-#ifndef FBM_EXP_SHORT_ONLY  // (a measurement variant: the launch's code without the table path)
-    if (__any(wide)) {  // wave-uniform: lanes with a narrow h multiply 0 and add nothing
-      lds_store_uniform<2 * NA>(lds, FBM_BLOCK, cst + FBM_CST_QR3);
-      fbm_na_mm_glb(aoff, table, tb0 + FBM_TSCRATCH * tstride, NK, np);  // h_hi*R^2 (wide lanes)
-      lds_to_glb(lds, table + (tb0 + tstride) / 4);
-      uint32_t h[64];
-#ifdef FBM_EXP_FULL_H_LOAD  // (A/B variant: the round-3 whole-row load)
-      load_row64(SEG(H, H_a) + ct * 64, h);
-#else
-      load_h(SEG(H, H_a), SEG(Hc, Hc_a), ct, h);
-#endif
-      uint32_t h29[2 * NA];
-      to29_row64(h, h29);
+    } else {  // the table path
+      if (__any(wide)) {  // wave-uniform: lanes with a narrow h multiply 0 and add nothing
+        lds_store_uniform<2 * NA>(lds, FBM_BLOCK, cst + FBM_CST_QR3);
+        fbm_na_mm_glb(aoff, table, tb0 + FBM_TSCRATCH * tstride, NK, np);  // h_hi*R^2 (wide lanes)
+        lds_to_glb(lds, table + (tb0 + tstride) / 4);
+        uint32_t h[64];
+        load_h(SEG(H, H_a), SEG(Hc, Hc_a), ct, h);
+        uint32_t h29[2 * NA];
+        to29_row64(h, h29);
 #pragma unroll
-      for (int k = NA; k < 2 * NA; ++k) h29[k] = 0u;  // (h_lo, 0)
-      col_store(table + (tb0 + FBM_TSCRATCH * tstride) / 4, h29);
-    }
-    lds_store_uniform<2 * NA>(lds, FBM_BLOCK, cst + FBM_CST_QR2);
-    fbm_na_mm_glb(aoff, table, tb0 + FBM_TSCRATCH * tstride, NK, np);  // h*R (narrow) | h_lo*R (wide)
-    if (__any(wide)) {  // h R = h_lo R + h_hi R^2: digit-wise sum (< 6N + 2, fine as an operand)
-      uint32_t a[2 * NA], b[2 * NA];
-      lds_load_col(lds, FBM_BLOCK, a);
-      col_load(table + (tb0 + tstride) / 4, b);
+        for (int k = NA; k < 2 * NA; ++k) h29[k] = 0u;  // (h_lo, 0)
+        col_store(table + (tb0 + FBM_TSCRATCH * tstride) / 4, h29);
+      }
+      lds_store_uniform<2 * NA>(lds, FBM_BLOCK, cst + FBM_CST_QR2);
+      fbm_na_mm_glb(aoff, table, tb0 + FBM_TSCRATCH * tstride, NK, np);  // h*R (narrow) | h_lo*R (wide)
+      if (__any(wide)) {  // h R = h_lo R + h_hi R^2: digit-wise sum (< 6N + 2, fine as an operand)
+        uint32_t a[2 * NA], b[2 * NA];
+        lds_load_col(lds, FBM_BLOCK, a);
+        col_load(table + (tb0 + tstride) / 4, b);
 #pragma unroll
-      for (int d = 0; d < 2; ++d) {
-        uint32_t c = 0;
+        for (int d = 0; d < 2; ++d) {
+          uint32_t c = 0;
 #pragma unroll
-        for (int k = 0; k < NA; ++k) {
-          const uint32_t v = a[d * NA + k] + (wide ? b[d * NA + k] : 0u) + c;
-          a[d * NA + k] = k + 1 < NA ? v & FBM_QMASK : v;  // the top limb keeps the digit's excess
-          c = v >> FBM_QA_LB;
+          for (int k = 0; k < NA; ++k) {
+            const uint32_t v = a[d * NA + k] + (wide ? b[d * NA + k] : 0u) + c;
+            a[d * NA + k] = k + 1 < NA ? v & FBM_QMASK : v;  // the top limb keeps the digit's excess
+            c = v >> FBM_QA_LB;
+          }
+        }
+        lds_store_col(lds, FBM_BLOCK, a);
+      }
+      if (!SEG(key_is_zero, key_is_zero_a)) {
+        lds_to_glb(lds, table + tb0 / 4);
+        fbm_na_sq_lds_looped(aoff, NK, np);  // h^2*R
+        lds_to_glb(lds, table + (tb0 + FBM_TSCRATCH * tstride) / 4);
+        glb_to_lds(table + tb0 / 4, lds);
+#pragma unroll 1
+        for (int t = 1; t < FBM_TABLE; ++t) {
+          fbm_na_mm_glb(aoff, table, tb0 + FBM_TSCRATCH * tstride, NK, np);
+          lds_to_glb(lds, table + (tb0 + (uint32_t)t * tstride) / 4);
+        }
+        glb_to_lds(table + (tb0 + (uint32_t)SEG(first, first_a) * tstride) / 4, lds);
+        const int n_ops = SEG(n_ops, n_ops_a);
+#pragma unroll 1
+        for (int k = 0; k < n_ops; ++k) {
+          const uint32_t op = __builtin_amdgcn_readfirstlane(SEG(ops, ops_a)[k]);
+          const int nsq = (int)(op >> FBM_OP_SHIFT);
+          const int idx = (int)(op & ((1u << FBM_OP_SHIFT) - 1u)) - 1;
+#pragma unroll 1
+          for (int q = 0; q < nsq; ++q) fbm_na_sq_lds_looped(aoff, NK, np);
+          if (idx >= 0) fbm_na_mm_glb(aoff, table, tb0 + (uint32_t)idx * tstride, NK, np);
         }
       }
-      lds_store_col(lds, FBM_BLOCK, a);
     }
-    if (!SEG(key_is_zero, key_is_zero_a)) {
-      lds_to_glb(lds, table + tb0 / 4);
-      fbm_na_sq_lds_looped(aoff, NK, np);  // h^2*R
-      lds_to_glb(lds, table + (tb0 + FBM_TSCRATCH * tstride) / 4);
-      glb_to_lds(table + tb0 / 4, lds);
-#pragma unroll 1
-      for (int t = 1; t < FBM_TABLE; ++t) {
-        fbm_na_mm_glb(aoff, table, tb0 + FBM_TSCRATCH * tstride, NK, np);
-        lds_to_glb(lds, table + (tb0 + (uint32_t)t * tstride) / 4);
-      }
-      glb_to_lds(table + (tb0 + (uint32_t)SEG(first, first_a) * tstride) / 4, lds);
-      const int n_ops = SEG(n_ops, n_ops_a);
-#pragma unroll 1
-      for (int k = 0; k < n_ops; ++k) {
-        const uint32_t op = __builtin_amdgcn_readfirstlane(SEG(ops, ops_a)[k]);
-        const int nsq = (int)(op >> FBM_OP_SHIFT);
-        const int idx = (int)(op & ((1u << FBM_OP_SHIFT) - 1u)) - 1;
-#pragma unroll 1
-        for (int q = 0; q < nsq; ++q) fbm_na_sq_lds_looped(aoff, NK, np);
-        if (idx >= 0) fbm_na_mm_glb(aoff, table, tb0 + (uint32_t)idx * tstride, NK, np);
-      }
-    }
-#endif
-    }  // (table path)
     const int mode = SEG(mode, mode_a);
     if ((mode & FBM_EXP_DEC) == 0) {  // x nude = (1, pt): jl_nude_kernel's 29-bit blocked column, read in place
       // (a chunk is one 256-ciphertext block: its base is uniform, the lane's offset is tid)
       const uint32_t* nb = SEG(nude, nude_a) + uniform_val((uint64_t)(ct >> 8)) * (FBM_NUDE_ROWS * 256);
-#ifdef FBM_NUDE_BOTH_DIGITS
-      fbm_na_mm_glb(aoff, nb, (uint32_t)(ct & 255) * 4u, NK, np);
-#else
       fbm_na_mm_nude(aoff, nb, (uint32_t)(ct & 255) * 4u, NK, np);
-#endif
     } else {
       fbm_na_mm_glb(aoff, cst + FBM_CST_ONE, 0u, NK, np);
     }

@@ -52,11 +52,21 @@ workgroup-blocked layout of tables and residue columns) or, for the square, from
 column itself.  The constants block (80 words, FBM_CST_NA29 in fbm_internal.hpp) holds
 N_0..N_9 at words 0..9, N_10..N_35 at words 16..41 and K'_0..K'_35 at words 42..77.
 
+The emitters, each written once and shared by every body that needs it:
+  row() / product()               the general product (and the plain square, product(True))
+  sq_row() / square_tri()         the triangular square as a row loop (the table path's square)
+  sq_row_unrolled() / sq_rows()   the unrolled triangular square: per call, in the chain bodies, modulo N
+  short_row()                     the short-base product's row, on the general plan or the square's
+  normalise()                     the window's carry walk, into the LDS column or the B registers
+  load_column(), st()             the lane's LDS column into B registers / a limb back into it
+  chain_flow()                    the exponent-bit control flow of chain_short / chain_modn / chain_seg
+
 Usage:  python tools/gen_nadic_asm.py   (rewrites the header and, beside it, fbm_nadic_chain_asm.hpp: the
         short path's register-resident chain body, chain_short below, and the split exponentiation's two
         bodies, chain_modn and chain_seg; the build does not run this)
 """
 
+import collections
 import os
 
 LB = 29     # bits per limb
@@ -79,20 +89,12 @@ def AtLo(k):
     return f"v{2 * k}"
 
 
-def AtHi(k):
-    return f"v{2 * k + 1}"
-
-
 def As(k):
     return f"v[{AS0 + 2 * k}:{AS0 + 2 * k + 1}]"
 
 
 def AsLo(k):
     return f"v{AS0 + 2 * k}"
-
-
-def AsHi(k):
-    return f"v{AS0 + 2 * k + 1}"
 
 
 def B0(j):
@@ -114,6 +116,13 @@ TT, TTLO, TS, TSLO = f"v[{_X + 4}:{_X + 5}]", f"v{_X + 4}", f"v[{_X + 6}:{_X + 7
 Q, Q2, NPV, AADR, TMP, CQ = (f"v{_X + 8 + i}" for i in range(6))
 MM_NREG = _X + 14
 ROW1 = L * 1024  # byte offset of digit 1 in the LDS column
+
+# What the short product's row, the window normalise and the column load name of a register plan: the
+# window pairs of both parts, the B digits, the retiring columns, the quotients, np and a scratch
+# register.  MMP is the plan above; SQP (below) the triangular square's, which the chain bodies run
+# both of their products on.
+Plan = collections.namedtuple("Plan", "At AtLo As AsLo B0 B1 TT TTLO TS TSLO Q Q2 NPV TMP")
+MMP = Plan(At, AtLo, As, AsLo, B0, B1, TT, TTLO, TS, TSLO, Q, Q2, NPV, TMP)
 
 
 def load_consts():
@@ -153,16 +162,20 @@ def load_b_nude():
     return out
 
 
-def load_b_square():
-    out = [f"v_add_u32 {TMP}, 0x10000, %[a]"]
+def load_column(p, hi=None):
+    """The lane's LDS column (72 limbs at %[a], stride 1024 B) into plan p's B registers.  A DS offset
+    is 16 bits: limbs 64..71 go through `hi` (default p.TMP) = %[a] + 0x10000."""
+    hi = hi or p.TMP
+    out = [f"v_add_u32 {hi}, 0x10000, %[a]"]
     for j in range(2 * L):
-        if j < 64:
-            out.append(f"ds_read_b32 {breg(j)}, %[a] offset:{j * 1024}")
-        else:
-            out.append(f"ds_read_b32 {breg(j)}, {TMP} offset:{(j - 64) * 1024}")
-    out.append("s_waitcnt lgkmcnt(0)")
-    out += [f"v_lshlrev_b32 {B1(j)}, 1, {B1(j)}" for j in range(L)]
+        reg = p.B0(j) if j < L else p.B1(j - L)
+        out.append(f"ds_read_b32 {reg}, %[a] offset:{j * 1024}" if j < 64 else
+                   f"ds_read_b32 {reg}, {hi} offset:{(j - 64) * 1024}")
     return out
+
+
+def load_b_square():
+    return load_column(MMP) + ["s_waitcnt lgkmcnt(0)"] + [f"v_lshlrev_b32 {B1(j)}, 1, {B1(j)}" for j in range(L)]
 
 
 def row(first, sq):
@@ -246,23 +259,45 @@ def mid_reduce(pairs, keep=None, one=None):
     return out
 
 
-def normalise_store():
-    out = [f"v_add_u32 {TMP}, 0x10000, %[a]"]
+def st(p, k, reg):
+    """Limb k of the lane's LDS column <- reg (limbs 64..71 through p.TMP = %[a] + 0x10000)."""
+    if k < 64:
+        return f"ds_write_b32 %[a], {reg} offset:{k * 1024}"
+    return f"ds_write_b32 {p.TMP}, {reg} offset:{(k - 64) * 1024}"
 
-    def st(k, reg):
-        if k < 64:
-            return f"ds_write_b32 %[a], {reg} offset:{k * 1024}"
-        return f"ds_write_b32 {TMP}, {reg} offset:{(k - 64) * 1024}"
 
-    for acc, lo, carry, carry_lo, base in ((At, AtLo, TT, TTLO, 0), (As, AsLo, TS, TSLO, L)):
-        out += [f"v_lshrrev_b64 {carry}, {LB}, {acc(0)}", f"v_and_b32 {lo(0)}, {MASK}, {lo(0)}", st(base, lo(0))]
-        for k in range(1, NW):
-            out += [f"v_lshl_add_u64 {acc(k)}, {carry}, 0, {acc(k)}",
-                    f"v_lshrrev_b64 {carry}, {LB}, {acc(k)}",
-                    f"v_and_b32 {lo(k)}, {MASK}, {lo(k)}",
-                    st(base + k, lo(k))]
-        out.append(st(base + NW, carry_lo))
-    out.append("s_waitcnt lgkmcnt(0)")
+def normalise(p, halves="ts", to_regs=False, prefetch=False):
+    """The window of plan p after the last row -> 36 limbs of 29 bits per digit: one carry walk per half
+    (`halves`: "ts", or "t" for the modulo-N bodies, whose digit 1 is zero).  The limbs go
+      to_regs=False: into the lane's LDS column (masked in place, stored; the t half carries in TT, the s half
+        in TS), then a wait for the stores;
+      to_regs=True: straight into the B registers the next product reads (the chain bodies: v_and_b32
+        B(k), MASK, lo; both halves carry in TT, TS is free) and, with `prefetch`, the next product's
+        initial s pair j is read from PADR + 8 j into the pair the s walk has just released."""
+    out = [] if to_regs else [f"v_add_u32 {p.TMP}, 0x10000, %[a]"]
+    for half in halves:
+        acc, lo, b, carry, carry_lo, base = ((p.At, p.AtLo, p.B0, p.TT, p.TTLO, 0) if half == "t" else
+                                             (p.As, p.AsLo, p.B1, p.TS, p.TSLO, L))
+        if to_regs:
+            carry, carry_lo = p.TT, p.TTLO
+        pf = prefetch and half == "s"
+        if pf:
+            out.append(pair_read(0))
+        for k in range(NW):
+            if k:
+                out.append(f"v_lshl_add_u64 {acc(k)}, {carry}, 0, {acc(k)}")
+            out.append(f"v_lshrrev_b64 {carry}, {LB}, {acc(k)}")
+            if to_regs:
+                out.append(f"v_and_b32 {b(k)}, {MASK}, {lo(k)}")
+            else:
+                out += [f"v_and_b32 {lo(k)}, {MASK}, {lo(k)}", st(p, base + k, lo(k))]
+            if pf:
+                out.append(pair_read(k + 1))
+        out.append(f"v_mov_b32 {b(NW)}, {carry_lo}" if to_regs else st(p, base + NW, carry_lo))
+    if not to_regs:
+        if halves == "t":
+            out += [f"v_mov_b32 {p.TSLO}, 0"] + [st(p, L + k, p.TSLO) for k in range(L)]
+        out.append("s_waitcnt lgkmcnt(0)")
     return out
 
 
@@ -297,7 +332,7 @@ def product(sq, nude=False):
     body += [f"s_cmp_lg_u32 s34, {MID - 1}", "s_cbranch_scc1 2f"]
     body += mid_reduce([[AtLo(k) for k in range(NW)], [AsLo(k) for k in range(NW)]]) + ["2:"]
     body += ["s_add_u32 s34, s34, 1", f"s_cmp_lg_u32 s34, {L}", "s_cbranch_scc1 1b"]
-    body += normalise_store()
+    body += normalise(MMP)
     body += [f"s_mov_b32 m0, {M0_SAVE}", "s_nop 1"]  # m0 read right after the asm: wait state
     return rotate_carries(body)
 
@@ -356,6 +391,7 @@ _ST = _SX + 3 + (_SX + 3) % 2  # 64-bit pairs start on an even VGPR
 STT, STTLO, STS, STSLO = f"v[{_ST}:{_ST + 1}]", f"v{_ST}", f"v[{_ST + 2}:{_ST + 3}]", f"v{_ST + 2}"
 SQ, SQ2, SNPV, SAADR, STMP, SCQ, SDI, SDADDR = (f"v{_ST + 4 + i}" for i in range(8))
 SQ_NREG = _ST + 12
+SQP = Plan(SAt, SAtLo, SAs, SAsLo, SB0, SB1, STT, STTLO, STS, STSLO, SQ, SQ2, SNPV, STMP)
 
 
 def sq_tri(tag, first=False):
@@ -429,15 +465,14 @@ def krow(row_expr):
     return row_expr + ["s_nop 1", f"s_movrels_b32 s35, {KBASE}"]
 
 
+def sq_top_diagonals():
+    """After the last row: the diagonals x0_h^2 of columns L .. 2L-2 (h >= L/2), from the B registers;
+    column 2h sits at window position 2h - L."""
+    return [f"v_mad_u64_u32 {SAt(2 * h - L)}, vcc, {SB0(h)}, {SB0(h)}, {SAt(2 * h - L)}" for h in range(L // 2, L)]
+
+
 def square_tri():
-    body = [f"s_mov_b32 {M0_SAVE}, m0"] + load_consts()
-    body.append(f"v_add_u32 {STMP}, 0x10000, %[a]")
-    for j in range(2 * L):
-        reg = SB0(j) if j < L else SB1(j - L)
-        if j < 64:
-            body.append(f"ds_read_b32 {reg}, %[a] offset:{j * 1024}")
-        else:
-            body.append(f"ds_read_b32 {reg}, {STMP} offset:{(j - 64) * 1024}")
+    body = [f"s_mov_b32 {M0_SAVE}, m0"] + load_consts() + load_column(SQP)
     body += [f"v_mov_b32 {SNPV}, %[np]", f"v_mov_b32 {SAADR}, %[a]", f"ds_read_b32 {SX0}, %[a]",
              f"ds_read_b32 {SDI}, %[a]", f"v_mov_b32 {SDADDR}, %[a]", "s_waitcnt lgkmcnt(0)",
              f"v_lshlrev_b32 {SX0D}, 1, {SX0}"]
@@ -452,24 +487,7 @@ def square_tri():
     body += krow(["s_add_u32 m0, s34, 1"]) + sq_row("even")
     body += ["s_add_u32 s34, s34, 2", f"s_cmp_lg_u32 s34, {L - 1}", "s_cbranch_scc1 1b"]
     body += krow([f"s_mov_b32 m0, {L - 1}"]) + sq_row("last")
-    # diagonals of columns L .. 2L-2 (h >= L/2): column 2h sits at window position 2h - L
-    body += [f"v_mad_u64_u32 {SAt(2 * h - L)}, vcc, {SB0(h)}, {SB0(h)}, {SAt(2 * h - L)}" for h in range(L // 2, L)]
-    body.append(f"v_add_u32 {STMP}, 0x10000, %[a]")
-
-    def st(k, reg):
-        if k < 64:
-            return f"ds_write_b32 %[a], {reg} offset:{k * 1024}"
-        return f"ds_write_b32 {STMP}, {reg} offset:{(k - 64) * 1024}"
-
-    for acc, lo, carry, carry_lo, base in ((SAt, SAtLo, STT, STTLO, 0), (SAs, SAsLo, STS, STSLO, L)):
-        body += [f"v_lshrrev_b64 {carry}, {LB}, {acc(0)}", f"v_and_b32 {lo(0)}, {MASK}, {lo(0)}", st(base, lo(0))]
-        for k in range(1, NW):
-            body += [f"v_lshl_add_u64 {acc(k)}, {carry}, 0, {acc(k)}",
-                     f"v_lshrrev_b64 {carry}, {LB}, {acc(k)}",
-                     f"v_and_b32 {lo(k)}, {MASK}, {lo(k)}",
-                     st(base + k, lo(k))]
-        body.append(st(base + NW, carry_lo))
-    body += ["s_waitcnt lgkmcnt(0)", f"s_mov_b32 m0, {M0_SAVE}", "s_nop 1"]
+    body += sq_top_diagonals() + normalise(SQP) + [f"s_mov_b32 m0, {M0_SAVE}", "s_nop 1"]
     return rotate_carries(body)
 
 
@@ -481,125 +499,73 @@ def square_tri():
 #     X h 2^-(29 KS)  (mod N^2)  =  t + N s,
 #     t = (x0 h + m N) / 2^(29 KS)                        (m = sum q_i 2^(29 i), i < KS)
 #     s = (x1 h + (2^(29 KS) - m) + D + m' N) / 2^(29 KS),   D = N - 2^(29 KS)
-# -- 2^(29 KS) - m is the rows' retiring-column adds (2^29 - 1 - q_i, + 1 in row 0), D enters as
-# the s window's initial value (row 0's addends: pairs (D_j, 0) read from LDS), so the s
-# numerator is x1 h - m + N (= x1 h - m mod N, and >= 0: m < 2^(29 KS) < N).  KS (36 + 36 +
-# 36 + 36 + 1) = 1 305 multiplies against 6 584 for a general product, and no table.  Bounds
-# (N > 2^(29 KS)): digits < 2N in -> t < 3N, s < 3N + 2 (the next squaring brings them back
+# -- 2^(29 KS) - m is the rows' retiring-column adds (2^29 - 1 - q_i, + 1 in row 0), folded like
+# the unrolled square's K': the s window starts at the pairs (D'_j, 0) read from LDS (row 0's
+# addends), D'_j = D_j + (2^29 - 1) [j < KS] + [j == 0] -- a non-normalised N (D + 2^261) -- and row
+# i subtracts q_i from its retiring column with one v_mad_i64_i32 (the column holds D'_i >= 2^29 - 1
+# >= q_i), so the s numerator is x1 h - m + N (= x1 h - m mod N, and >= 0: m < 2^(29 KS) < N).
+# KS (36 + 36 + 36 + 36 + 1) = 1 305 multiplies against 6 584 for a general product, and no table.
+# Bounds (N > 2^(29 KS)): digits < 2N in -> t < 3N, s < 3N + 2 (the next squaring brings them back
 # below 2N); a column gathers at most KS rows of 2 products < 2^58: < 2^62.2, no mid-product
 # reduction.  The factor 2^-(29 KS) per multiply (and R^-1 per squaring) is a constant of the
 # exponent, cancelled by one product with a host-built constant after the chain.
-# Register plan: the general product's, with h's limbs in v226..v234 and (D_35, 0) in v[214:215]
-# (the row-operand prefetch registers, unused here); the multiplier needs no LDS rows.
+# h's KS limbs are asm inputs (%[h0] .. %[h8], registers the kernel holds for the whole chain) and the
+# rows are unrolled.  short_row() is the row on either register plan: mul_short_reg() runs it on the
+# general product's, with pair j in As_j and (D'_35, 0) in v[214:215] (the row-operand prefetch
+# registers, unused here); the chain bodies run it on the square's (short_rows() below).
 # ------------------------------------------------------------------------------------------
 KS = 9
-SHORT_LOOPED = True   # rows 1..8 as a loop (3 KB of code instead of 14 KB: the unrolled square is 43 KB)
-HS = [f"v{MM_NREG + i}" for i in range(KS)]
 D35 = f"v[{_X + 2}:{_X + 3}]"
-HADDR = X1  # (looped rows) the address of the next row's limb of h
-MS_NREG = MM_NREG if SHORT_LOOPED else MM_NREG + KS
 
 
-def short_row(i, x=None):
-    """Row i of the short product: multiplier limb h_i (HS[i], or the register x), t then s part,
-    both retires (rows >= 1 are the same instruction stream whatever i: the loop body)."""
-    x, first = (x or HS[i]), i == 0
-    out = [f"v_mad_u64_u32 {TT}, vcc, {x}, {B0(0)}, {'0' if first else At(0)}"]
+def short_row(p, i, x, pairs, halves="ts", waits=False):
+    """Row i of the short product on plan p: multiplier limb x = h_i, the t part and (halves "ts") the s
+    part, then the retires.  Row 0 starts both windows: the t addends are 0 and the s multiply j adds
+    pairs[j], the initial pair of the column that starts there -- waited for by count when `waits`
+    (chain_wait: the pairs were prefetched in order).  Rows >= 1 are one instruction stream whatever i."""
+    first = i == 0
+    out = [f"v_mad_u64_u32 {p.TT}, vcc, {x}, {p.B0(0)}, {'0' if first else p.At(0)}"]
     for j in range(1, L):
-        addend = "0" if (first or j == NW) else At(j)
-        out.append(f"v_mad_u64_u32 {At(j - 1)}, vcc, {x}, {B0(j)}, {addend}")
+        addend = "0" if (first or j == NW) else p.At(j)
+        out.append(f"v_mad_u64_u32 {p.At(j - 1)}, vcc, {x}, {p.B0(j)}, {addend}")
         if j == 3:
-            out.append(f"v_mul_lo_u32 {Q}, {TTLO}, {NPV}")
+            out.append(f"v_mul_lo_u32 {p.Q}, {p.TTLO}, {p.NPV}")
         if j == 6:
-            out.append(f"v_and_b32 {Q}, {MASK}, {Q}")
-        if j == 8 and not SHORT_KFOLD:  # 2^29 - 1 - q_i (+ 1 in row 0: the sum over the rows is 2^(29 KS) - m)
-            out.append(f"v_sub_u32 {CQ}, {hex(1 << LB) if first else MASK}, {Q}")
-    out.append(f"v_mad_u64_u32 {TT}, vcc, {Q}, {Ns(0)}, {TT}")
+            out.append(f"v_and_b32 {p.Q}, {MASK}, {p.Q}")
+    out.append(f"v_mad_u64_u32 {p.TT}, vcc, {p.Q}, {Ns(0)}, {p.TT}")
     for j in range(1, L):
-        out.append(f"v_mad_u64_u32 {At(j - 1)}, vcc, {Q}, {Ns(j)}, {At(j - 1)}")
-    # s part: the window's addends (row 0: D, loaded into it; the top slot's D_35 from D35)
-    out.append(f"v_mad_u64_u32 {TS}, vcc, {x}, {B1(0)}, {As(0)}")
-    for j in range(1, L):
-        addend = (D35 if first else "0") if j == NW else As(j)
-        out.append(f"v_mad_u64_u32 {As(j - 1)}, vcc, {x}, {B1(j)}, {addend}")
-        if j == 12:
-            out.append(f"v_mad_i64_i32 {TS}, vcc, {Q}, -1, {TS}" if SHORT_KFOLD else
-                       f"v_mad_u64_u32 {TS}, vcc, {CQ}, 1, {TS}")
-        if j == 20:
-            out.append(f"v_mul_lo_u32 {Q2}, {TSLO}, {NPV}")
-        if j == 26:
-            out.append(f"v_and_b32 {Q2}, {MASK}, {Q2}")
-    out.append(f"v_mad_u64_u32 {TS}, vcc, {Q2}, {Ns(0)}, {TS}")
-    for j in range(1, L):
-        out.append(f"v_mad_u64_u32 {As(j - 1)}, vcc, {Q2}, {Ns(j)}, {As(j - 1)}")
-    out += [f"v_lshrrev_b64 {TT}, {LB}, {TT}", f"v_lshl_add_u64 {At(0)}, {TT}, 0, {At(0)}",
-            f"v_lshrrev_b64 {TS}, {LB}, {TS}", f"v_lshl_add_u64 {As(0)}, {TS}, 0, {As(0)}"]
+        out.append(f"v_mad_u64_u32 {p.At(j - 1)}, vcc, {p.Q}, {Ns(j)}, {p.At(j - 1)}")
+    if "s" in halves:
+        for j in range(L):
+            if first:
+                addend = pairs[j]
+                out += chain_wait(j) if waits else []
+            else:
+                addend = "0" if j == NW else p.As(j)
+            out.append(f"v_mad_u64_u32 {p.As(j - 1) if j else p.TS}, vcc, {x}, {p.B1(j)}, {addend}")
+            if j == 12:  # - q_i, from the retiring column
+                out.append(f"v_mad_i64_i32 {p.TS}, vcc, {p.Q}, -1, {p.TS}")
+            if j == 20:
+                out.append(f"v_mul_lo_u32 {p.Q2}, {p.TSLO}, {p.NPV}")
+            if j == 26:
+                out.append(f"v_and_b32 {p.Q2}, {MASK}, {p.Q2}")
+        out.append(f"v_mad_u64_u32 {p.TS}, vcc, {p.Q2}, {Ns(0)}, {p.TS}")
+        for j in range(1, L):
+            out.append(f"v_mad_u64_u32 {p.As(j - 1)}, vcc, {p.Q2}, {Ns(j)}, {p.As(j - 1)}")
+    out += [f"v_lshrrev_b64 {p.TT}, {LB}, {p.TT}", f"v_lshl_add_u64 {p.At(0)}, {p.TT}, 0, {p.At(0)}"]
+    if "s" in halves:
+        out += [f"v_lshrrev_b64 {p.TS}, {LB}, {p.TS}", f"v_lshl_add_u64 {p.As(0)}, {p.TS}, 0, {p.As(0)}"]
     return out
 
 
-# Round 4: the short product with h's KS limbs in registers (asm inputs %[h0] .. %[h8], held by the
-# kernel for the whole chain: no global reads of h per product) and its rows unrolled; the rows'
-# 2^29 - 1 - q_i folded like the square's K': the s window starts at the pairs (D'_j, 0),
-# D'_j = D_j + (2^29 - 1) [j < KS] + [j == 0] -- a non-normalised N (D + 2^261) -- and each row
-# subtracts q_i with one v_mad_i64_i32 (column i >= 2^29 - 1 >= q_i).
-SHORT_KFOLD = True
-
-
 def mul_short_reg():
-    body = list(load_consts())
-    body.append(f"v_add_u32 {AADR}, 0x10000, %[a]")
-    for j in range(2 * L):
-        if j < 64:
-            body.append(f"ds_read_b32 {breg(j)}, %[a] offset:{j * 1024}")
-        else:
-            body.append(f"ds_read_b32 {breg(j)}, {AADR} offset:{(j - 64) * 1024}")
+    body = load_consts() + load_column(MMP, hi=AADR)
     body += [f"ds_read_b64 {As(j)}, %[d] offset:{8 * j}" for j in range(NW)]
     body += [f"ds_read_b64 {D35}, %[d] offset:{8 * NW}", f"v_mov_b32 {NPV}, %[np]", "s_waitcnt lgkmcnt(0)"]
+    pairs = [As(j) for j in range(NW)] + [D35]
     for i in range(KS):
-        body += short_row(i, f"%[h{i}]")
-    body += normalise_store()
-    return rotate_carries(body)
-
-
-def mul_short():
-    body = list(load_consts())
-    # h's KS limbs: global, workgroup-blocked (limb k at hb + h_off + k * 1024)
-    body += ["s_waitcnt vmcnt(0)", f"v_mov_b32 {TMP}, %[h]"]
-    if SHORT_LOOPED:  # limb 0 now, each next one prefetched a row ahead (HADDR = its address)
-        body += [f"global_load_dword {X0}, {TMP}, %[hb]", f"v_add_u32 {HADDR}, 0x400, {TMP}"]
-    else:
-        for k in range(KS):
-            if k and k % 4 == 0:
-                body.append(f"v_add_u32 {TMP}, 0x1000, {TMP}")
-            body.append(f"global_load_dword {HS[k]}, {TMP}, %[hb] offset:{(k % 4) * 1024}")
-    # B = X from the lane's column (undoubled); the s window <- (D_j, 0), D35 <- (D_35, 0)
-    body.append(f"v_add_u32 {AADR}, 0x10000, %[a]")
-    for j in range(2 * L):
-        if j < 64:
-            body.append(f"ds_read_b32 {breg(j)}, %[a] offset:{j * 1024}")
-        else:
-            body.append(f"ds_read_b32 {breg(j)}, {AADR} offset:{(j - 64) * 1024}")
-    body += [f"ds_read_b64 {As(j)}, %[d] offset:{8 * j}" for j in range(NW)]
-    body += [f"ds_read_b64 {D35}, %[d] offset:{8 * NW}", f"v_mov_b32 {NPV}, %[np]",
-             "s_waitcnt vmcnt(0) lgkmcnt(0)"]
-    if SHORT_LOOPED:  # row 0 peeled, rows 1 .. KS-1 a runtime loop over row pairs (operands X0N / X0)
-        assert (KS - 1) % 2 == 0
-
-        def pref(dst):  # the next row's limb of h, a row ahead
-            return [f"global_load_dword {dst}, {HADDR}, %[hb]", f"v_add_u32 {HADDR}, 0x400, {HADDR}"]
-
-        xb = AADR  # the second operand register (AADR is free once the prologue's loads are in; X0N
-        #            holds D_35 until row 0's last s product)
-        body += pref(xb) + short_row(0, X0) + ["s_waitcnt vmcnt(0)"]
-        body += ["s_mov_b32 s34, 0", "3:"]
-        body += pref(X0) + short_row(1, xb) + ["s_waitcnt vmcnt(0)"]
-        body += pref(xb) + short_row(1, X0) + ["s_waitcnt vmcnt(0)"]
-        body += ["s_add_u32 s34, s34, 1", f"s_cmp_lg_u32 s34, {(KS - 1) // 2}", "s_cbranch_scc1 3b"]
-    else:
-        for i in range(KS):
-            body += short_row(i)
-    body += normalise_store()
-    return rotate_carries(body)
+        body += short_row(MMP, i, f"%[h{i}]", pairs)
+    return rotate_carries(body + normalise(MMP))
 
 
 def ms_mads():
@@ -607,149 +573,159 @@ def ms_mads():
 
 
 # ------------------------------------------------------------------------------------------
-# The triangular square with every row unrolled (round 3): the same arithmetic, registers and
-# instruction order per row as square_tri, but with the row index static -- the cross products
-# k = i + 1 .. 35 emitted directly (no computed jump, s_setpc's instruction-buffer refetch), K'_i
-# read from s(62 + i) (no m0 / s_movrels), the diagonal x_(i/2)^2 of an even row from the B
-# register that holds x_(i/2) (no LDS read, no address add), the row operands read at static
-# offsets from the column base (no address add).  4 273 instructions (~35 KB) instead of a loop;
-# bit-identical results (tests/test_nadic_asm.py runs both).
+# The triangular square with every row unrolled: the same arithmetic, registers and order of
+# multiplies per row as square_tri, but with the row index static -- the cross products
+# k = i + 1 .. 35 emitted directly (no computed jump, s_setpc's instruction-buffer refetch), the
+# diagonal x_(i/2)^2 of an even row from the B register that holds x_(i/2) (no LDS read, no
+# address add), the row operands read at static offsets from the column base (no address add).
+# 4 273 instructions (~35 KB) instead of a loop; bit-identical results (tests/test_nadic_asm.py
+# runs both).  Two things differ from the looped square's arithmetic:
+# (1) K' is folded -- the s window starts at the pairs (K'_j, 0) (read from LDS, pair j into the pair
+# column j starts in: STS, SAs_0 .. SAs_34) and each row subtracts its quotient digit with one
+# v_mad_i64_i32 (q * -1 + column; the column holds K'_i >= 2^29 - 1 >= q, so it stays non-negative)
+# instead of v_sub (K'_i - q) + v_mad_u64_u32 (+ 1 x (K'_i - q)): one VALU instruction less per row, and
+# no m0 / s_movrels;
+# (2) the mid-product reduction runs only on the slots whose columns could otherwise pass 2^64
+# (tests/asm_bounds.py proves the rest stay below it for every operand within the product's input
+# bounds: 6 t slots and 28 s slots of 34 + 34).
+# sq_row_unrolled() is the row, sq_rows() the 36 of them; square_unrolled() is the per-call product
+# around them (column in, column out), the chain bodies further below keep X in the B registers.
 # ------------------------------------------------------------------------------------------
-UNROLLED_SQUARE = True
-# Round 4: (1) K' folded -- the s window starts at the pairs (K'_j, 0) (LDS, %[k]) and each row
-# subtracts its quotient digit with one v_mad_i64_i32 (q * -1 + column; the column holds K'_i >= 2^29 - 1
-# >= q, so it stays non-negative) instead of v_sub (K'_i - q) + v_mad_u64_u32 (+ 1 x (K'_i - q)): one VALU
-# instruction less per row; (2) the mid-product reduction only on the slots whose columns could
-# otherwise pass 2^64 (tests/asm_bounds.py proves the rest stay below it for every operand within the
-# product's input bounds: 6 t slots and 28 s slots of 34 + 34).
-SQ_KFOLD = True
-SQ_MID_KEEP = (set(range(14, 20)), set(range(3, 31)))  # (t slots, s slots); None: every slot
+SQ_MID_KEEP = (set(range(14, 20)), set(range(3, 31)))  # (t slots, s slots); read at call time
 SQ_MID_T = SQ_MID_S = MID  # the reduction follows row SQ_MID_{T,S} - 1 (t part, s part)
 
 
 def sq_one_slots():
     """The s slots the mid-product reduction leaves at 2^32 + low dword (mid_reduce's `one`): those
     reduced whose column (SQ_MID_S + slot) still has a quotient digit to lose (column <= L - 1)."""
-    keep = range(NW - 1) if SQ_MID_KEEP is None else SQ_MID_KEEP[1]
-    return {k for k in keep if SQ_MID_S + k <= L - 1}
+    return {k for k in SQ_MID_KEEP[1] if SQ_MID_S + k <= L - 1}
 
 
 def sq_kfold_extra():
     """E: what the reduction's high dwords of 1 add to the square's s numerator, sum over those slots
     of 2^(32 + 29 column).  The host's initial pairs are (2^29 - 1 + P'_j, 0) with P' = (K - E) mod N, so
     that the constant added in all is R - 1 + P' + E == 0 (mod N) (K = (1 - R) mod N)."""
-    return sum(1 << (32 + LB * (SQ_MID_S + k)) for k in sq_one_slots()) if SQ_KFOLD else 0
+    return sum(1 << (32 + LB * (SQ_MID_S + k)) for k in sq_one_slots())
 
 
-def sq_row_static(i):
-    first, last, even = i == 0, i == L - 1, i % 2 == 0
-    kreg = f"s{62 + i}"  # K'_i (KBASE + i)
-    out = [] if last else [f"ds_read_b32 {SX0N}, %[a] offset:{(i + 1) * 1024}"]
+def pair_dst(j):
+    """Where the initial s pair j of a product on the square's plan goes: the pair column j starts in."""
+    return STS if j == 0 else SAs(j - 1)
+
+
+def sq_row_unrolled(i, halves="ts", next_from_lds=False, waits=False):
+    """Row i of the unrolled triangular square: the t part and (halves "ts") the s part.  On entry SX0D =
+    2 x0_i; the next row's comes from SX0N, read from the lane's LDS column here and waited for at the
+    row's end (`next_from_lds`: the per-call square), or from SB0(i + 1) (the chain bodies, whose
+    normalise left X there).  `waits`: row 0's s multiply j waits by count for the prefetched pair j
+    (chain_wait).  The modulo-N bodies' row ("t") is the same instructions without the s part's, the
+    quotient's mask then following the second cross product."""
+    first, last, even, s = i == 0, i == L - 1, i % 2 == 0, "s" in halves
+    out = [f"ds_read_b32 {SX0N}, %[a] offset:{(i + 1) * 1024}"] if next_from_lds and not last else []
     if even:  # the diagonal x0_(i/2)^2 of column i completes it
         out.append(f"v_mad_u64_u32 {SAt(0)}, vcc, {SB0(i // 2)}, {SB0(i // 2)}, {'0' if first else SAt(0)}")
     out.append(f"v_mul_lo_u32 {SQ}, {SAtLo(0)}, {SNPV}")
-    # ---- s part: (2 x0_i) * x1, - q (K'_i pre-added to column i: SQ_KFOLD) or + (K'_i - q), q' ----
-    s0 = (STS if SQ_KFOLD else "0") if first else SAs(0)
-    out.append(f"v_mad_u64_u32 {STS}, vcc, {SX0D}, {SB1(0)}, {s0}")
-    for j in range(1, L):
-        if first:
-            addend = SAs(j - 1) if SQ_KFOLD else "0"
-        else:
-            addend = "0" if j == NW else SAs(j)
-        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {SX0D}, {SB1(j)}, {addend}")
-        if j == 2:
-            out.append(f"v_and_b32 {SQ}, {MASK}, {SQ}")
-        if j == 4 and not SQ_KFOLD:
-            out.append(f"v_sub_u32 {SCQ}, {kreg}, {SQ}")
-        if j == 12:
-            out.append(f"v_mad_i64_i32 {STS}, vcc, {SQ}, -1, {STS}" if SQ_KFOLD else
-                       f"v_mad_u64_u32 {STS}, vcc, {SCQ}, 1, {STS}")
-        if j == 20:
-            out.append(f"v_mul_lo_u32 {SQ2}, {STSLO}, {SNPV}")
-        if j == 26:
-            out.append(f"v_and_b32 {SQ2}, {MASK}, {SQ2}")
+    mask_q = f"v_and_b32 {SQ}, {MASK}, {SQ}"
     # ---- t part: doubled cross products 2 x0_i x0_k, k > i (the top position written fresh) ----
-    for k in range(i + 1, L):
-        addend = "0" if (first or k == L - 1) else SAt(k)
-        out.append(f"v_mad_u64_u32 {SAt(k)}, vcc, {SX0D}, {SB0(k)}, {addend}")
+    cross = [f"v_mad_u64_u32 {SAt(k)}, vcc, {SX0D}, {SB0(k)}, {'0' if (first or k == L - 1) else SAt(k)}"
+             for k in range(i + 1, L)]
+    if s:  # ---- s part first: (2 x0_i) * x1, - q (K'_i sits in column i), q' ----
+        for j in range(L):
+            if first:
+                addend = pair_dst(j)
+                out += chain_wait(j) if waits else []
+            else:
+                addend = "0" if j == NW else SAs(j)
+            out.append(f"v_mad_u64_u32 {pair_dst(j)}, vcc, {SX0D}, {SB1(j)}, {addend}")
+            if j == 2:
+                out.append(mask_q)
+            if j == 12:
+                out.append(f"v_mad_i64_i32 {STS}, vcc, {SQ}, -1, {STS}")
+            if j == 20:
+                out.append(f"v_mul_lo_u32 {SQ2}, {STSLO}, {SNPV}")
+            if j == 26:
+                out.append(f"v_and_b32 {SQ2}, {MASK}, {SQ2}")
+        out += cross
+    else:
+        out += cross[:2] + [mask_q] + cross[2:]
     # ---- t: q * N (shifting the window);  s: q' * N ----
     top = "0" if last else SAt(L - 1)
     out.append(f"v_mad_u64_u32 {STT}, vcc, {SQ}, {Ns(0)}, {SAt(0)}")
     for k in range(1, L):
         out.append(f"v_mad_u64_u32 {SAt(k - 1)}, vcc, {SQ}, {Ns(k)}, {SAt(k) if k < L - 1 else top}")
-    out.append(f"v_mad_u64_u32 {STS}, vcc, {SQ2}, {Ns(0)}, {STS}")
-    for j in range(1, L):
-        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {SQ2}, {Ns(j)}, {SAs(j - 1)}")
-    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}",
-            f"v_lshrrev_b64 {STS}, {LB}, {STS}", f"v_lshl_add_u64 {SAs(0)}, {STS}, 0, {SAs(0)}"]
+    if s:
+        out.append(f"v_mad_u64_u32 {STS}, vcc, {SQ2}, {Ns(0)}, {STS}")
+        for j in range(1, L):
+            out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {SQ2}, {Ns(j)}, {SAs(j - 1)}")
+    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}"]
+    if s:
+        out += [f"v_lshrrev_b64 {STS}, {LB}, {STS}", f"v_lshl_add_u64 {SAs(0)}, {STS}, 0, {SAs(0)}"]
     if not last:
-        out += ["s_waitcnt lgkmcnt(0)", f"v_lshlrev_b32 {SX0D}, 1, {SX0N}"]
+        out += (["s_waitcnt lgkmcnt(0)", f"v_lshlrev_b32 {SX0D}, 1, {SX0N}"] if next_from_lds else
+                [f"v_lshlrev_b32 {SX0D}, 1, {SB0(i + 1)}"])
     return out
 
 
-def square_unrolled():
-    body = list(load_consts())
-    body.append(f"v_add_u32 {STMP}, 0x10000, %[a]")
-    for j in range(2 * L):
-        reg = SB0(j) if j < L else SB1(j - L)
-        if j < 64:
-            body.append(f"ds_read_b32 {reg}, %[a] offset:{j * 1024}")
-        else:
-            body.append(f"ds_read_b32 {reg}, {STMP} offset:{(j - 64) * 1024}")
-    if SQ_KFOLD:  # the s window starts at the pairs (K'_j, 0): column j's K'_j, added once
-        body += [f"ds_read_b64 {STS}, %[k]"] + [f"ds_read_b64 {SAs(j - 1)}, %[k] offset:{8 * j}" for j in range(1, L)]
-    body += [f"v_mov_b32 {SNPV}, %[np]", f"ds_read_b32 {SX0}, %[a]", "s_waitcnt lgkmcnt(0)",
-             f"v_lshlrev_b32 {SX0D}, 1, {SX0}"]
+def sq_rows(halves="ts", resident=False):
+    """The unrolled square's 36 rows with the mid-product reduction (the t part after row SQ_MID_T - 1, the
+    s part after row SQ_MID_S - 1, interleaved when both fall after the same row, each on its SQ_MID_KEEP
+    slots) and the top diagonals: X in the B registers (the s pairs in place) -> window.  `resident`: a
+    chain body's square -- the row operands from SB0, row 0's pairs prefetched; else SX0 = x0_0 and the
+    next rows' come from the LDS column."""
+    body = [f"v_lshlrev_b32 {SX0D}, 1, {SB0(0) if resident else SX0}"]
     for i in range(L):
-        body += sq_row_static(i)
-        # the mid-product reduction: the t part after row SQ_MID_T - 1, the s part after row SQ_MID_S - 1
-        # (interleaved when both fall after the same row), each on its SQ_MID_KEEP slots
-        t_regs, s_regs = [SAtLo(k) for k in range(L - 1)], [SAsLo(k) for k in range(NW)]
-        keep = SQ_MID_KEEP or (None, None)
-        parts = ([t_regs], [keep[0]]) if i == SQ_MID_T - 1 else ([], [])
-        if i == SQ_MID_S - 1:
-            parts = (parts[0] + [s_regs], parts[1] + [keep[1]])
-        if parts[0]:
-            one = [set() if r is t_regs else sq_one_slots() for r in parts[0]] if SQ_KFOLD else None
-            body += mid_reduce(parts[0], keep=None if SQ_MID_KEEP is None else parts[1], one=one)
-    # diagonals of columns L .. 2L-2 (h >= L/2): column 2h sits at window position 2h - L
-    body += [f"v_mad_u64_u32 {SAt(2 * h - L)}, vcc, {SB0(h)}, {SB0(h)}, {SAt(2 * h - L)}" for h in range(L // 2, L)]
-    body.append(f"v_add_u32 {STMP}, 0x10000, %[a]")
+        body += sq_row_unrolled(i, halves, next_from_lds=not resident, waits=resident)
+        parts = []  # (slot pair low registers oldest to youngest, kept slots, slots left at 2^32 + low)
+        if i == SQ_MID_T - 1:
+            parts.append(([SAtLo(k) for k in range(L - 1)], SQ_MID_KEEP[0], set()))
+        if i == SQ_MID_S - 1 and "s" in halves:
+            parts.append(([SAsLo(k) for k in range(NW)], SQ_MID_KEEP[1], sq_one_slots()))
+        if parts:
+            regs, keep, one = zip(*parts)
+            body += mid_reduce(regs, keep=keep, one=one)
+    return body + sq_top_diagonals()
 
-    def st(k, reg):
-        if k < 64:
-            return f"ds_write_b32 %[a], {reg} offset:{k * 1024}"
-        return f"ds_write_b32 {STMP}, {reg} offset:{(k - 64) * 1024}"
 
-    for acc, lo, carry, carry_lo, base in ((SAt, SAtLo, STT, STTLO, 0), (SAs, SAsLo, STS, STSLO, L)):
-        body += [f"v_lshrrev_b64 {carry}, {LB}, {acc(0)}", f"v_and_b32 {lo(0)}, {MASK}, {lo(0)}", st(base, lo(0))]
-        for k in range(1, NW):
-            body += [f"v_lshl_add_u64 {acc(k)}, {carry}, 0, {acc(k)}",
-                     f"v_lshrrev_b64 {carry}, {LB}, {acc(k)}",
-                     f"v_and_b32 {lo(k)}, {MASK}, {lo(k)}",
-                     st(base + k, lo(k))]
-        body.append(st(base + NW, carry_lo))
-    body.append("s_waitcnt lgkmcnt(0)")
-    return rotate_carries(body)
+def square_unrolled():
+    body = load_consts() + load_column(SQP)
+    body += [f"ds_read_b64 {pair_dst(j)}, %[k]" + (f" offset:{8 * j}" if j else "") for j in range(L)]
+    body += [f"v_mov_b32 {SNPV}, %[np]", f"ds_read_b32 {SX0}, %[a]", "s_waitcnt lgkmcnt(0)"]
+    return rotate_carries(body + sq_rows() + normalise(SQP))
 
 
 # ------------------------------------------------------------------------------------------
-# The short path's whole binary chain as ONE body (round 7): the running value X never leaves the
-# lane's registers between products.  Both products use the square's register plan (the short
-# product's At_k / As_k / B are the square's SAt_k / SAs_k / SB, k < 35; its rows take h's limbs
-# from the asm inputs %[h0] .. %[h8]), the square's rows take x0_i from SB0(i) (no LDS row
-# operand), and each product ends in a normalise that writes limb k straight into the B register
-# the next product reads (v_and_b32 B(k), MASK, lo: the instruction that masked the limb before
-# its store) while the next product's initial s pairs -- (K'_j, 0) at %[d] + 288 before a square,
-# (D'_j, 0) at %[d] before a short product, read j into the pair column j starts in: STS, SAs_0 ..
-# SAs_34, for both products -- are read behind the pairs the normalise releases.  Row 0 of either
-# product waits for read j by count (LDS reads return in order; no scalar load is in flight then).
-# The multiplies, their order, the mid-product reduction and the folds are square_unrolled()'s and
-# mul_short_reg()'s: the results are bit-identical (tests/test_nadic_chain_asm.py).
+# The chain bodies: a whole run of the binary exponentiation as ONE asm body, the running value X
+# never leaving the lane's registers between products.  Both products use the square's register
+# plan (SQP: the short product's At_k / As_k / B are the square's SAt_k / SAs_k / SB, k < 35; its
+# rows take h's limbs from the asm inputs %[h0] .. %[h8]), the square's rows take x0_i from SB0(i)
+# (no LDS row operand), and each product ends in a normalise that writes limb k straight into the B
+# register the next product reads (normalise(to_regs=True)) while the next product's initial s
+# pairs -- (K'_j, 0) at %[d] + KOFF before a square, (D'_j, 0) at %[d] before a short product, pair j
+# into pair_dst(j) for both products -- are read behind the pairs the normalise releases.  Row 0 of
+# either product waits for read j by count (LDS reads return in order; no scalar load is in flight
+# then).  The multiplies, their order, the mid-product reduction and the folds are
+# square_unrolled()'s and mul_short_reg()'s: the results are bit-identical
+# (tests/test_nadic_chain_asm.py).
 #   s34 = j (the exponent bit of the current squaring), s35 = the exponent word holding bit j
 #   (one scalar load per 32 bits from %[kw]), s30 / s31 scratch, PADR (= SAADR) the pairs' address.
-# Control:  entry -> [square -> (bit j set: normalise, short product)] -> j == 0 ? exit :
-#           --j, normalise -> square ...;  exit: one normalise-and-store into the LDS column.
+# Control (chain_flow):  entry -> [square -> (bit j set: normalise, short product)] -> j == lo ?
+#   exit : --j, normalise -> square ...;  exit: one normalise-and-store into the LDS column.
+#
+# chain_short(): the short path's whole chain, X = (h, 0), bits sbits - 1 .. 0 of the key.
+#
+# The split exponentiation (DESIGN.md 5.7): |key| = k1 N + k0 and
+#     h^|key| = (h^k1 mod N)^N h^k0   (mod N^2)
+# (y = y' mod N gives y^N = y'^N mod N^2) runs two more bodies on the same flow:
+# chain_modn(): PHASE 1, h^k1 modulo N -- only the t half ("t") of the square and of the short
+#   product: x0 only, one quotient per row, no s window, no LDS pairs.  The t part of either product
+#   never reads the s part, so its multiplies, their order, the t slots of the mid-product reduction
+#   and the column bounds are square_unrolled()'s / mul_short_reg()'s t half, and its limbs are theirs
+#   whatever the s digit (tests/test_nadic_split_asm.py).  It exits by storing (x0, 0) into the
+#   lane's LDS column.
+# chain_seg(): a SEGMENT of the modulo-N^2 chain for phase 2 -- X enters from the lane's LDS column,
+#   the exponent bits %[hi] - 1 .. %[lo] of the words at %[kw] are run and the result leaves through
+#   the normalise-and-store; between two segments the kernel multiplies the column by a window-table
+#   entry (fbm_na_mm_glb).
 # ------------------------------------------------------------------------------------------
 PADR = SAADR
 KOFF = 2 * L * 4  # the square's pairs follow the short product's 36 pairs in the LDS row
@@ -762,110 +738,12 @@ def chain_wait(j):
     return [f"s_waitcnt lgkmcnt({L - 1 - j})"] if L - 1 - j < 15 else []
 
 
-def chain_pair_dst(j):
-    return STS if j == 0 else SAs(j - 1)
+def pair_read(j):
+    return f"ds_read_b64 {pair_dst(j)}, {PADR}" + (f" offset:{8 * j}" if j else "")
 
 
 def chain_prefetch_all():
-    return [f"ds_read_b64 {chain_pair_dst(j)}, {PADR} offset:{8 * j}" for j in range(L)]
-
-
-def chain_sq_row(i):
-    """sq_row_static(i) with the row operand 2 x0_i taken from SB0 (set by the previous row)."""
-    first, last, even = i == 0, i == L - 1, i % 2 == 0
-    out = []
-    if even:
-        out.append(f"v_mad_u64_u32 {SAt(0)}, vcc, {SB0(i // 2)}, {SB0(i // 2)}, {'0' if first else SAt(0)}")
-    out.append(f"v_mul_lo_u32 {SQ}, {SAtLo(0)}, {SNPV}")
-    if first:
-        out += chain_wait(0)
-    out.append(f"v_mad_u64_u32 {STS}, vcc, {SX0D}, {SB1(0)}, {STS if first else SAs(0)}")
-    for j in range(1, L):
-        if first:
-            addend = SAs(j - 1)
-            out += chain_wait(j)
-        else:
-            addend = "0" if j == NW else SAs(j)
-        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {SX0D}, {SB1(j)}, {addend}")
-        if j == 2:
-            out.append(f"v_and_b32 {SQ}, {MASK}, {SQ}")
-        if j == 12:
-            out.append(f"v_mad_i64_i32 {STS}, vcc, {SQ}, -1, {STS}")
-        if j == 20:
-            out.append(f"v_mul_lo_u32 {SQ2}, {STSLO}, {SNPV}")
-        if j == 26:
-            out.append(f"v_and_b32 {SQ2}, {MASK}, {SQ2}")
-    for k in range(i + 1, L):
-        addend = "0" if (first or k == L - 1) else SAt(k)
-        out.append(f"v_mad_u64_u32 {SAt(k)}, vcc, {SX0D}, {SB0(k)}, {addend}")
-    top = "0" if last else SAt(L - 1)
-    out.append(f"v_mad_u64_u32 {STT}, vcc, {SQ}, {Ns(0)}, {SAt(0)}")
-    for k in range(1, L):
-        out.append(f"v_mad_u64_u32 {SAt(k - 1)}, vcc, {SQ}, {Ns(k)}, {SAt(k) if k < L - 1 else top}")
-    out.append(f"v_mad_u64_u32 {STS}, vcc, {SQ2}, {Ns(0)}, {STS}")
-    for j in range(1, L):
-        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {SQ2}, {Ns(j)}, {SAs(j - 1)}")
-    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}",
-            f"v_lshrrev_b64 {STS}, {LB}, {STS}", f"v_lshl_add_u64 {SAs(0)}, {STS}, 0, {SAs(0)}"]
-    if not last:
-        out.append(f"v_lshlrev_b32 {SX0D}, 1, {SB0(i + 1)}")
-    return out
-
-
-def chain_sq_rows():
-    """The unrolled triangular square on the B registers (its s pairs prefetched): window out."""
-    assert SQ_KFOLD and UNROLLED_SQUARE and SQ_MID_KEEP is not None
-    body = [f"v_lshlrev_b32 {SX0D}, 1, {SB0(0)}"]
-    t_regs, s_regs = [SAtLo(k) for k in range(L - 1)], [SAsLo(k) for k in range(NW)]
-    for i in range(L):
-        body += chain_sq_row(i)
-        parts = ([t_regs], [SQ_MID_KEEP[0]]) if i == SQ_MID_T - 1 else ([], [])
-        if i == SQ_MID_S - 1:
-            parts = (parts[0] + [s_regs], parts[1] + [SQ_MID_KEEP[1]])
-        if parts[0]:
-            one = [set() if r is t_regs else sq_one_slots() for r in parts[0]]
-            body += mid_reduce(parts[0], keep=parts[1], one=one)
-    body += [f"v_mad_u64_u32 {SAt(2 * h - L)}, vcc, {SB0(h)}, {SB0(h)}, {SAt(2 * h - L)}" for h in range(L // 2, L)]
-    return body
-
-
-def chain_short_row(i, x=None):
-    """short_row(i) on the square's register plan; row 0's s addends are the prefetched pairs."""
-    assert SHORT_KFOLD
-    x, first = x or f"%[h{i}]", i == 0
-    out = [f"v_mad_u64_u32 {STT}, vcc, {x}, {SB0(0)}, {'0' if first else SAt(0)}"]
-    for j in range(1, L):
-        addend = "0" if (first or j == NW) else SAt(j)
-        out.append(f"v_mad_u64_u32 {SAt(j - 1)}, vcc, {x}, {SB0(j)}, {addend}")
-        if j == 3:
-            out.append(f"v_mul_lo_u32 {SQ}, {STTLO}, {SNPV}")
-        if j == 6:
-            out.append(f"v_and_b32 {SQ}, {MASK}, {SQ}")
-    out.append(f"v_mad_u64_u32 {STT}, vcc, {SQ}, {Ns(0)}, {STT}")
-    for j in range(1, L):
-        out.append(f"v_mad_u64_u32 {SAt(j - 1)}, vcc, {SQ}, {Ns(j)}, {SAt(j - 1)}")
-    if first:
-        out += chain_wait(0)
-    out.append(f"v_mad_u64_u32 {STS}, vcc, {x}, {SB1(0)}, {STS if first else SAs(0)}")
-    for j in range(1, L):
-        if first:
-            addend = SAs(j - 1)
-            out += chain_wait(j)
-        else:
-            addend = "0" if j == NW else SAs(j)
-        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {x}, {SB1(j)}, {addend}")
-        if j == 12:
-            out.append(f"v_mad_i64_i32 {STS}, vcc, {SQ}, -1, {STS}")
-        if j == 20:
-            out.append(f"v_mul_lo_u32 {SQ2}, {STSLO}, {SNPV}")
-        if j == 26:
-            out.append(f"v_and_b32 {SQ2}, {MASK}, {SQ2}")
-    out.append(f"v_mad_u64_u32 {STS}, vcc, {SQ2}, {Ns(0)}, {STS}")
-    for j in range(1, L):
-        out.append(f"v_mad_u64_u32 {SAs(j - 1)}, vcc, {SQ2}, {Ns(j)}, {SAs(j - 1)}")
-    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}",
-            f"v_lshrrev_b64 {STS}, {LB}, {STS}", f"v_lshl_add_u64 {SAs(0)}, {STS}, 0, {SAs(0)}"]
-    return out
+    return [f"ds_read_b64 {pair_dst(j)}, {PADR} offset:{8 * j}" for j in range(L)]
 
 
 # The chain's short rows 1 .. 8 unrolled (11 KB of code beside the square's 35 KB) or, A/B switch
@@ -874,9 +752,14 @@ def chain_short_row(i, x=None):
 CHAIN_SHORT_LOOPED = os.environ.get("FBM_GEN_CHAIN_SHORT_LOOPED", "0") == "1"
 
 
-def chain_short_rows():
-    if not CHAIN_SHORT_LOOPED:
-        return [ln for i in range(KS) for ln in chain_short_row(i)]
+def chain_short_row(i, halves="ts"):
+    return short_row(SQP, i, f"%[h{i}]", [pair_dst(j) for j in range(L)], halves, waits=True)
+
+
+def short_rows(halves="ts"):
+    """The short product on the B registers (its s pairs prefetched): window out."""
+    if not CHAIN_SHORT_LOOPED or halves == "t":
+        return [ln for i in range(KS) for ln in chain_short_row(i, halves)]
     loop = ".Lfbm_ch_row_%="
     rot = [f"v_mov_b32 {STMP}, %[h1]"] + [f"v_mov_b32 %[h{i}], %[h{i + 1}]" for i in range(1, KS - 1)]
     rot.append(f"v_mov_b32 %[h{KS - 1}], {STMP}")
@@ -884,265 +767,97 @@ def chain_short_rows():
             ["s_sub_u32 s31, s31, 1", "s_cmp_lg_u32 s31, 0", f"s_cbranch_scc1 {loop}"])
 
 
-def chain_normalise(prefetch):
-    """Window -> the B registers (limb k of digit d into SB_d(k)); `prefetch`: read the next product's
-    pair j from PADR + 8 j into the pair the s normalise has just released (STS is free throughout:
-    both halves carry in STT)."""
-    out = []
-    for acc, lo, dst, s_part in ((SAt, SAtLo, SB0, False), (SAs, SAsLo, SB1, True)):
-        pf = prefetch and s_part
-        if pf:
-            out.append(f"ds_read_b64 {chain_pair_dst(0)}, {PADR}")
-        out += [f"v_lshrrev_b64 {STT}, {LB}, {acc(0)}", f"v_and_b32 {dst(0)}, {MASK}, {lo(0)}"]
-        if pf:
-            out.append(f"ds_read_b64 {chain_pair_dst(1)}, {PADR} offset:8")
-        for k in range(1, NW):
-            out += [f"v_lshl_add_u64 {acc(k)}, {STT}, 0, {acc(k)}",
-                    f"v_lshrrev_b64 {STT}, {LB}, {acc(k)}",
-                    f"v_and_b32 {dst(k)}, {MASK}, {lo(k)}"]
-            if pf:
-                out.append(f"ds_read_b64 {chain_pair_dst(k + 1)}, {PADR} offset:{8 * (k + 1)}")
-        out.append(f"v_mov_b32 {dst(NW)}, {STTLO}")
-    return out
-
-
-def chain_store():
-    """The chain's exit: the window normalised into the lane's LDS column (square_unrolled's tail)."""
-    out = [f"v_add_u32 {STMP}, 0x10000, %[a]"]
-
-    def st(k, reg):
-        if k < 64:
-            return f"ds_write_b32 %[a], {reg} offset:{k * 1024}"
-        return f"ds_write_b32 {STMP}, {reg} offset:{(k - 64) * 1024}"
-
-    for acc, lo, carry, carry_lo, base in ((SAt, SAtLo, STT, STTLO, 0), (SAs, SAsLo, STS, STSLO, L)):
-        out += [f"v_lshrrev_b64 {carry}, {LB}, {acc(0)}", f"v_and_b32 {lo(0)}, {MASK}, {lo(0)}", st(base, lo(0))]
-        for k in range(1, NW):
-            out += [f"v_lshl_add_u64 {acc(k)}, {carry}, 0, {acc(k)}",
-                    f"v_lshrrev_b64 {carry}, {LB}, {acc(k)}",
-                    f"v_and_b32 {lo(k)}, {MASK}, {lo(k)}",
-                    st(base + k, lo(k))]
-        out.append(st(base + NW, carry_lo))
-    out.append("s_waitcnt lgkmcnt(0)")
-    return out
+def one_product(short, halves):
+    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]"]
+    if "s" in halves:
+        body += [f"v_mov_b32 {PADR}, %[p]"] + chain_prefetch_all()
+    body.append("s_waitcnt lgkmcnt(0)")
+    body += short_rows(halves) if short else sq_rows(halves, resident=True)
+    return rotate_carries(body + normalise(SQP, halves, to_regs=True))
 
 
 def chain_one(short):
     """One product of the chain as a body of its own, registers in (X in SB0 / SB1), registers out
     (tests/test_nadic_chain_asm.py): the pairs from %[p], the rows, the normalise into SB0 / SB1."""
-    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]", f"v_mov_b32 {PADR}, %[p]"] + chain_prefetch_all()
-    body.append("s_waitcnt lgkmcnt(0)")
-    body += chain_short_rows() if short else chain_sq_rows()
-    return rotate_carries(body + chain_normalise(False))
+    return one_product(short, "ts")
+
+
+def modn_one(short):
+    """One product of phase 1 as a body of its own, x0 in SB0 and out in SB0 (the simulator tests)."""
+    return one_product(short, "t")
+
+
+def chain_label(tag, k):
+    return f".Lfbm_{tag}_{k}_%="
+
+
+def chain_flow(tag, halves, entry, leave, lo="0"):
+    """The exponent-bit control flow around the resident products.  `entry` leaves X in the B registers and
+    s34 = the first bit's index (and may branch to the exit label); bits s34 .. `lo` of the words at %[kw]
+    are run; `leave` follows the exit label with the window not yet normalised.  `halves` "ts" adds what
+    the s half needs: the pairs' address and the prefetch behind each normalise."""
+    s = "s" in halves
+    word = ["s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2", "s_load_dword s35, %[kw], s30"]
+    sq_pairs = [f"s_add_u32 s31, %[d], {KOFF}", f"v_mov_b32 {PADR}, s31"] if s else []
+    body = entry + word + sq_pairs + (chain_prefetch_all() if s else [])
+    body += ["s_waitcnt lgkmcnt(0)", chain_label(tag, "sq") + ":"] + sq_rows(halves, resident=True)
+    # bit j of the exponent: a short product follows the square
+    body += ["s_and_b32 s30, s34, 31", "s_lshr_b32 s30, s35, s30", "s_and_b32 s30, s30, 1",
+             f"s_cbranch_scc0 {chain_label(tag, 'next')}"] + ([f"v_mov_b32 {PADR}, %[d]"] if s else [])
+    body += normalise(SQP, halves, to_regs=True, prefetch=True) + short_rows(halves)
+    body += [chain_label(tag, "next") + ":", f"s_cmp_eq_u32 s34, {lo}", f"s_cbranch_scc1 {chain_label(tag, 'exit')}",
+             "s_sub_u32 s34, s34, 1", "s_and_b32 s30, s34, 31", "s_cmp_lg_u32 s30, 31",
+             f"s_cbranch_scc1 {chain_label(tag, 'word')}"]
+    # the next 32 exponent bits (no LDS read is in flight here: the counted waits stay exact)
+    body += word + ["s_waitcnt lgkmcnt(0)", chain_label(tag, "word") + ":"] + sq_pairs
+    body += normalise(SQP, halves, to_regs=True, prefetch=True)
+    body += [f"s_branch {chain_label(tag, 'sq')}", chain_label(tag, "exit") + ":"] + leave
+    return rotate_carries(body)
+
+
+def chain_from_h(tag, halves):
+    """The entry of a chain that starts at X = (h, 0): the B registers <- h's limbs, and the window <- X, so
+    that zero iterations (%[sb] = 0: the exponent is 1) send X through the exit's normalise unchanged."""
+    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]"]
+    body += [f"v_mov_b32 {SB0(i)}, " + (f"%[h{i}]" if i < KS else "0") for i in range(L)]
+    if "s" in halves:
+        body += [f"v_mov_b32 {SB1(i)}, 0" for i in range(L)]
+    body += [f"v_mov_b32 {SAtLo(k)}, {SB0(k)}" for k in range(NW)] + [f"v_mov_b32 v{2 * k + 1}, 0" for k in range(NW)]
+    if "s" in halves:
+        body += [f"v_mov_b32 {SAsLo(k)}, 0" for k in range(NW)]
+        body += [f"v_mov_b32 v{SAS0 + 2 * k + 1}, 0" for k in range(NW)]
+    return body + ["s_mov_b32 s34, %[sb]", "s_cmp_eq_u32 s34, 0", f"s_cbranch_scc1 {chain_label(tag, 'exit')}",
+                   "s_sub_u32 s34, s34, 1"]
 
 
 def chain_short():
     """The whole chain: X = (h, 0), then for j = sbits - 1 .. 0 a square and, where bit j of the
     exponent (%[kw]'s words) is set, a short product; the result normalised into the LDS column."""
-    lbl = {k: f".Lfbm_ch_{k}_%=" for k in ("sq", "next", "exit", "word")}
-    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]"]
-    body += [f"v_mov_b32 {SB0(i)}, " + (f"%[h{i}]" if i < KS else "0") for i in range(L)]
-    body += [f"v_mov_b32 {SB1(i)}, 0" for i in range(L)]
-    # zero iterations (|key| = 1): the store below normalises the window, so X goes through it
-    body += [f"v_mov_b32 {SAtLo(k)}, {SB0(k)}" for k in range(NW)] + [f"v_mov_b32 v{2 * k + 1}, 0" for k in range(NW)]
-    body += [f"v_mov_b32 {SAsLo(k)}, 0" for k in range(NW)] + [f"v_mov_b32 v{SAS0 + 2 * k + 1}, 0" for k in range(NW)]
-    body += ["s_mov_b32 s34, %[sb]", "s_cmp_eq_u32 s34, 0", f"s_cbranch_scc1 {lbl['exit']}",
-             "s_sub_u32 s34, s34, 1", "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2",
-             "s_load_dword s35, %[kw], s30",
-             f"s_add_u32 s31, %[d], {KOFF}", f"v_mov_b32 {PADR}, s31"]
-    body += chain_prefetch_all() + ["s_waitcnt lgkmcnt(0)", lbl["sq"] + ":"]
-    body += chain_sq_rows()
-    # bit j of the exponent: a short product follows the square
-    body += ["s_and_b32 s30, s34, 31", "s_lshr_b32 s30, s35, s30", "s_and_b32 s30, s30, 1",
-             f"s_cbranch_scc0 {lbl['next']}", f"v_mov_b32 {PADR}, %[d]"]
-    body += chain_normalise(True) + chain_short_rows()
-    body += [lbl["next"] + ":", "s_cmp_eq_u32 s34, 0", f"s_cbranch_scc1 {lbl['exit']}",
-             "s_sub_u32 s34, s34, 1", "s_and_b32 s30, s34, 31", "s_cmp_lg_u32 s30, 31",
-             f"s_cbranch_scc1 {lbl['word']}",
-             # the next 32 exponent bits (no LDS read is in flight here: the counted waits stay exact)
-             "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2", "s_load_dword s35, %[kw], s30",
-             "s_waitcnt lgkmcnt(0)", lbl["word"] + ":",
-             f"s_add_u32 s31, %[d], {KOFF}", f"v_mov_b32 {PADR}, s31"]
-    body += chain_normalise(True) + [f"s_branch {lbl['sq']}", lbl["exit"] + ":"]
-    body += chain_store()
-    return rotate_carries(body)
-
-
-# ------------------------------------------------------------------------------------------
-# The split exponentiation (round 8, DESIGN.md 5.7): |key| = k1 N + k0 and
-#     h^|key| = (h^k1 mod N)^N h^k0   (mod N^2)
-# (y = y' mod N gives y^N = y'^N mod N^2).  Two more bodies on the chain's register plan:
-#
-# chain_modn(): PHASE 1, h^k1 modulo N -- chain_short()'s binary chain with only the t half of the
-#   square and of the short product: x0 only, one quotient per row, no s window, no LDS pairs.  The t
-#   part of either product never reads the s part, so its multiplies, their order, the t slots of the
-#   mid-product reduction and the column bounds are square_unrolled()'s / mul_short_reg()'s t half, and
-#   its limbs are theirs whatever the s digit (tests/test_nadic_split_asm.py).  It exits by storing
-#   (x0, 0) into the lane's LDS column.
-# chain_seg(): a SEGMENT of the modulo-N^2 chain for phase 2 -- X enters from the lane's LDS column,
-#   the exponent bits %[hi] - 1 .. %[lo] of the words at %[kw] are run (a square per bit, a short
-#   product where the bit is set) and the result leaves through the normalise-and-store; between two
-#   segments the kernel multiplies the column by a window-table entry (fbm_na_mm_glb).
-# ------------------------------------------------------------------------------------------
-def modn_sq_row(i):
-    """The t half of chain_sq_row(i)."""
-    first, last, even = i == 0, i == L - 1, i % 2 == 0
-    out = []
-    if even:
-        out.append(f"v_mad_u64_u32 {SAt(0)}, vcc, {SB0(i // 2)}, {SB0(i // 2)}, {'0' if first else SAt(0)}")
-    out.append(f"v_mul_lo_u32 {SQ}, {SAtLo(0)}, {SNPV}")
-    cross = []
-    for k in range(i + 1, L):
-        addend = "0" if (first or k == L - 1) else SAt(k)
-        cross.append(f"v_mad_u64_u32 {SAt(k)}, vcc, {SX0D}, {SB0(k)}, {addend}")
-    out += cross[:2] + [f"v_and_b32 {SQ}, {MASK}, {SQ}"] + cross[2:]
-    top = "0" if last else SAt(L - 1)
-    out.append(f"v_mad_u64_u32 {STT}, vcc, {SQ}, {Ns(0)}, {SAt(0)}")
-    for k in range(1, L):
-        out.append(f"v_mad_u64_u32 {SAt(k - 1)}, vcc, {SQ}, {Ns(k)}, {SAt(k) if k < L - 1 else top}")
-    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}"]
-    if not last:
-        out.append(f"v_lshlrev_b32 {SX0D}, 1, {SB0(i + 1)}")
-    return out
-
-
-def modn_sq_rows():
-    """The unrolled triangular square modulo N on SB0: window out (the t half of chain_sq_rows())."""
-    assert SQ_KFOLD and UNROLLED_SQUARE and SQ_MID_KEEP is not None
-    body = [f"v_lshlrev_b32 {SX0D}, 1, {SB0(0)}"]
-    t_regs = [SAtLo(k) for k in range(L - 1)]
-    for i in range(L):
-        body += modn_sq_row(i)
-        if i == SQ_MID_T - 1:
-            body += mid_reduce([t_regs], keep=[SQ_MID_KEEP[0]], one=[set()])
-    body += [f"v_mad_u64_u32 {SAt(2 * h - L)}, vcc, {SB0(h)}, {SB0(h)}, {SAt(2 * h - L)}" for h in range(L // 2, L)]
-    return body
-
-
-def modn_short_row(i):
-    """The t half of chain_short_row(i)."""
-    x, first = f"%[h{i}]", i == 0
-    out = [f"v_mad_u64_u32 {STT}, vcc, {x}, {SB0(0)}, {'0' if first else SAt(0)}"]
-    for j in range(1, L):
-        addend = "0" if (first or j == NW) else SAt(j)
-        out.append(f"v_mad_u64_u32 {SAt(j - 1)}, vcc, {x}, {SB0(j)}, {addend}")
-        if j == 3:
-            out.append(f"v_mul_lo_u32 {SQ}, {STTLO}, {SNPV}")
-        if j == 6:
-            out.append(f"v_and_b32 {SQ}, {MASK}, {SQ}")
-    out.append(f"v_mad_u64_u32 {STT}, vcc, {SQ}, {Ns(0)}, {STT}")
-    for j in range(1, L):
-        out.append(f"v_mad_u64_u32 {SAt(j - 1)}, vcc, {SQ}, {Ns(j)}, {SAt(j - 1)}")
-    out += [f"v_lshrrev_b64 {STT}, {LB}, {STT}", f"v_lshl_add_u64 {SAt(0)}, {STT}, 0, {SAt(0)}"]
-    return out
-
-
-def modn_short_rows():
-    return [ln for i in range(KS) for ln in modn_short_row(i)]
-
-
-def modn_normalise():
-    """The t window -> SB0 (the t half of chain_normalise)."""
-    out = [f"v_lshrrev_b64 {STT}, {LB}, {SAt(0)}", f"v_and_b32 {SB0(0)}, {MASK}, {SAtLo(0)}"]
-    for k in range(1, NW):
-        out += [f"v_lshl_add_u64 {SAt(k)}, {STT}, 0, {SAt(k)}",
-                f"v_lshrrev_b64 {STT}, {LB}, {SAt(k)}",
-                f"v_and_b32 {SB0(k)}, {MASK}, {SAtLo(k)}"]
-    out.append(f"v_mov_b32 {SB0(NW)}, {STTLO}")
-    return out
-
-
-def modn_store():
-    """Phase 1's exit: the t window normalised into digit 0 of the lane's LDS column, digit 1 = 0."""
-    out = [f"v_add_u32 {STMP}, 0x10000, %[a]"]
-
-    def st(k, reg):
-        if k < 64:
-            return f"ds_write_b32 %[a], {reg} offset:{k * 1024}"
-        return f"ds_write_b32 {STMP}, {reg} offset:{(k - 64) * 1024}"
-
-    out += [f"v_lshrrev_b64 {STT}, {LB}, {SAt(0)}", f"v_and_b32 {SAtLo(0)}, {MASK}, {SAtLo(0)}", st(0, SAtLo(0))]
-    for k in range(1, NW):
-        out += [f"v_lshl_add_u64 {SAt(k)}, {STT}, 0, {SAt(k)}",
-                f"v_lshrrev_b64 {STT}, {LB}, {SAt(k)}",
-                f"v_and_b32 {SAtLo(k)}, {MASK}, {SAtLo(k)}",
-                st(k, SAtLo(k))]
-    out += [st(NW, STTLO), f"v_mov_b32 {STSLO}, 0"]
-    out += [st(L + k, STSLO) for k in range(L)]
-    out.append("s_waitcnt lgkmcnt(0)")
-    return out
-
-
-def modn_one(short):
-    """One product of phase 1 as a body of its own, x0 in SB0 and out in SB0 (the simulator tests)."""
-    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]", "s_waitcnt lgkmcnt(0)"]
-    body += modn_short_rows() if short else modn_sq_rows()
-    return rotate_carries(body + modn_normalise())
+    return chain_flow("ch", "ts", chain_from_h("ch", "ts"), normalise(SQP))
 
 
 def chain_modn():
     """Phase 1: x0 = h, then for j = sbits - 1 .. 0 a square modulo N and, where bit j of the exponent
-    (%[kw]'s words: k1) is set, a short product; (x0, 0) stored into the LDS column."""
-    lbl = {k: f".Lfbm_cn_{k}_%=" for k in ("sq", "next", "exit", "word")}
-    body = load_consts() + [f"v_mov_b32 {SNPV}, %[np]"]
-    body += [f"v_mov_b32 {SB0(i)}, " + (f"%[h{i}]" if i < KS else "0") for i in range(L)]
-    # zero iterations (k1 = 1): the store below normalises the window, so x0 goes through it
-    body += [f"v_mov_b32 {SAtLo(k)}, {SB0(k)}" for k in range(NW)] + [f"v_mov_b32 v{2 * k + 1}, 0" for k in range(NW)]
-    body += ["s_mov_b32 s34, %[sb]", "s_cmp_eq_u32 s34, 0", f"s_cbranch_scc1 {lbl['exit']}",
-             "s_sub_u32 s34, s34, 1", "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2",
-             "s_load_dword s35, %[kw], s30", "s_waitcnt lgkmcnt(0)", lbl["sq"] + ":"]
-    body += modn_sq_rows()
-    body += ["s_and_b32 s30, s34, 31", "s_lshr_b32 s30, s35, s30", "s_and_b32 s30, s30, 1",
-             f"s_cbranch_scc0 {lbl['next']}"]
-    body += modn_normalise() + modn_short_rows()
-    body += [lbl["next"] + ":", "s_cmp_eq_u32 s34, 0", f"s_cbranch_scc1 {lbl['exit']}",
-             "s_sub_u32 s34, s34, 1", "s_and_b32 s30, s34, 31", "s_cmp_lg_u32 s30, 31",
-             f"s_cbranch_scc1 {lbl['word']}",
-             "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2", "s_load_dword s35, %[kw], s30",
-             "s_waitcnt lgkmcnt(0)", lbl["word"] + ":"]
-    body += modn_normalise() + [f"s_branch {lbl['sq']}", lbl["exit"] + ":"]
-    body += ["s_waitcnt lgkmcnt(0)"] + modn_store()
-    return rotate_carries(body)
+    (%[kw]'s words: k1) is set, a short product; (x0, 0) stored into the LDS column (digit 1 as zeros)."""
+    return chain_flow("cn", "t", chain_from_h("cn", "t"), ["s_waitcnt lgkmcnt(0)"] + normalise(SQP, "t"))
 
 
 def chain_seg():
     """A segment of the modulo-N^2 chain: X from the lane's LDS column, then for j = %[hi] - 1 .. %[lo] a
     square and, where bit j of the words at %[kw] is set, a short product; X back into the column.
     %[hi] == %[lo]: nothing is run and the column stays as it is."""
-    lbl = {k: f".Lfbm_cs_{k}_%=" for k in ("sq", "next", "exit", "word", "done")}
-    body = ["s_cmp_eq_u32 %[hi], %[lo]", f"s_cbranch_scc1 {lbl['done']}"]
-    body += load_consts() + [f"v_mov_b32 {SNPV}, %[np]", f"v_add_u32 {STMP}, 0x10000, %[a]"]
-    for j in range(2 * L):
-        reg = SB0(j) if j < L else SB1(j - L)
-        if j < 64:
-            body.append(f"ds_read_b32 {reg}, %[a] offset:{j * 1024}")
-        else:
-            body.append(f"ds_read_b32 {reg}, {STMP} offset:{(j - 64) * 1024}")
-    body += ["s_sub_u32 s34, %[hi], 1", "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2",
-             "s_load_dword s35, %[kw], s30",
-             f"s_add_u32 s31, %[d], {KOFF}", f"v_mov_b32 {PADR}, s31"]
-    body += chain_prefetch_all() + ["s_waitcnt lgkmcnt(0)", lbl["sq"] + ":"]
-    body += chain_sq_rows()
-    body += ["s_and_b32 s30, s34, 31", "s_lshr_b32 s30, s35, s30", "s_and_b32 s30, s30, 1",
-             f"s_cbranch_scc0 {lbl['next']}", f"v_mov_b32 {PADR}, %[d]"]
-    body += chain_normalise(True) + chain_short_rows()
-    body += [lbl["next"] + ":", "s_cmp_eq_u32 s34, %[lo]", f"s_cbranch_scc1 {lbl['exit']}",
-             "s_sub_u32 s34, s34, 1", "s_and_b32 s30, s34, 31", "s_cmp_lg_u32 s30, 31",
-             f"s_cbranch_scc1 {lbl['word']}",
-             "s_lshr_b32 s30, s34, 5", "s_lshl_b32 s30, s30, 2", "s_load_dword s35, %[kw], s30",
-             "s_waitcnt lgkmcnt(0)", lbl["word"] + ":",
-             f"s_add_u32 s31, %[d], {KOFF}", f"v_mov_b32 {PADR}, s31"]
-    body += chain_normalise(True) + [f"s_branch {lbl['sq']}", lbl["exit"] + ":"]
-    body += chain_store() + [lbl["done"] + ":"]
-    return rotate_carries(body)
+    done = chain_label("cs", "done")
+    entry = ["s_cmp_eq_u32 %[hi], %[lo]", f"s_cbranch_scc1 {done}"] + load_consts()
+    entry += [f"v_mov_b32 {SNPV}, %[np]"] + load_column(SQP) + ["s_sub_u32 s34, %[hi], 1"]
+    return chain_flow("cs", "ts", entry, normalise(SQP) + [done + ":"], lo="%[lo]")
 
 
 def modn_sq_mads():
-    return count_mads(modn_sq_rows())
+    return count_mads(sq_rows("t", resident=True))
 
 
 def modn_short_mads():
-    return count_mads(modn_short_rows())
+    return count_mads(short_rows("t"))
 
 
 def chain_macros(lines, prefix="FBM_CH_R"):
@@ -1252,18 +967,16 @@ def chain_counts():
     ms_rows = [ln for i in range(KS) for ln in chain_short_row(i)]
     if CHAIN_SHORT_LOOPED:
         ms_rows += ["v_mov_b32"] * (KS * (KS - 1))
-    return {"CHAIN_SQ": count_kinds(chain_normalise(True) + chain_sq_rows()),
-            "CHAIN_SHORT": count_kinds(chain_normalise(True) + ms_rows),
+    norm = normalise(SQP, to_regs=True, prefetch=True)
+    return {"CHAIN_SQ": count_kinds(norm + sq_rows(resident=True)),
+            "CHAIN_SHORT": count_kinds(norm + ms_rows),
             "CALL_SQ": count_kinds(square_unrolled()), "CALL_SHORT": count_kinds(mul_short_reg())}
 
 
 def sq_mads():
     """64-bit multiply-adds per square: triangular t part (cross products + diagonals), the s part's
     (2 x0) x1 and - q (K' - q), the two q N passes, the mid-product reduction (its kept slots)."""
-    if UNROLLED_SQUARE:
-        return count_mads(square_unrolled())
-    cross = L * (L - 1) // 2
-    return cross + L + L * L + (L * L + L + L * L) + (L - 2) + (NW - 1)
+    return count_mads(square_unrolled())
 
 
 def mm_mads():
@@ -1271,7 +984,7 @@ def mm_mads():
 
 
 def clobbers():
-    regs = [f'"v{i}"' for i in range(max(MM_NREG, SQ_NREG, MS_NREG))]
+    regs = [f'"v{i}"' for i in range(max(MM_NREG, SQ_NREG))]
     regs += [f'"s{i}"' for i in [16, 17] + list(range(19, 32)) + [34, 35] + list(range(36, 100))]
     out = [", ".join(regs[i:i + 16]) for i in range(0, len(regs), 16)]
     return " \\\n  ".join(x + "," for x in out[:-1]) + " \\\n  " + out[-1]
@@ -1286,7 +999,7 @@ def count_mads(lines):
 
 
 def main():
-    mm, sq, ms = product(False), (square_unrolled() if UNROLLED_SQUARE else square_tri()), mul_short_reg()
+    mm, sq, ms = product(False), square_unrolled(), mul_short_reg()
     sq_looped, chain = square_tri(), chain_short()
     mm_row, sq_body = row(False, False), sq_row("odd")
     hdr = f"""// GENERATED by tools/gen_nadic_asm.py -- do not edit by hand.
@@ -1310,7 +1023,7 @@ def main():
 // the square's s window starts at the pairs (2^29 - 1 + P'_j, 0), P' = (K - E) mod N, K = (1 - R) mod N,
 // E = sum of 2^(32 + 29 c) over the columns c set in this mask (the mid-product reduction leaves them at
 // 2^32 + low dword: sq_kfold_extra in the generator).  The short product's: (D'_j, 0) (mul_short_reg).
-#define FBM_NA_SQ_ONE_MASK {hex(sum(1 << (SQ_MID_S + k) for k in sq_one_slots()) if SQ_KFOLD else 0)}ull
+#define FBM_NA_SQ_ONE_MASK {hex(sum(1 << (SQ_MID_S + k) for k in sq_one_slots()))}ull
 
 #define FBM_NA_CLOBBERS \\
   {clobbers()}
@@ -1350,7 +1063,6 @@ __device__ __forceinline__ void fbm_na_ms_reg(uint32_t a_off, const uint32_t (&h
       : "memory", "vcc", "scc", FBM_NA_CLOBBERS);
 }}
 
-#if !defined(FBM_NA_PLAIN_SQUARE) && !defined(FBM_NA_LOOPED_SQUARE)
 // a <- a^2 R^-1 (mod N^2): triangular x0^2, full x0 * 2 x1, every row unrolled ({len(sq)} instructions);
 // k: LDS byte address of the s window's initial pairs (2^29 - 1 + P'_j, 0) (FBM_NA_SQ_ONE_MASK).
 __device__ __forceinline__ void fbm_na_sq_lds(uint32_t a_off, uint32_t k_off, const uint32_t* NK, uint32_t np) {{
@@ -1360,26 +1072,6 @@ __device__ __forceinline__ void fbm_na_sq_lds(uint32_t a_off, uint32_t k_off, co
       : [a] "v"(a_off), [k] "v"(k_off), [NK] "s"(NK), [np] "s"(np)
       : "memory", "vcc", "scc", FBM_NA_CLOBBERS);
 }}
-#elif defined(FBM_NA_LOOPED_SQUARE)
-// A/B variant (-DFBM_NA_LOOPED_SQUARE): the row loop with computed-jump row suffixes ({len(sq_looped)} instructions).
-__device__ __forceinline__ void fbm_na_sq_lds(uint32_t a_off, uint32_t, const uint32_t* NK, uint32_t np) {{
-  asm volatile(
-{c_string(sq_looped)}
-      :
-      : [a] "v"(a_off), [NK] "s"(NK), [np] "s"(np)
-      : "memory", "vcc", "scc", FBM_NA_CLOBBERS);
-}}
-#else
-// A/B variant (-DFBM_NA_PLAIN_SQUARE): the general product with B = A from LDS -- no computed
-// jumps, {L * count_mads(row(False, True)) + 2 * (NW - 1)} multiplies instead of {sq_mads()}.
-__device__ __forceinline__ void fbm_na_sq_lds(uint32_t a_off, uint32_t, const uint32_t* NK, uint32_t np) {{
-  asm volatile(
-{c_string(product(True))}
-      :
-      : [a] "v"(a_off), [NK] "s"(NK), [np] "s"(np)
-      : "memory", "vcc", "scc", FBM_NA_CLOBBERS);
-}}
-#endif
 
 // The looped triangular square (computed-jump row suffixes, {len(sq_looped)} instructions): the table path's squares
 // (small moduli, FDH retries -- cold), so the launch's hot code keeps one copy of the unrolled square.

@@ -757,7 +757,7 @@ def square_cyc(g, carries=CARRY_PAIRS):
 
 
 # ------------------------------------------------------------------------------------------
-# The short-base product x h 2^-261 (tools/gen_nadic_asm.py's mul_short: rows = h's KS limbs,
+# The short-base product x h 2^-261 (tools/gen_nadic_asm.py's mul_short_reg: rows = h's KS limbs,
 # digit 1 of the multiplier 0, KS quotient digits) over a lane group: the multiplier rows are
 # LDS rows HROW .. HROW + KS - 1 of the ciphertext's column (every lane of the group reads the
 # same word: a broadcast, one row ahead, as the general product's rows), B = the lane's slice of
