@@ -1561,6 +1561,51 @@ def jl_product(cts: torch.Tensor, biprime: int) -> torch.Tensor:
     return out
 
 
+def _on_current_stream(t: torch.Tensor) -> torch.Tensor:
+    """A fold's operand made on another stream (an upload on a copy stream): held by the allocator until the
+    current stream's work on it is done.  The caller orders the streams (wait_stream / wait_event)."""
+    if t.is_cuda:
+        t.record_stream(torch.cuda.current_stream(t.device))
+    return t
+
+
+def jl_fold(acc: torch.Tensor, rows: torch.Tensor, biprime: int, seed_ops: int = 0) -> torch.Tensor:
+    """Streaming product (fbm_jl_fold): acc[c] <- acc[c] * prod_j rows[j][c] mod N^2 in place, on the current
+    stream.  acc: int32 [n_ct, 64], contiguous; rows: int32 [n_ct, 64] or [k, n_ct, 64].  seed_ops > 0 starts
+    the accumulator (its contents ignored) for seed_ops rows in total: once that many have been folded in, acc
+    is jl_product's canonical product of them, bit for bit; seed_ops = 0 continues it."""
+    if rows.dim() == 2:
+        rows = rows[None]
+    k, n_ct, _ = rows.shape
+    if acc.dtype != torch.int32 or rows.dtype != torch.int32 or tuple(acc.shape) != (n_ct, 64) or \
+            rows.shape[2] != 64 or not acc.is_contiguous() or acc.device != rows.device:
+        raise ValueError("jl_fold takes a contiguous int32 [n_ct, 64] accumulator and int32 [k, n_ct, 64] rows "
+                         "on its device")
+    bp = _biprime_limbs(biprime)
+    if n_ct == 0 and k >= 1:
+        return acc
+    lib = N.load()
+    rows = _on_current_stream(rows.contiguous())
+    ws = torch.empty(int(lib.fbm_jl_aggregate_workspace(1)), dtype=torch.uint8, device=acc.device)
+    _call(lib.fbm_jl_fold, _ptr(acc), _ptr(rows), k, n_ct, _np_ptr(bp), int(seed_ops), _ptr(ws), _stream())
+    return acc
+
+
+def lom_fold(acc: torch.Tensor, Y: torch.Tensor, first: bool) -> torch.Tensor:
+    """Streaming column sum (fbm_lom_fold): acc[i] <- (0 if first else acc[i]) + sum_j Y[j][i] mod 2^64 in
+    place, on the current stream.  acc: int64 [n], contiguous (any slice of a larger buffer); Y: int64 [n] or
+    [k, n]."""
+    if Y.dim() == 1:
+        Y = Y[None]
+    k, n = Y.shape
+    if acc.dtype != torch.int64 or Y.dtype != torch.int64 or tuple(acc.shape) != (n,) or \
+            not acc.is_contiguous() or acc.device != Y.device:
+        raise ValueError("lom_fold takes a contiguous int64 [n] accumulator and int64 [k, n] rows on its device")
+    Y = _on_current_stream(Y.contiguous())
+    _call(N.load().fbm_lom_fold, _ptr(acc), _ptr(Y), k, n, 1 if first else 0, _stream())
+    return acc
+
+
 def jl_decrypt(cts: torch.Tensor, biprime: int, key: int, tau: int, ct_offset: int = 0) -> torch.Tensor:
     """ServerKey.decrypt (delta = 1) of the product of P ciphertext rows: int32 [P, n_ct, 64] ->
     x = ((prod * H(t_k)^key mod N^2) - 1) // N mod N as int32 [n_ct, 32] limbs."""

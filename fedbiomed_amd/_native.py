@@ -129,6 +129,9 @@ SIGNATURES = {
     "fbm_ves_unpack": (c_int, [c_vp, c_u64, c_int, c_int, c_int, c_u64, c_int, c_vp, c_vp]),
     "fbm_jl_product": (c_int, [c_vp, c_int, c_u64, c_vp, c_vp, c_vp, c_vp]),
     "fbm_jl_decrypt": (c_int, [c_vp, c_int, c_u64, c_vp, c_vp, c_int, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp]),
+    # streaming aggregation (additions to ABI 7): in-place folds of one party's rows, or several
+    "fbm_jl_fold": (c_int, [c_vp, c_vp, c_int, c_u64, c_vp, c_int, c_vp, c_vp]),
+    "fbm_lom_fold": (c_int, [c_vp, c_vp, c_int, c_u64, c_int, c_vp]),
     "fbm_jl_powmod": (c_int, [c_vp, c_vp, c_u64, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "fbm_jl_decrypt_with": (c_int, [c_vp, c_int, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "fbm_int_ops": (c_int, [c_vp, c_u64, c_u64, c_int, c_vp, c_vp, c_vp]),

@@ -1102,6 +1102,49 @@ int fbm_jl_product(const uint32_t* cts, int n_parties, uint64_t n_ct, const uint
   return timed("jl_prod", s, [&] { return launch_jl_prod(cts, n_parties, n_ct, jp, w.cst, nullptr, out, s); });
 }
 
+// the streaming product: acc <- acc * prod_j rows[j] mod N^2 in place (jl_fold_kernel; generic: jl_gen_fold_kernel)
+int fbm_jl_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, const uint32_t* biprime, int seed_ops,
+                void* workspace, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = jl_agg_checks(k, n_ct, biprime, 1))) return rc;
+  if (seed_ops < 0 || (seed_ops > 0 && k > seed_ops)) {
+    set_error("fbm_jl_fold: %d rows into an accumulator seeded for %d", k, seed_ops);
+    return FBM_E_ARG;
+  }
+  if (n_ct == 0) return FBM_OK;
+  if (!acc || !rows || !workspace) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  const JlAggWs w = agg_ws(workspace, 1);  // (ops and cst only: their place does not depend on n_ct)
+  if (jl_generic(biprime)) {
+    GenCtx g;
+    if ((rc = build_gen_ctx(biprime, nullptr, 0, g)) || (rc = launch_jl_gen_setup(g, w.cst, s))) return rc;
+    return timed("jl_gen_fold", s, [&] { return launch_jl_gen_fold(acc, rows, k, n_ct, w.cst, seed_ops > 0, s); });
+  }
+  JlParams jp;
+  if ((rc = build_jl_params(biprime, 1, 1, nullptr, 0, jp))) return rc;
+  JlSched none;
+  memset(&none, 0, sizeof(none));
+  if ((rc = timed("jl_setup", s, [&] { return launch_jl_setup(jp, none, w.ops, w.cst, s); }))) return rc;
+  if (seed_ops > 0) {  // R^seed_ops: every folded row drops one R
+    JlRk r;
+    jl_rk_for(jp.N32, seed_ops - 1, r);
+    if ((rc = timed("jl_rk", s, [&] { return launch_jl_rk(r, w.cst, s); }))) return rc;
+  }
+  return timed("jl_fold", s, [&] { return launch_jl_fold(acc, rows, k, n_ct, jp, w.cst, seed_ops > 0, s); });
+}
+
+int fbm_lom_fold(uint64_t* acc, const uint64_t* y, int k, uint64_t n, int first, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (k < 1 || (n > 0 && (!acc || !y))) {
+    set_error("invalid fold arguments (k=%d)", k);
+    return FBM_E_ARG;
+  }
+  return timed("lom_fold", s, [&] { return launch_lom_fold(acc, y, k, n, first, s); });
+}
+
 int fbm_jl_decrypt(const uint32_t* cts, int n_parties, uint64_t n_ct, const uint32_t* biprime, const uint32_t* key,
                    int key_negative, const uint32_t* tau, uint64_t ct_offset, uint32_t* x, void* workspace, uint32_t* stats,
                    void* stream) {

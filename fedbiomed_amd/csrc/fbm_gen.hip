@@ -397,6 +397,42 @@ __global__ void __launch_bounds__(GEN_W) jl_gen_combine_kernel(const uint32_t* _
   if (err && stats) atomicOr(stats + FBM_STAT_ERRFLAGS, err);
 }
 
+// the streaming product's generic form (fbm_jl_fold with an even N or N = 1): acc <- acc * prod_j rows[j]
+// mod M in place, acc starting from 1 mod M when seed (no R-power bookkeeping: Barrett products).  The error flags
+// of g_reduce_row / g_modmul (Barrett's correction count, FBM_ERR_ITER_CAP) are dropped: fbm_jl_fold has no status
+// words, as fbm_jl_product's generic path, which passes jl_gen_combine_kernel no stats either.
+__global__ void __launch_bounds__(GEN_W) jl_gen_fold_kernel(uint32_t* __restrict__ acc,
+                                                            const uint32_t* __restrict__ rows, int k, uint64_t n_ct,
+                                                            const GenCtx* __restrict__ g, int seed) {
+  __shared__ uint32_t lds[GEN_WORDS * GEN_W];
+  const uint64_t ct = (uint64_t)blockIdx.x * GEN_W + threadIdx.x;
+  if (ct >= n_ct) return;
+  const Col base{lds + threadIdx.x};
+  const Col HB = base.at(GEN_HB), AC = base.at(GEN_AC), T = base.at(GEN_T), Q = base.at(GEN_Q);
+  const int kM = g->kM;
+  const Glb M{g->M}, muM{g->muM};
+  uint32_t* arow = acc + ct * 64;
+  if (seed) {
+    g_zero(AC, kM + 1);
+    AC[0] = (kM == 1 && M[0] == 1u) ? 0u : 1u;  // 1 mod 1 = 0
+  } else {
+    g_reduce_row(arow, 64, kM, M, muM, T, Q, AC);
+  }
+  for (int u = 0; u < k; ++u) {
+    g_reduce_row(rows + ((uint64_t)u * n_ct + ct) * 64, 64, kM, M, muM, T, Q, HB);
+    g_modmul(AC, HB, kM, M, muM, T, Q);
+  }
+  g_store_row(arow, AC, kM, 64);
+}
+
+int launch_jl_gen_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, const uint32_t* cst, int seed,
+                       hipStream_t s) {
+  if (n_ct == 0) return FBM_OK;
+  hipLaunchKernelGGL(jl_gen_fold_kernel, dim3((unsigned)((n_ct + GEN_W - 1) / GEN_W)), dim3(GEN_W), 0, s, acc, rows, k,
+                     n_ct, (const GenCtx*)cst, seed);
+  return check_launch("jl_gen_fold_kernel");
+}
+
 __global__ void jl_gen_setup_kernel(GenCtx g, uint32_t* __restrict__ dst) {
   const uint32_t* src = reinterpret_cast<const uint32_t*>(&g);
   for (int i = threadIdx.x; i < (int)(sizeof(GenCtx) / 4); i += blockDim.x) dst[i] = src[i];

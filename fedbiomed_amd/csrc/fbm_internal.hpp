@@ -57,6 +57,8 @@ int launch_prf_key(const LomPeers& peers, uint32_t* seed_out, hipStream_t s);
 int lom_aggregate_kernel_name(int n_parties, uint64_t n, const void* y, char* buf, int len);
 int launch_lom_aggregate(const uint64_t* y, int n_parties, uint64_t n, uint64_t total_weight, double neg_c,
                          double step, void* out, int out_dtype, uint64_t* sums, uint32_t* stats, hipStream_t s);
+// acc[i] = (first ? 0 : acc[i]) + sum_j y[j][i] mod 2^64 in place (y [k][n])
+int launch_lom_fold(uint64_t* acc, const uint64_t* y, int k, uint64_t n, int first, hipStream_t s);
 
 // ---- Joye-Libert -------------------------------------------------------------------
 // exponent schedule (host-computed sliding window, uniform across lanes)
@@ -281,6 +283,10 @@ int launch_jl_encf(const uint32_t* pt, uint64_t n_ct, const JlParams& jp, const 
                    const uint32_t* factor, uint32_t* out, hipStream_t s);
 int launch_jl_prod(const uint32_t* cts, int n_parties, uint64_t n_ct, const JlParams& jp, const uint32_t* cst,
                    const uint32_t* factor, uint32_t* xout, hipStream_t s);
+// acc_k <- acc_k * prod_j rows[j][k] mod N^2 in place (rows [k][n_ct][64]); seed: start from cst[FBM_CST_RK]
+// (R^s mod N^2, s = the rows the accumulator takes in total) instead of acc's contents
+int launch_jl_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, const JlParams& jp, const uint32_t* cst,
+                   int seed, hipStream_t s);
 #define FBM_EXP_DEC 1        // jl_exp mode bits: plain power (no nude product)
 #define FBM_EXP_OUT_NADIC 4  // out rows are the result's N-adic digits (v mod N, v div N)
 #define FBM_EXP_PERCALL 8    // (one-lane engine, short path) the per-product chain loop instead of the chain body
@@ -322,6 +328,9 @@ int launch_jl_gen_exp(const uint32_t* H, const uint32_t* pt, int negative, uint6
 // v = prod_u cts[u] (* factor) mod N^2 -> out (FBM_GEN_PRODUCT) or ((v - 1) // N) mod N (FBM_GEN_DECRYPT)
 int launch_jl_gen_combine(const uint32_t* cts, int n_parties, uint64_t n_ct, const uint32_t* factor,
                           const uint32_t* cst, int mode, uint32_t* out, uint32_t* stats, hipStream_t s);
+// acc <- acc * prod_j rows[j] mod N^2 in place (rows [k][n_ct][64]); seed: acc starts from 1 mod N^2
+int launch_jl_gen_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, const uint32_t* cst, int seed,
+                       hipStream_t s);
 // the same per-ciphertext work on the host, one ciphertext (test hooks; cts: n_parties rows of 64)
 uint32_t host_gen_exp(const uint32_t* Hrow, const uint32_t* ptrow, int negative, const GenCtx& g, uint32_t* out);
 uint32_t host_gen_combine(const uint32_t* cts, int n_parties, const uint32_t* frow, const GenCtx& g, int mode,

@@ -1763,6 +1763,62 @@ __global__ void __launch_bounds__(FBM_BLOCK, 2) jl_prod_kernel(const uint32_t* _
 }
 
 // ------------------------------------------------------------------------------------
+// streaming product (fbm_jl_fold; EncryptedNumber sums, _jls.py:353-374, one party at a time):
+//   acc_k <- acc_k * prod_j rows[j][k] mod N^2, in place, one lane per ciphertext, built as jl_prod_kernel:
+// the running value in the lane's LDS column, each operand row read by fbm_mm_row, mont_csub and from28 at
+// the end; one LDS column per lane, two waves per SIMD, no scratch.
+//   seed != 0: a = cst[FBM_CST_RK] = R^s mod M (uniform; s = the number of rows the accumulator will have
+//              taken when it is read), acc's contents ignored
+//   seed == 0: a = acc's own row (canonical, below M: an earlier call's result)
+// Each row drops one R, so after s rows in total acc = prod c: the one-shot's product count (one per
+// operand, no Montgomery-form round trips); in between acc = R^(s - rows so far) prod c mod M, canonical.
+// Operands: a < 2M (lazy) or < M (reloaded), b < 2^2048, so a b < R M (R = 2^2072).
+// A lane past n_ct folds ciphertext n_ct - 1's operand rows (read-only) into a zero column and stores nothing
+// (it does not read acc: the owning lane may already have overwritten that row).
+// ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(FBM_BLOCK, 2) jl_fold_kernel(uint32_t* __restrict__ acc,
+                                                              const uint32_t* __restrict__ rows, int k,
+                                                              uint64_t n_ct, const uint32_t* __restrict__ cst,
+                                                              JlParams jp, int seed) {
+  __shared__ uint32_t lds_a[(FBM_NL + 1) * FBM_BLOCK];
+  const int tid = threadIdx.x;
+  uint32_t* lds = lds_a + tid;
+  const uint32_t aoff = lds_addr(lds);
+  const uint32_t* M = cst + FBM_CST_M;
+  const uint64_t ct_raw = (uint64_t)blockIdx.x * FBM_BLOCK + tid;
+  const bool valid = ct_raw < n_ct;  // no early return: every lane runs the products
+  const uint64_t ct = valid ? ct_raw : n_ct - 1;
+  if (seed) {
+    lds_store_uniform<FBM_NL>(lds, FBM_BLOCK, cst + FBM_CST_RK);
+  } else {
+    uint32_t w[64], a[FBM_NL];
+    if (valid) {
+      const uint4* src = reinterpret_cast<const uint4*>(acc + ct * 64);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const uint4 v = src[i];
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 64; ++i) w[i] = 0u;
+    }
+    to28<64, FBM_NL>(w, a);
+    lds_store_col(lds, FBM_BLOCK, a);
+  }
+#pragma unroll 1
+  for (int u = 0; u < k; ++u) fbm_mm_row(aoff, rows + ((uint64_t)u * n_ct + ct) * 64, M, jp.mc.mp);
+  uint32_t D[64];
+  {
+    uint32_t v[FBM_NL];
+    lds_load_col(lds, FBM_BLOCK, v);
+    mont_csub(v, jp.mc.M);
+    from28<FBM_NL, 64>(v, D);
+  }
+  if (valid) store_row64(acc + ct * 64, D);
+}
+
+// ------------------------------------------------------------------------------------
 // encrypt with its factor computed ahead (fbm_jl_encrypt_factor, UserKey.encrypt, _jls.py:473-505):
 //   c = (N pt + 1) F mod N^2,  F = H(t_k)^sk mod N^2 (jl_factor: the decryption factor's
 // kernels with the party's key, run before the plaintext exists), the exponentiation's encrypt
@@ -2550,6 +2606,13 @@ int launch_jl_prod(const uint32_t* cts, int n_parties, uint64_t n_ct, const JlPa
   hipLaunchKernelGGL(jl_prod_kernel, grid1(n_ct, FBM_BLOCK), dim3(FBM_BLOCK), 0, s, cts, n_parties, n_ct, cst, jp,
                      factor, xout);
   return check_launch("jl_prod_kernel");
+}
+
+int launch_jl_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, const JlParams& jp, const uint32_t* cst,
+                   int seed, hipStream_t s) {
+  if (n_ct == 0) return FBM_OK;
+  hipLaunchKernelGGL(jl_fold_kernel, grid1(n_ct, FBM_BLOCK), dim3(FBM_BLOCK), 0, s, acc, rows, k, n_ct, cst, jp, seed);
+  return check_launch("jl_fold_kernel");
 }
 
 __global__ void jl_rk_kernel(JlRk rk, uint32_t* __restrict__ cst) {

@@ -421,6 +421,58 @@ __global__ void __launch_bounds__(64 * W) lom_aggregate_ws_kernel(const uint64_t
   if (err && out) atomicOr(stats + FBM_STAT_ERRFLAGS, FBM_ERR_DEQUANT_RANGE);
 }
 
+// Streaming column sum (fbm_lom_fold; LOM.aggregate's sum, _lom.py:177-192, one party at a time):
+//   acc[i] = (first ? 0 : acc[i]) + sum_j y[j][i]  mod 2^64, in place.
+// A workgroup owns one tile of 256 * 2 elements, a thread two neighbouring ones: a full tile of 16-byte
+// aligned rows takes one 16-byte load per row (eight rows' loads issued before their sums; the rows are read
+// once: nontemporal) and one 16-byte load and store of acc; the last tile, an odd n (rows then start on odd
+// 8-byte boundaries) and a misaligned acc or y take bounds-checked element accesses, as the ws kernel's tail.
+// HBM-bound: 8 n (k + 1) algorithmic bytes for a first call, 8 n (k + 2) afterwards.  Any k >= 1.
+#define FBM_FOLD_TILE 512
+#define FBM_FOLD_ROWS 8
+__global__ void __launch_bounds__(256) lom_fold_kernel(uint64_t* __restrict__ acc, const uint64_t* __restrict__ y,
+                                                       int k, uint64_t n, int first, int vec) {
+  const uint64_t base = (uint64_t)blockIdx.x * FBM_FOLD_TILE;
+  const uint64_t i = base + 2ull * threadIdx.x;
+  if (vec && base + FBM_FOLD_TILE <= n) {
+    typedef uint64_t v2 __attribute__((ext_vector_type(2)));
+    v2* a = reinterpret_cast<v2*>(acc + i);
+    v2 s = first ? v2{0, 0} : *a;
+    int u = 0;
+    for (; u + FBM_FOLD_ROWS <= k; u += FBM_FOLD_ROWS) {
+      v2 v[FBM_FOLD_ROWS];
+#pragma unroll
+      for (int r = 0; r < FBM_FOLD_ROWS; ++r)
+        v[r] = __builtin_nontemporal_load(reinterpret_cast<const v2*>(y + (uint64_t)(u + r) * n + i));
+#pragma unroll
+      for (int r = 0; r < FBM_FOLD_ROWS; ++r) s += v[r];
+    }
+    for (; u < k; ++u) s += __builtin_nontemporal_load(reinterpret_cast<const v2*>(y + (uint64_t)u * n + i));
+    *a = s;
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    if (i + e >= n) break;
+    uint64_t s = first ? 0ull : acc[i + e];
+    for (int u = 0; u < k; ++u) s += __builtin_nontemporal_load(y + (uint64_t)u * n + i + e);
+    acc[i + e] = s;
+  }
+}
+
+int launch_lom_fold(uint64_t* acc, const uint64_t* y, int k, uint64_t n, int first, hipStream_t s) {
+  if (n == 0) return FBM_OK;
+  const uint64_t g = (n + FBM_FOLD_TILE - 1) / FBM_FOLD_TILE;
+  if (g > 0x7fffffffull) {
+    set_error("fbm_lom_fold: %llu elements exceed one launch's grid", (unsigned long long)n);
+    return FBM_E_UNSUPPORTED;
+  }
+  // 16-byte accesses: every row and acc on a 16-byte boundary (rows start n * 8 bytes apart)
+  const int vec = (n % 2) == 0 && (reinterpret_cast<uintptr_t>(y) % 16) == 0 && (reinterpret_cast<uintptr_t>(acc) % 16) == 0;
+  hipLaunchKernelGGL(lom_fold_kernel, dim3((unsigned)g), dim3(256), 0, s, acc, y, k, n, first, vec);
+  return check_launch("lom_fold_kernel");
+}
+
 int launch_lom_protect(const void* x, int x_dtype, uint64_t n, const QuantParams& qp, uint64_t weight,
                        const LomPeers& peers, uint64_t* y, uint32_t* stats, hipStream_t s) {
   if (n == 0) return FBM_OK;

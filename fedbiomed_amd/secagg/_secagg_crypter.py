@@ -105,8 +105,377 @@ def _scrub_prep(prep, keys) -> None:
             t.zero_()
 
 
+def _ended() -> FedbiomedSecaggCrypterError:
+    return FedbiomedSecaggCrypterError(
+        f"{ErrorNumbers.FB624.value}: this streaming aggregation has ended (finish or abort was called); "
+        f"begin_aggregate starts a new one")
+
+
+def _check_int_list(node_params) -> None:
+    """One party's share of _check_int_lists, with its messages."""
+    if not isinstance(node_params, list):
+        raise FedbiomedSecaggCrypterError(
+            f"{ErrorNumbers.FB624.value}: The parameters to aggregate should be a "
+            f"list containing list of parameters")
+    if not D.all_ints(node_params):
+        raise FedbiomedSecaggCrypterError(
+            f"{ErrorNumbers.FB624.value}: Invalid parameter type. The parameters "
+            f"should be of type of integers.")
+
+
+class JlStreamAggregation:
+    """Extension (not in the reference): `SecaggCrypter.aggregate` one reply at a time.
+
+        agg = crypter.begin_aggregate(current_round, num_nodes, key, biprime, total_sample_size, ...)
+        agg.add(node_params)      # as each node's reply arrives
+        result = agg.finish()     # == crypter.aggregate(current_round, num_nodes, [all of them], ...)
+
+    The product of the ciphertexts modulo N^2 is associative and commutative, so the device holds one running
+    accumulator ([n_ct, 64] limbs) plus the reply in hand instead of all parties' rows, and each reply's host
+    conversion, upload and product run while the researcher waits for the next one.  The first `add` fixes the
+    vector's size and obtains the decryption factor H(t_k)^key -- `prepare_aggregate`'s if one matches, else
+    issued on a side stream so that it runs while later replies arrive.  `finish` is the one-shot's last step
+    (factor product, division by N, decode, average, dequantise) on the accumulator; its results equal the
+    one-shot's bit for bit, for the replies in any order.
+
+    Errors are the one-shot's, raised where they can first be known: a reply's type checks and the key's at
+    `add`; the reply count, the non-empty check, a bad total_sample_size and the device's status words at
+    `finish`.  The reference zips the parties' lists, so the shortest reply fixes the length: a shorter `add`
+    truncates the accumulator, a longer one has its tail ignored, an empty one makes `finish` return [].
+    `finish` and `abort` zero a factor this object issued before its memory returns to the allocator; after
+    either, every method raises FedbiomedSecaggCrypterError.
+
+    All state is this object's (nothing class-wide): two aggregations on two threads are independent.  One
+    object is used by one thread at a time."""
+
+    def __init__(self, crypter, current_round, num_nodes, key, biprime, total_sample_size, clipping_range,
+                 num_expected_params, target_range):
+        self._crypter = crypter
+        self._round, self._num_nodes, self._key, self._biprime = current_round, num_nodes, key, biprime
+        self._total, self._clip, self._n_exp, self._target = total_sample_size, clipping_range, num_expected_params, \
+            target_range
+        self._adds = 0
+        self._n_ct = None  # the shortest reply so far
+        self._acc = None  # int32 [n_ct of the first non-empty reply, 64]
+        self._folded = 0
+        self._stripes, self._factors, self._pool = None, None, None
+        self._own = None  # {"factor": tensor, "event": its side stream's} of a factor issued here
+        self._checks = []
+        self._start_error = None  # what kept the factor from being issued: finish raises it, in the one-shot's place
+        self._copy = None
+        self._ended = False
+
+    @property
+    def total_sample_size(self):
+        """Read by finish only: a caller that learns it with the last reply assigns it before finish()."""
+        return self._total
+
+    @total_sample_size.setter
+    def total_sample_size(self, value) -> None:
+        self._total = value
+
+    # ---- replies ---------------------------------------------------------------------------------
+    def add(self, node_params) -> None:
+        """One node's reply: its List[int] (the reference's form), a `wire.EncryptedParams`, or its
+        ciphertexts as an int32 [n_ct, 64] device tensor."""
+        if self._ended:
+            raise _ended()
+        is_tensor = isinstance(node_params, torch.Tensor)
+        if is_tensor:
+            if node_params.dtype != torch.int32 or node_params.dim() != 2 or node_params.shape[1] != 64 or \
+                    not node_params.is_cuda:
+                raise FedbiomedSecaggCrypterError(
+                    f"{ErrorNumbers.FB624.value}: a tensor reply is an int32 [n_ct, 64] device tensor")
+        else:
+            _check_int_list(node_params)
+        if not isinstance(self._key, int):
+            raise TypeError("The key should be type of integer")
+        n = node_params.shape[0] if is_tensor else len(node_params)
+        self._adds += 1
+        self._n_ct = n if self._n_ct is None else min(self._n_ct, n)
+        if self._n_ct == 0 or self._start_error is not None or not isinstance(self._num_nodes, int) or \
+                self._adds > self._num_nodes:
+            return  # finish returns [] or raises: nothing to compute
+        dev = node_params.device if is_tensor else D.device()
+        with torch.cuda.device(dev):
+            if self._acc is None and not self._begin(self._n_ct, dev):
+                return
+            m = self._n_ct
+            rows = node_params[:m] if is_tensor else self._upload(node_params, m, dev)
+            chunk = D.jl_chunk_ct()
+            seed = self._num_nodes if self._folded == 0 else 0
+            for k0 in range(0, m, chunk):  # (as jl_aggregate loops: at most FBM_JL_MAX_CT per library call)
+                k1 = min(m, k0 + chunk)
+                D.jl_fold(self._acc[k0:k1], rows[k0:k1], self._biprime, seed_ops=seed)
+            self._folded += 1
+            if self._folded == 1 and not is_tensor and self._pool is None:
+                # a list caller's finish() returns a list: its float objects made now, beside the factor's
+                # exponentiations, their values written in place by finish (prepare_aggregate's pool, made here)
+                try:
+                    cr = D.jl_slot(self._target or SAParameters.TARGET_RANGE, self._num_nodes)[1]
+                    self._pool = D.float_pool(max(0, min(int(self._n_exp), m * cr)))
+                except Exception:  # noqa: BLE001 -- finish makes the list itself
+                    self._pool = None
+
+    def _begin(self, n_ct, dev) -> bool:
+        """The first non-empty reply: the factor (prepare_aggregate's, or issued on a side stream), then the
+        accumulator."""
+        c = self._crypter
+        try:
+            with D.capture_checks() as taken:  # (the prepared factors' status words: checked by finish)
+                prep = c._take_prepared(self._round, self._num_nodes, self._key, self._biprime, self._target, n_ct,
+                                        dev)
+            if prep is not None:
+                self._stripes, self._factors, self._pool = prep[0], list(prep[1]), prep[2]
+                self._checks = taken.pending
+            else:
+                main = torch.cuda.current_stream(dev)
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(main)
+                with torch.cuda.stream(side), D.capture_checks() as checks:
+                    factor = c.decrypt_factor_tensor(self._round, n_ct, self._key, self._biprime)
+                ev = torch.cuda.Event()
+                ev.record(side)
+                self._own = {"factor": factor, "event": ev}
+                self._checks = checks.pending
+                self._stripes, self._factors = [(0, n_ct)], [factor]
+        except Exception as e:  # noqa: BLE001 -- kept: finish raises it, in the one-shot's order
+            self._start_error = e
+            return False
+        self._acc = torch.empty((n_ct, 64), dtype=torch.int32, device=dev)
+        return True
+
+    def _upload(self, lst, m, dev) -> torch.Tensor:
+        """The first m ciphertexts of one party's list -> a pinned buffer (host threads) -> the device, on a
+        copy stream the current stream then waits for.  Both buffers go back to their allocators once the
+        copy and the fold that follows have consumed them."""
+        staged = D.host_empty((1, m, 64), torch.int32)
+        limbs = staged.numpy().view(np.uint32)
+        packed = wire.packed_rows([lst], "jl", m)
+        if packed is not None:
+            limbs[:] = packed
+        else:
+            D.convert_stripe([lst], 0, m, self._biprime * self._biprime, limbs)
+        if self._copy is None:
+            self._copy = torch.cuda.Stream(device=dev)
+        main = torch.cuda.current_stream(dev)
+        with torch.cuda.stream(self._copy):
+            rows = staged[0].to(dev, non_blocking=True)
+        main.wait_stream(self._copy)
+        return rows  # (jl_fold records the current stream on it)
+
+    # ---- the end ---------------------------------------------------------------------------------
+    def _scrub(self) -> None:
+        own, self._own = self._own, None
+        _scrub_prep(own, ("factor",))
+        self._acc = self._factors = self._stripes = self._pool = None
+        self._ended = True
+
+    def abort(self) -> None:
+        """Drops the aggregation: the accumulator freed, a factor issued here zeroed first."""
+        if self._ended:
+            raise _ended()
+        self._scrub()
+
+    def _finish(self, as_list: bool, out_dtype=None, out=None):
+        if self._ended:
+            raise _ended()
+        try:
+            if self._adds != self._num_nodes:
+                raise FedbiomedSecaggCrypterError(
+                    f"{ErrorNumbers.FB624.value}: Num of parameters that are received from nodes "
+                    f"does not match the number of nodes has been set for the encrypter. There might "
+                    f"be some nodes did not answered to training request or num of clients of "
+                    "`ParameterEncrypter` has not been set properly before train request.")
+            if not isinstance(self._key, int):
+                raise TypeError("The key should be type of integer")
+            if self._adds == 0:
+                raise FedbiomedSecaggCrypterError(
+                    f"{ErrorNumbers.FB624.value}: The aggregation of encrypted parameters "
+                    f"is not successful: list_y_u_tau should be a non-empty list.")
+            if self._n_ct == 0:
+                return [] if as_list else None
+            target = self._target or SAParameters.TARGET_RANGE
+            if self._start_error is not None:  # (after the total's checks, as the one-shot raises them first)
+                self._check_total()
+                raise self._start_error
+            dev = self._acc.device
+            with torch.cuda.device(dev), D.deferred_checks():
+                res = self._combine(target, dev, as_list, out_dtype, out)
+            return res
+        finally:
+            self._scrub()
+
+    def _check_total(self) -> None:
+        """jl_aggregate's checks of total_sample_size, with its errors."""
+        if self._total == 0:
+            raise ZeroDivisionError("division by zero")
+        if self._total < 0 or self._total > D.U64_MAX:
+            raise FedbiomedSecaggCrypterError(
+                f"{ErrorNumbers.FB624.value}: total_sample_size must be in [1, 2^64) for the device path")
+
+    def _combine(self, target, dev, as_list, out_dtype, out):
+        n_ct = self._n_ct
+        self._check_total()  # (ahead of the destination's checks, as in jl_aggregate)
+        slot = D.jl_slot(target, self._num_nodes)
+        cr = slot[1]
+        n_exp = int(self._n_exp)
+        stripes = [(c0, min(c1, n_ct)) for c0, c1 in self._stripes if c0 < n_ct]
+        n_outs = [max(0, min(n_exp - c0 * cr, (c1 - c0) * cr)) for c0, c1 in stripes]
+        dest, _ = D._out_tensor(sum(n_outs), dev, out_dtype, out)
+        main = torch.cuda.current_stream(dev)
+        if self._own is not None:
+            main.wait_event(self._own["event"])
+            self._own["factor"].record_stream(main)
+        D.adopt_checks(self._checks)
+        self._checks = []
+        off = 0
+        for (c0, c1), f, n_k in zip(stripes, self._factors, n_outs):
+            D.jl_aggregate(self._acc[None, c0:c1], self._biprime, self._key, self._round, n_k, self._total,
+                           clip=self._clip, target=target, slot=slot, ct_offset=c0, factor=f[:c1 - c0],
+                           out=dest[off:off + n_k])
+            off += n_k
+        if not as_list:
+            return dest
+        vals = D.to_host(dest).numpy()
+        if self._pool is not None and len(self._pool) == vals.shape[0]:
+            D.f64_into_list(self._pool, 0, vals)
+            return self._pool
+        return vals.tolist()
+
+    def finish(self) -> List[float]:
+        """The averaged parameters: exactly `aggregate`'s list for the same replies."""
+        return self._finish(True)
+
+    def finish_tensor(self, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None):
+        """The averaged parameters in HBM: exactly `aggregate_tensor`'s tensor for the stacked replies, with its
+        `out_dtype` / `out` rules (None when a reply was empty)."""
+        return self._finish(False, out_dtype, out)
+
+
+class LomStreamAggregation:
+    """Extension (not in the reference): `SecaggLomCrypter.aggregate` one reply at a time -- the sum modulo
+    2^64 kept in one device accumulator ([n] uint64) instead of the [P, n] block.  `add` takes a List[int], a
+    `wire.EncryptedParams` or an int64 [n] device tensor; its type and range errors are the one-shot's,
+    raised at `add`; replies of unequal lengths (the one-shot's numpy conversion refuses them), a bad
+    total_sample_size and the device's status words are raised at `finish`.  No reply, or empty ones, make
+    `finish` return [].  After `finish` or `abort` every method raises FedbiomedSecaggCrypterError.  All state
+    is this object's; one object is used by one thread at a time."""
+
+    def __init__(self, crypter, total_sample_size, clipping_range, target_range):
+        self._crypter = crypter
+        self._total, self._clip, self._target = total_sample_size, clipping_range, target_range
+        self._n = None
+        self._acc = None
+        self._pool = None
+        self._ragged = False
+        self._copy = None
+        self._ended = False
+
+    @property
+    def total_sample_size(self):
+        """Read by finish only: a caller that learns it with the last reply assigns it before finish()."""
+        return self._total
+
+    @total_sample_size.setter
+    def total_sample_size(self, value) -> None:
+        self._total = value
+
+    def add(self, node_params) -> None:
+        if self._ended:
+            raise _ended()
+        is_tensor = isinstance(node_params, torch.Tensor)
+        if is_tensor:
+            if node_params.dtype != torch.int64 or node_params.dim() != 1 or not node_params.is_cuda:
+                raise FedbiomedSecaggCrypterError(
+                    f"{ErrorNumbers.FB624.value}: a tensor reply is an int64 [n] device tensor")
+            row, pinned = node_params, False
+        else:
+            _check_int_list(node_params)
+            packed = wire.packed_rows([node_params], "lom")
+            try:
+                row, pinned = (torch.from_numpy(packed.view(np.int64)), False) if packed is not None else \
+                    D.u64_to_host([node_params])
+            except (ValueError, TypeError) as e:
+                raise FedbiomedSecaggCrypterError(
+                    f"{ErrorNumbers.FB624.value}: The aggregation of encrypted parameters "
+                    f"is not successful: {e}") from e
+            row = row.reshape(-1)
+        n = row.shape[0]
+        if self._n is None:
+            self._n = n
+        elif n != self._n:
+            self._ragged = True
+        if self._ragged or n == 0:
+            return
+        dev = row.device if is_tensor else D.device()
+        with torch.cuda.device(dev):
+            if not is_tensor:
+                if self._copy is None:
+                    self._copy = torch.cuda.Stream(device=dev)
+                with torch.cuda.stream(self._copy):
+                    row = row.to(dev, non_blocking=pinned)
+                torch.cuda.current_stream(dev).wait_stream(self._copy)
+            first = self._acc is None
+            if first:
+                self._acc = torch.empty(n, dtype=torch.int64, device=dev)
+            D.lom_fold(self._acc, row, first)
+            if first and not is_tensor and getattr(self._crypter, "_lom_agg_pool", None) is None:
+                self._pool = D.float_pool(n)  # a list caller's output floats, made while replies still arrive
+
+    def abort(self) -> None:
+        if self._ended:
+            raise _ended()
+        self._acc, self._pool, self._ended = None, None, True
+
+    def _finish(self, as_list: bool, out_dtype=None, out=None):
+        if self._ended:
+            raise _ended()
+        try:
+            if self._ragged:
+                raise FedbiomedSecaggCrypterError(
+                    f"{ErrorNumbers.FB624.value}: The aggregation of encrypted parameters "
+                    f"is not successful: the nodes' replies differ in length")
+            if self._acc is None:
+                return [] if as_list else None
+            dev = self._acc.device
+            with torch.cuda.device(dev), D.deferred_checks():
+                dest, _ = D.lom_aggregate(self._acc[None], self._total, self._clip,
+                                          self._target or SAParameters.TARGET_RANGE, out_dtype=out_dtype, out=out)
+                vals = D.to_host(dest).numpy() if as_list else None
+            if not as_list:
+                return dest
+            pool = getattr(self._crypter, "_lom_agg_pool", None)
+            if pool is not None and len(pool) == vals.shape[0]:  # prepare_aggregate's floats, written in place
+                self._crypter._lom_agg_pool = None
+            else:
+                pool = self._pool  # (the first add's)
+            if pool is not None and len(pool) == vals.shape[0]:
+                D.f64_into_list(pool, 0, vals)
+                return pool
+            return vals.tolist()
+        finally:
+            self._acc, self._pool, self._ended = None, None, True
+
+    def finish(self) -> List[float]:
+        """The averaged parameters: exactly `aggregate`'s list for the same replies."""
+        return self._finish(True)
+
+    def finish_tensor(self, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None):
+        """Exactly `aggregate_tensor`'s tensor for the stacked replies (None when there was nothing to sum)."""
+        return self._finish(False, out_dtype, out)
+
+
 class SecaggCrypter:
     """Joye-Libert secure aggregation (encrypt on nodes, aggregate on the researcher)."""
+
+    def begin_aggregate(self, current_round: int, num_nodes: int, key: int, biprime: int, total_sample_size: int,
+                        clipping_range: Union[int, None] = None, num_expected_params: int = 1,
+                        target_range: Optional[int] = None) -> JlStreamAggregation:
+        """Extension (not in the reference): `aggregate` as a stream -- `add` each node's reply as it arrives,
+        then `finish()` (List[float]) or `finish_tensor()`; see JlStreamAggregation.  Nothing runs here."""
+        return JlStreamAggregation(self, current_round, num_nodes, key, biprime, total_sample_size, clipping_range,
+                                   num_expected_params, target_range)
 
     # prepare_encrypt's factor, held by the class: the node makes a SecaggCrypter per encrypt call
     # (`node/secagg/_secagg_round.py:139-157`), so the call that takes it is another instance's
@@ -636,6 +1005,12 @@ class SecaggLomCrypter(SecaggCrypter):
             return None
         self._lom_enc_prep = None
         return prep["pool"]
+
+    def begin_aggregate(self, total_sample_size: int, clipping_range: Union[int, None] = None,
+                        target_range: Optional[int] = None) -> LomStreamAggregation:
+        """Extension (not in the reference): `aggregate` as a stream -- `add` each node's reply as it arrives,
+        then `finish()` (List[float]) or `finish_tensor()`; see LomStreamAggregation.  Nothing runs here."""
+        return LomStreamAggregation(self, total_sample_size, clipping_range, target_range)
 
     def __init__(self, nonce: Optional[str] = None):
         if nonce:

@@ -294,6 +294,39 @@ int fbm_jl_decrypt(const uint32_t* cts, int n_parties, uint64_t n_ct, const uint
                    int key_negative, const uint32_t* tau, uint64_t ct_offset, uint32_t* x, void* workspace, uint32_t* stats,
                    void* stream);
 
+/* ---- streaming aggregation: fold each party's reply in as it arrives (additions, ABI still 7) ------
+ * The product mod N^2 and the sum mod 2^64 are associative and commutative, so an aggregate needs one
+ * running accumulator plus the reply in hand, not all parties' rows at once.  Both calls are stream-ordered
+ * and work in place on a device accumulator the caller owns.
+ *
+ * fbm_jl_fold: EncryptedNumber sums (_jls.py:353-374) one party, or several, at a time:
+ *     acc[c] <- acc[c] * prod_j rows[j][c] mod N^2,  c < n_ct
+ *   acc    device, n_ct x 64 limbs, read and overwritten in place
+ *   rows   device, k x n_ct x 64 limbs (party-major), each row any value below 2^2048 (as fbm_jl_product's)
+ *   seed_ops > 0: acc's contents are ignored; the accumulator is started so that once seed_ops rows in
+ *     total have been folded into it (this call's k included), acc holds their canonical product mod N^2
+ *     -- bit for bit fbm_jl_product's of the same rows, in any order and any grouping.  Until then acc's
+ *     contents are unspecified (but always canonical rows < N^2).  k > seed_ops is FBM_E_ARG.
+ *   seed_ops == 0: continues an accumulator started by an earlier call (same biprime).
+ *   workspace: fbm_jl_aggregate_workspace(n_ct) bytes suffice; only the call's constants at its start are
+ *     used, so fbm_jl_aggregate_workspace(1) bytes are enough for any n_ct.
+ *   The finish needs no entry point of its own: fbm_jl_aggregate[_factor][_as] (or fbm_jl_decrypt[_with])
+ *   with n_parties = 1 on the accumulator and the slot (es, cr) of the real party count.
+ *   No status words (as fbm_jl_product): the generic engine's internal iteration-cap flag is not reported.
+ *   Checks as fbm_jl_product's: k < 1 or a null biprime is FBM_E_ARG, n_ct > FBM_JL_MAX_CT
+ *   FBM_E_UNSUPPORTED, n_ct == 0 FBM_OK, then null acc / rows / workspace FBM_E_ARG.
+ *
+ * fbm_lom_fold: LOM.aggregate's sum (_lom.py:177-192) one party, or several, at a time:
+ *     acc[i] <- (first ? 0 : acc[i]) + sum_j y[j][i]  mod 2^64,  i < n
+ *   acc    device, n uint64 (8-byte aligned: any element offset of a larger buffer), in place;
+ *          first != 0: its contents are ignored
+ *   y      device, k x n uint64 (row-major, party-major), any k >= 1
+ *   The finish: fbm_lom_aggregate[_as] with n_parties = 1 on the accumulator.
+ *   k < 1 or (n > 0 and a null pointer) is FBM_E_ARG; n == 0 FBM_OK.                                  */
+int fbm_jl_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, const uint32_t* biprime,
+                int seed_ops, void* workspace, void* stream);
+int fbm_lom_fold(uint64_t* acc, const uint64_t* y, int k, uint64_t n, int first, void* stream);
+
 /* Keys whose PublicParam hashes with a callable other than FBM's FDH(2048, N^2).H (BaseKey._populate_tau,
  * _jls.py:451-467, calls it per t on the host; the exponentiations stay on the device):
  * fbm_jl_powmod: out[k] = (N*pt[k] + 1) * h[k]^key mod N^2 (UserKey.encrypt, _jls.py:473-505), or with
