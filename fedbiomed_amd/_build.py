@@ -6,7 +6,7 @@
                                             device routines, per-thread engine switches, the per-kernel
                                             event timer) -- for tests/ and bench.py
 
-Both link the SAME kernel objects (fbm_lom / fbm_jl / fbm_gen / fbm_ass) and the same host setup
+Both link the SAME kernel objects (fbm_lom / fbm_jl / fbm_gen / fbm_ass / fbm_wire) and the same host setup
 (fbm_setup.hip: per-modulus and per-key constants on fbm_bigint.hpp), compiled once; only the
 host-side C ABI (fbm_capi.hip) is compiled twice, the second time with -DFBM_TEST_HOOKS.  A linker
 version script made from each library's header(s) keeps every other symbol local.
@@ -30,7 +30,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "_lib", "libfbm_secagg.so")
 TEST_OUT = os.path.join(HERE, "_lib", "libfbm_secagg_test.so")
-KERNEL_SOURCES = ["fbm_lom.hip", "fbm_jl.hip", "fbm_gen.hip", "fbm_ass.hip"]
+KERNEL_SOURCES = ["fbm_lom.hip", "fbm_jl.hip", "fbm_gen.hip", "fbm_ass.hip", "fbm_wire.hip"]
 SETUP_SOURCE = "fbm_setup.hip"  # host only, no test hooks: compiled once, like the kernels
 CAPI_SOURCE = "fbm_capi.hip"
 SOURCES = KERNEL_SOURCES + [SETUP_SOURCE, CAPI_SOURCE]

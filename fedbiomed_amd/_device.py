@@ -1804,3 +1804,126 @@ def int128_to_ints(arr: np.ndarray) -> List[int]:
         w = (hi << 64) | lo
         out.append(w - 2**128 if w >> 127 else w)
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# the reference Serializer's update bytes (fbm_wire_*; fedbiomed/common/serializer.py:96-110, 140-149)
+# ------------------------------------------------------------------------------------------
+_WIRE_SCHEME = {"jl": N.WIRE_JL, "lom": N.WIRE_LOM}
+_WIRE_NAME = {v: k for k, v in _WIRE_SCHEME.items()}
+
+
+def wire_scan(data, min_items: int) -> Optional[list]:
+    """The host scanner (fbm_wire_scan) over a message: [(begin, end, n_items, scheme, checkpoints)] of the arrays
+    it recorded -- scheme "jl" / "lom", checkpoints a uint64 array --, or None where it gives up (the message
+    stays msgpack's).  No device call."""
+    lib = N.load()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    n = buf.size
+    n_arr, n_ck = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    # (tables sized for updates first; len entries always suffice)
+    for a_cap, c_cap in ((1024, n // 8 + 1024), (n // max(int(min_items), 1) + 1, n + 16)):
+        arrays = (N.WireArray * a_cap)()
+        ckpt = np.empty(c_cap, dtype=np.uint64)
+        rc = lib.fbm_wire_scan(_np_ptr(buf) if n else None, n, max(int(min_items), 1), ctypes.addressof(arrays), a_cap,
+                               ctypes.addressof(n_arr), _np_ptr(ckpt), c_cap, ctypes.addressof(n_ck))
+        if rc == N.FBM_E_RANGE:
+            continue
+        if rc == N.FBM_E_UNSUPPORTED:
+            return None
+        if rc != N.FBM_OK:
+            _raise(rc)
+        return [(int(a.begin), int(a.end), int(a.n_items), _WIRE_NAME[a.scheme],
+                 ckpt[a.ckpt_first:a.ckpt_first + a.ckpt_count]) for a in arrays[:n_arr.value]]
+    return None
+
+
+def _wire_rows(scheme: str, rows, dev) -> torch.Tensor:
+    """The scheme's rows as a contiguous device tensor: int32 [n, 64] (jl) or int64 [n] (lom)."""
+    if scheme not in _WIRE_SCHEME:
+        raise ValueError("scheme must be 'jl' or 'lom'")
+    if isinstance(rows, np.ndarray):
+        a = np.ascontiguousarray(rows)
+        a = a.view(np.int32).reshape(-1, 64) if scheme == "jl" else a.view(np.int64).reshape(-1)
+        host = host_empty(a.shape, torch.int32 if scheme == "jl" else torch.int64)
+        host.numpy()[...] = a
+        return host.to(dev, non_blocking=host.is_pinned())
+    want = torch.int32 if scheme == "jl" else torch.int64
+    if rows.dtype != want or (scheme == "jl" and (rows.dim() != 2 or rows.shape[1] != 64)) or \
+            (scheme == "lom" and rows.dim() != 1):
+        raise ValueError("wire_encode takes int32 [n, 64] rows (jl) or int64 [n] words (lom)")
+    return rows.contiguous()
+
+
+def wire_encode(scheme: str, rows, timing: Optional[dict] = None) -> bytes:
+    """The bytes the reference's packb writes for the update whose device layout is `rows` (fbm_wire_encode):
+    a device tensor, or the host packed form (uploaded first).  timing: receives h2d / kernel / d2h seconds."""
+    import time
+
+    dev = rows.device if isinstance(rows, torch.Tensor) and rows.is_cuda else device()
+    lib = N.load()
+    t0 = time.perf_counter()
+    with torch.cuda.device(dev):
+        r = _wire_rows(scheme, rows, dev)
+        if timing is not None:
+            torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        n, sch = r.shape[0], _WIRE_SCHEME[scheme]
+        cap = int(lib.fbm_wire_encode_bound(sch, n))
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        ws = torch.empty(int(lib.fbm_wire_encode_workspace(sch, n)), dtype=torch.uint8, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        _call(lib.fbm_wire_encode, sch, _ptr(r), n, _ptr(out), cap, _ptr(ws), _ptr(total), _stream())
+        size = int(total.item())  # the one small copy; synchronises the stream
+        t2 = time.perf_counter()
+        data = to_host(out[:size]).numpy().tobytes()
+        t3 = time.perf_counter()
+    if timing is not None:
+        timing.update(h2d=t1 - t0, kernel=t2 - t1, d2h=t3 - t2)
+    return data
+
+
+def wire_decode(data, arrays: list, timing: Optional[dict] = None) -> List[np.ndarray]:
+    """The packed rows of wire_scan's arrays of the message `data` (fbm_wire_decode): their spans and tables go
+    to the device in one staging block, each is decoded there, and the rows come back as uint32 [n, 64] (jl) /
+    uint64 [n] (lom) host arrays."""
+    import time
+
+    dev = device()
+    lib = N.load()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    t0 = time.perf_counter()
+    # one staging block: every span (each padded to 8 bytes), then every table
+    s_off, c_off, pos = [], [], 0
+    for b, e, _, _, _ in arrays:
+        s_off.append(pos)
+        pos += (e - b + 7) // 8 * 8
+    for *_, ck in arrays:
+        c_off.append(pos)
+        pos += ck.size * 8
+    host = host_empty(pos, torch.uint8)
+    hv = host.numpy()
+    for (b, e, _, _, ck), so, co in zip(arrays, s_off, c_off):
+        hv[so:so + e - b] = buf[b:e]
+        hv[co:co + ck.size * 8] = ck.view(np.uint8)
+    with torch.cuda.device(dev):
+        blk = host.to(dev, non_blocking=host.is_pinned())
+        if timing is not None:
+            torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        outs = []
+        for (b, e, n, scheme, ck), so, co in zip(arrays, s_off, c_off):
+            rows = torch.empty((n, 64), dtype=torch.int32, device=dev) if scheme == "jl" else \
+                torch.empty(n, dtype=torch.int64, device=dev)
+            base = blk.data_ptr()
+            _call(lib.fbm_wire_decode, _WIRE_SCHEME[scheme], ctypes.c_void_p(base + so), e - b, b,
+                  ctypes.c_void_p(base + co), ck.size, n, _ptr(rows), _stream())
+            outs.append(rows)
+        if timing is not None:
+            torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        res = [to_host(r).numpy().view(np.uint32 if r.dtype == torch.int32 else np.uint64) for r in outs]
+        t3 = time.perf_counter()
+    if timing is not None:
+        timing.update(h2d=t1 - t0, kernel=t2 - t1, d2h=t3 - t2)
+    return res

@@ -139,7 +139,22 @@ SIGNATURES = {
     "fbm_ass_reconstruct": (c_int, [c_vp, c_int, c_u64, c_vp, c_vp]),
     "fbm_ass_split_wide": (c_int, [c_vp, c_u64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_u64, c_vp, c_vp]),
     "fbm_ass_reconstruct_wide": (c_int, [c_vp, c_int, c_int, c_u64, c_vp, c_vp]),
+    # the reference Serializer's update bytes on the device (additions to ABI 7)
+    "fbm_wire_encode_bound": (c_u64, [c_int, c_u64]),
+    "fbm_wire_encode_workspace": (c_u64, [c_int, c_u64]),
+    "fbm_wire_encode": (c_int, [c_int, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]),
+    "fbm_wire_scan": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp]),
+    "fbm_wire_decode": (c_int, [c_int, c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp, c_vp]),
 }
+WIRE_JL = 0  # FBM_WIRE_JL
+WIRE_LOM = 1  # FBM_WIRE_LOM
+WIRE_LOM_GROUP = 64  # FBM_WIRE_LOM_GROUP
+
+
+class WireArray(ctypes.Structure):
+    """fbm_wire_array: one array fbm_wire_scan recorded."""
+    _fields_ = [("begin", c_u64), ("end", c_u64), ("n_items", c_u64), ("ckpt_first", c_u64), ("ckpt_count", c_u64),
+                ("scheme", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 # include/fbm_secagg_test.h: exported by the test build only
 TEST_SIGNATURES = {
@@ -165,6 +180,8 @@ TEST_SIGNATURES = {
     "fbm_test_gen_exp": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "fbm_test_gen_combine": (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "fbm_test_lom_aggregate_kernel": (c_int, [c_int, c_u64, c_vp, ctypes.c_char_p, c_int]),
+    "fbm_test_wire_encode": (c_int, [c_int, c_vp, c_u64, c_vp, c_u64, c_vp]),
+    "fbm_test_wire_decode": (c_int, [c_int, c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp]),
     "fbm_prof_enable": (c_int, [c_int]),
     "fbm_prof_report": (c_int, [ctypes.c_char_p, c_int]),
 }

@@ -18,6 +18,8 @@
 #include "fbm_quad_asm.hpp"
 #include "fbm_tri_asm.hpp"
 #include "fbm_safegcd.hpp"
+#include "fbm_wire.hpp"
+#include "fbm_wire_scan.hpp"
 #ifdef FBM_TEST_HOOKS
 #include "../../include/fbm_secagg_test.h"
 #endif
@@ -1394,6 +1396,109 @@ int fbm_ass_reconstruct_wide(const uint32_t* shares, int n_shares, int l, uint64
                [&] { return launch_ass_reconstruct_wide(shares, n_shares, l, n, out, s); });
 }
 
+// ---- the reference Serializer's update bytes (serializer.py:96-110 / :140-149) -----------------------
+static bool wire_scheme(int scheme) { return scheme == FBM_WIRE_JL || scheme == FBM_WIRE_LOM; }
+
+uint64_t fbm_wire_encode_bound(int scheme, uint64_t n) {
+  return !wire_scheme(scheme) ? 0 : 5 + n * (scheme == FBM_WIRE_JL ? FBM_WIRE_ITEM_MAX + 1 : FBM_WIRE_NATIVE_MAX);
+}
+
+uint64_t fbm_wire_encode_workspace(int scheme, uint64_t n) {
+  return wire_scheme(scheme) ? wire_encode_workspace(scheme, n) : 0;
+}
+
+// the checks fbm_wire_encode and its host hook share
+static int wire_encode_checks(int scheme, const void* rows, uint64_t n, const uint8_t* out, uint64_t out_cap,
+                              const uint64_t* total) {
+  if (!wire_scheme(scheme)) {
+    set_error("fbm_wire_encode: scheme=%d must be FBM_WIRE_JL or FBM_WIRE_LOM", scheme);
+    return FBM_E_ARG;
+  }
+  if (n > 0xffffffffull) {
+    set_error("fbm_wire_encode: %llu items exceed a msgpack array", (unsigned long long)n);
+    return FBM_E_ARG;
+  }
+  if (!out || !total || (n > 0 && !rows)) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  if (out_cap < fbm_wire_encode_bound(scheme, n)) {
+    set_error("fbm_wire_encode: out_cap=%llu below fbm_wire_encode_bound's %llu", (unsigned long long)out_cap,
+              (unsigned long long)fbm_wire_encode_bound(scheme, n));
+    return FBM_E_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(rows) % (scheme == FBM_WIRE_JL ? 4 : 8)) || (reinterpret_cast<uintptr_t>(total) % 8)) {
+    set_error("fbm_wire_encode: rows / total not aligned to their element size");
+    return FBM_E_ARG;
+  }
+  return FBM_OK;
+}
+
+int fbm_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, void* workspace,
+                    uint64_t* total, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc = wire_encode_checks(scheme, rows, n, out, out_cap, total);
+  if (rc) return rc;
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) % 8)) {
+    set_error("fbm_wire_encode: null or misaligned workspace");
+    return FBM_E_ARG;
+  }
+  return timed("wire_encode", s, [&] { return launch_wire_encode(scheme, rows, n, out, out_cap, workspace, total, s); });
+}
+
+int fbm_wire_scan(const uint8_t* data, uint64_t len, uint64_t min_items, fbm_wire_array* arrays, uint64_t arrays_cap,
+                  uint64_t* n_arrays, uint64_t* ckpt, uint64_t ckpt_cap, uint64_t* n_ckpt) {
+  if ((len > 0 && !data) || !n_arrays || !n_ckpt || (arrays_cap > 0 && !arrays) || (ckpt_cap > 0 && !ckpt)) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  fbm_wire_scan_out o = {arrays, arrays_cap, 0, ckpt, ckpt_cap, 0};
+  const int r = fbm_wire_scan_impl(data, len, min_items, &o);
+  *n_arrays = o.n_arrays, *n_ckpt = o.n_ckpt;
+  if (r == FBM_WIRE_SCAN_GAVE_UP) {
+    set_error("fbm_wire_scan: not one well-formed msgpack object within the nesting bound");
+    return FBM_E_UNSUPPORTED;
+  }
+  if (r == FBM_WIRE_SCAN_FULL) {
+    set_error("fbm_wire_scan: arrays_cap / ckpt_cap too small");
+    return FBM_E_RANGE;
+  }
+  return FBM_OK;
+}
+
+static int wire_decode_checks(int scheme, const uint8_t* span, const uint64_t* ckpt, uint64_t n_ckpt, uint64_t n_items,
+                              const void* rows) {
+  if (!wire_scheme(scheme)) {
+    set_error("fbm_wire_decode: scheme=%d must be FBM_WIRE_JL or FBM_WIRE_LOM", scheme);
+    return FBM_E_ARG;
+  }
+  const uint64_t want = scheme == FBM_WIRE_JL ? n_items : (n_items + FBM_WIRE_LOM_GROUP - 1) / FBM_WIRE_LOM_GROUP;
+  if (n_ckpt != want) {
+    set_error("fbm_wire_decode: %llu checkpoints for %llu items (the scheme takes %llu)", (unsigned long long)n_ckpt,
+              (unsigned long long)n_items, (unsigned long long)want);
+    return FBM_E_ARG;
+  }
+  if (n_items > 0 && (!span || !ckpt || !rows)) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(ckpt) % 8) || (reinterpret_cast<uintptr_t>(rows) % (scheme == FBM_WIRE_JL ? 4 : 8))) {
+    set_error("fbm_wire_decode: ckpt / rows not aligned to their element size");
+    return FBM_E_ARG;
+  }
+  return FBM_OK;
+}
+
+int fbm_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                    uint64_t n_ckpt, uint64_t n_items, void* rows, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc = wire_decode_checks(scheme, span, ckpt, n_ckpt, n_items, rows);
+  if (rc) return rc;
+  if (n_items == 0) return FBM_OK;
+  return timed("wire_decode", s,
+               [&] { return launch_wire_decode(scheme, span, span_len, span_base, ckpt, n_ckpt, n_items, rows, s); });
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------
@@ -1404,6 +1509,18 @@ int fbm_ass_reconstruct_wide(const uint32_t* shares, int n_shares, int l, uint64
 // ---------------------------------------------------------------------------------------
 #ifdef FBM_TEST_HOOKS
 extern "C" {
+
+int fbm_test_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total) {
+  int rc = wire_encode_checks(scheme, rows, n, out, out_cap, total);
+  return rc ? rc : host_wire_encode(scheme, rows, n, out, out_cap, total);
+}
+
+int fbm_test_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                         uint64_t n_ckpt, uint64_t n_items, void* rows) {
+  int rc = wire_decode_checks(scheme, span, ckpt, n_ckpt, n_items, rows);
+  if (rc == FBM_OK && n_items) host_wire_decode(scheme, span, span_len, span_base, ckpt, n_ckpt, n_items, rows);
+  return rc;
+}
 
 int fbm_jl_window(void) { return FBM_WIN; }
 int fbm_jl_mads(int square) {  // 0: general product, 1: square, 2: short-base product

@@ -346,6 +346,17 @@ int launch_ass_split_wide(const uint32_t* secret, uint64_t n, int l_in, const ui
 int launch_ass_reconstruct_wide(const uint32_t* shares, int n_shares, int l, uint64_t n, uint32_t* out,
                                 hipStream_t s);
 
+// ---- the reference Serializer's update bytes (fbm_wire.hip; fbm_wire_encode / fbm_wire_decode) ----------
+uint64_t wire_encode_workspace(int scheme, uint64_t n);
+int launch_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, void* workspace,
+                       uint64_t* total, hipStream_t s);
+int launch_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt,
+                       uint64_t n_ckpt, uint64_t n, void* rows, hipStream_t s);
+// the same per-item routines on the host (test hooks)
+int host_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total);
+void host_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt,
+                      uint64_t n_ckpt, uint64_t n, void* rows);
+
 // table slots the encrypt/aggregate kernels need for a given grid
 uint64_t jl_table_slots();
 // exponentiation engine policy (fbm_jl_set_engine) and the table bytes both engines fit in

@@ -1,0 +1,352 @@
+// fedbiomed_amd -- the reference Serializer's update bytes, written and read on the device (gfx950).
+//
+// Encode (fedbiomed/common/serializer.py:96-110): JL rows [n, 64] u32 / LOM words [n] u64 -> the msgpack
+// array the reference's packb writes for the same ints.
+//   1. wire_sizes_*_kernel    each item's encoded size from its bit length; a tile's sum -> partial[tile]
+//   2. wire_scan_kernel       exclusive scan of the tile sums (one workgroup) + the array header; the total
+//   3. wire_emit_*_kernel     a tile's in-LDS scan gives every item its offset; header and big-endian bytes
+// Item offsets are unaligned.  JL: one wave per item (<= 280 bytes): the bytes before the first 4-byte
+// boundary and after the last go out as byte stores, every aligned dword between is composed by one lane
+// from the row (which the L1 holds after the first touch) and stored whole -- <= 71 dword stores per item,
+// consecutive lanes consecutive dwords.  LOM: a tile's items (<= 9 bytes each) are laid out in LDS at their
+// tile-local offsets, then the tile's one contiguous span is copied out the same way (byte edges, aligned
+// dwords between, consecutive lanes consecutive dwords).
+// Algorithmic bytes per item: JL 4 (top limb, pass 1; a 64-byte sector in practice) + 2 + 2 (size) + 256
+// read, <= 280 written; LOM 8 + 8 read (passes 1 and 3), <= 9 written.
+//
+// Decode (serializer.py:140-149), from the host scanner's checkpoints (fbm_wire_scan.hpp):
+//   wire_decode_jl_kernel   one wave per item: lane j assembles limb j from the <= 257 big-endian bytes
+//                           (byte loads of one contiguous run; 256-byte coalesced row store)
+//   wire_decode_lom_kernel  one wave per group of FBM_WIRE_LOM_GROUP = 64 items: the group's <= 576 bytes
+//                           into LDS with consecutive lanes on consecutive bytes, lane j walks j items
+//                           there (every lane still walking reads the same LDS byte: a broadcast), one
+//                           coalesced 512-byte store of the 64 words
+// Every read of the message is checked against its length and every write against the output's capacity,
+// whatever the table holds.
+#include "fbm_internal.hpp"
+#include "fbm_wire.hpp"
+
+namespace fbm {
+
+#define FBM_WIRE_BLOCK 256
+#define FBM_WIRE_TILE_JL 256                    // items per workgroup, one per thread in passes 1 and 3's scan
+#define FBM_WIRE_LOM_PER_THREAD 4
+#define FBM_WIRE_TILE_LOM (FBM_WIRE_BLOCK * FBM_WIRE_LOM_PER_THREAD)
+#define FBM_WIRE_SCAN_THREADS 256
+
+// exclusive scan of one value per thread over the workgroup's 256 threads; total = the tile's sum
+__device__ __forceinline__ uint32_t wire_block_scan(uint32_t v, uint32_t* sh, uint32_t& total) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int d = 1; d < FBM_WIRE_BLOCK; d <<= 1) {
+    const uint32_t x = t >= d ? sh[t - d] : 0u;
+    __syncthreads();
+    sh[t] += x;
+    __syncthreads();
+  }
+  const uint32_t incl = sh[t];
+  total = sh[FBM_WIRE_BLOCK - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_sizes_jl_kernel(const uint32_t* __restrict__ rows, uint64_t n,
+                                                                       uint16_t* __restrict__ sz,
+                                                                       uint64_t* __restrict__ partial) {
+  __shared__ uint32_t sh[FBM_WIRE_BLOCK];
+  const uint64_t i = (uint64_t)blockIdx.x * FBM_WIRE_TILE_JL + threadIdx.x;
+  uint32_t s = 0;
+  if (i < n) {
+    const uint32_t* row = rows + i * 64;
+    s = wire_jl_size(row, wire_jl_bits(row));
+    sz[i] = (uint16_t)s;
+  }
+  uint32_t total;
+  wire_block_scan(s, sh, total);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_sizes_lom_kernel(const uint64_t* __restrict__ vals, uint64_t n,
+                                                                        uint64_t* __restrict__ partial) {
+  __shared__ uint32_t sh[FBM_WIRE_BLOCK];
+  const uint64_t i0 = (uint64_t)blockIdx.x * FBM_WIRE_TILE_LOM + (uint64_t)threadIdx.x * FBM_WIRE_LOM_PER_THREAD;
+  uint32_t s = 0;
+#pragma unroll
+  for (int e = 0; e < FBM_WIRE_LOM_PER_THREAD; ++e)
+    if (i0 + e < n) s += wire_native_size(vals[i0 + e]);
+  uint32_t total;
+  wire_block_scan(s, sh, total);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+// partial[b] <- header size + sum of the tiles before b; the header's bytes; *total = the message's length
+__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_scan_kernel(uint64_t* __restrict__ partial, uint64_t nb,
+                                                                          uint64_t n, uint8_t* __restrict__ out,
+                                                                          uint64_t out_cap, uint64_t* __restrict__ total) {
+  __shared__ uint64_t sh[FBM_WIRE_SCAN_THREADS];
+  const int t = threadIdx.x;
+  const uint64_t chunk = (nb + FBM_WIRE_SCAN_THREADS - 1) / FBM_WIRE_SCAN_THREADS;
+  const uint64_t b0 = (uint64_t)t * chunk, b1 = b0 + chunk < nb ? b0 + chunk : nb;
+  uint64_t s = 0;
+  for (uint64_t b = b0; b < b1; ++b) s += partial[b];
+  sh[t] = s;
+  __syncthreads();
+  for (int d = 1; d < FBM_WIRE_SCAN_THREADS; d <<= 1) {
+    const uint64_t x = t >= d ? sh[t - d] : 0ull;
+    __syncthreads();
+    sh[t] += x;
+    __syncthreads();
+  }
+  const uint32_t hdr = wire_header_size(n);
+  uint64_t run = hdr + sh[t] - s;
+  for (uint64_t b = b0; b < b1; ++b) {
+    const uint64_t v = partial[b];
+    partial[b] = run;
+    run += v;
+  }
+  if (t == 0) {
+    *total = hdr + sh[FBM_WIRE_SCAN_THREADS - 1];
+    for (uint32_t k = 0; k < hdr && k < out_cap; ++k) out[k] = wire_header_byte(n, k);
+  }
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_emit_jl_kernel(const uint32_t* __restrict__ rows, uint64_t n,
+                                                                      const uint16_t* __restrict__ sz,
+                                                                      const uint64_t* __restrict__ partial,
+                                                                      uint8_t* __restrict__ out, uint64_t out_cap) {
+  __shared__ uint32_t sh[FBM_WIRE_BLOCK];
+  __shared__ uint32_t sh_off[FBM_WIRE_TILE_JL];
+  __shared__ uint32_t sh_sz[FBM_WIRE_TILE_JL];
+  const int t = threadIdx.x;
+  const uint64_t tile0 = (uint64_t)blockIdx.x * FBM_WIRE_TILE_JL;
+  const uint32_t s = tile0 + t < n ? sz[tile0 + t] : 0u;
+  uint32_t total;
+  sh_off[t] = wire_block_scan(s, sh, total);
+  sh_sz[t] = s;
+  __syncthreads();
+  const uint64_t base = partial[blockIdx.x];
+  const int wave = t >> 6, lane = t & 63;
+  for (int it = wave; it < FBM_WIRE_TILE_JL; it += FBM_WIRE_BLOCK / 64) {
+    const uint64_t i = tile0 + it;
+    if (i >= n) break;
+    const uint32_t S = sh_sz[it];
+    const uint64_t p = base + sh_off[it];
+    if (p > out_cap || out_cap - p < S) continue;  // (the caller's bound holds every item: never taken)
+    const uint32_t* row = rows + i * 64;
+    // the bit length, one limb per lane: the highest nonzero limb, then its width
+    const uint64_t nz = __ballot(row[lane] != 0);
+    int bits = 0;
+    if (nz) {
+      const int top = 63 - __builtin_clzll(nz);
+      bits = 32 * top + 32 - __builtin_clz(row[top]);
+    }
+    uint8_t* o = out + p;
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(o) & 3u);
+    uint32_t head = mis ? 4u - mis : 0u;
+    if (head > S) head = S;
+    const uint32_t ndw = (S - head) / 4;
+    const uint32_t tail0 = head + 4 * ndw;
+    if ((uint32_t)lane < head) o[lane] = wire_jl_byte(row, bits, lane);
+    for (uint32_t d = lane; d < ndw; d += 64) {
+      const uint32_t k = head + 4 * d;
+      const uint32_t w = (uint32_t)wire_jl_byte(row, bits, k) | ((uint32_t)wire_jl_byte(row, bits, k + 1) << 8) |
+                         ((uint32_t)wire_jl_byte(row, bits, k + 2) << 16) | ((uint32_t)wire_jl_byte(row, bits, k + 3) << 24);
+      *reinterpret_cast<uint32_t*>(o + k) = w;
+    }
+    if (tail0 + lane < S) o[tail0 + lane] = wire_jl_byte(row, bits, tail0 + lane);
+  }
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_emit_lom_kernel(const uint64_t* __restrict__ vals, uint64_t n,
+                                                                       const uint64_t* __restrict__ partial,
+                                                                       uint8_t* __restrict__ out, uint64_t out_cap) {
+  __shared__ uint32_t sh[FBM_WIRE_BLOCK];
+  __shared__ uint8_t buf[FBM_WIRE_TILE_LOM * FBM_WIRE_NATIVE_MAX];
+  const int t = threadIdx.x;
+  const uint64_t i0 = (uint64_t)blockIdx.x * FBM_WIRE_TILE_LOM + (uint64_t)t * FBM_WIRE_LOM_PER_THREAD;
+  uint64_t v[FBM_WIRE_LOM_PER_THREAD];
+  uint32_t sz[FBM_WIRE_LOM_PER_THREAD], s = 0;
+#pragma unroll
+  for (int e = 0; e < FBM_WIRE_LOM_PER_THREAD; ++e) {
+    v[e] = i0 + e < n ? vals[i0 + e] : 0ull;
+    sz[e] = i0 + e < n ? wire_native_size(v[e]) : 0u;
+    s += sz[e];
+  }
+  uint32_t total;
+  uint32_t lo = wire_block_scan(s, sh, total);
+#pragma unroll
+  for (int e = 0; e < FBM_WIRE_LOM_PER_THREAD; ++e) {
+    for (uint32_t k = 0; k < sz[e]; ++k) buf[lo + k] = wire_native_byte(v[e], sz[e], k);
+    lo += sz[e];
+  }
+  __syncthreads();
+  const uint64_t p = partial[blockIdx.x];
+  if (p > out_cap || out_cap - p < total) return;  // (the caller's bound holds every tile: never taken)
+  uint8_t* o = out + p;
+  const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(o) & 3u);
+  uint32_t head = mis ? 4u - mis : 0u;
+  if (head > total) head = total;
+  const uint32_t ndw = (total - head) / 4;
+  const uint32_t tail0 = head + 4 * ndw;
+  if ((uint32_t)t < head) o[t] = buf[t];
+  for (uint32_t d = t; d < ndw; d += FBM_WIRE_BLOCK) {
+    const uint32_t k = head + 4 * d;
+    *reinterpret_cast<uint32_t*>(o + k) =
+        (uint32_t)buf[k] | ((uint32_t)buf[k + 1] << 8) | ((uint32_t)buf[k + 2] << 16) | ((uint32_t)buf[k + 3] << 24);
+  }
+  if (tail0 + t < total) o[tail0 + t] = buf[tail0 + t];
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_decode_jl_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                        uint64_t base, const uint64_t* __restrict__ ckpt,
+                                                                        uint64_t n, uint32_t* __restrict__ rows) {
+  const uint64_t i = (uint64_t)blockIdx.x * (FBM_WIRE_BLOCK / 64) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (i >= n) return;
+  const uint64_t c = ckpt[i];
+  const uint64_t voff = c >> 16;
+  const uint32_t vlen = (uint32_t)(c & 0xffff);
+  uint32_t w = 0;
+  if (voff >= base && voff - base <= span_len && span_len - (voff - base) >= vlen && vlen <= 257)
+    w = wire_jl_limb(span + (voff - base), vlen, lane);
+  rows[i * 64 + lane] = w;
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_decode_lom_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                         uint64_t base, const uint64_t* __restrict__ ckpt,
+                                                                         uint64_t n_groups, uint64_t n,
+                                                                         uint64_t* __restrict__ out) {
+  constexpr int GB = FBM_WIRE_LOM_GROUP * FBM_WIRE_NATIVE_MAX;  // a group's bytes at most
+  __shared__ uint8_t buf[FBM_WIRE_BLOCK / 64][GB];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t g = (uint64_t)blockIdx.x * (FBM_WIRE_BLOCK / 64) + wave;
+  uint32_t avail = 0;
+  if (g < n_groups) {
+    const uint64_t c = ckpt[g];
+    if (c >= base && c - base < span_len) {
+      const uint64_t goff = c - base, left = span_len - goff;
+      avail = left < (uint64_t)GB ? (uint32_t)left : (uint32_t)GB;
+      for (uint32_t k = lane; k < avail; k += 64) buf[wave][k] = span[goff + k];
+    }
+  }
+  __syncthreads();
+  const uint64_t i = g * FBM_WIRE_LOM_GROUP + lane;
+  if (g < n_groups && i < n) out[i] = wire_lom_group_item(buf[wave], avail, lane);
+}
+
+static int wire_grid(uint64_t blocks, const char* what, unsigned& g) {
+  if (blocks > 0x7fffffffull) {
+    set_error("%s: %llu workgroups exceed one launch's grid", what, (unsigned long long)blocks);
+    return FBM_E_UNSUPPORTED;
+  }
+  g = (unsigned)blocks;
+  return FBM_OK;
+}
+
+static uint64_t wire_tiles(int scheme, uint64_t n) {
+  const uint64_t tile = scheme == FBM_WIRE_JL ? FBM_WIRE_TILE_JL : FBM_WIRE_TILE_LOM;
+  return (n + tile - 1) / tile;
+}
+
+// workspace: the tile sums (u64 each, rounded up to 256 bytes), then JL's item sizes (u16 each)
+uint64_t wire_encode_workspace(int scheme, uint64_t n) {
+  const uint64_t part = (wire_tiles(scheme, n) * 8 + 255) / 256 * 256 + 256;
+  return part + (scheme == FBM_WIRE_JL ? (n * 2 + 255) / 256 * 256 : 0);
+}
+
+int launch_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, void* workspace,
+                       uint64_t* total, hipStream_t s) {
+  const uint64_t nb = wire_tiles(scheme, n);
+  unsigned g = 0;
+  int rc = wire_grid(nb, "fbm_wire_encode", g);
+  if (rc) return rc;
+  uint64_t* partial = reinterpret_cast<uint64_t*>(workspace);
+  uint16_t* sz = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(workspace) + (nb * 8 + 255) / 256 * 256 + 256);
+  if (g) {
+    if (scheme == FBM_WIRE_JL)
+      hipLaunchKernelGGL(wire_sizes_jl_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, (const uint32_t*)rows, n, sz, partial);
+    else
+      hipLaunchKernelGGL(wire_sizes_lom_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, (const uint64_t*)rows, n, partial);
+    if ((rc = check_launch("wire_sizes_kernel"))) return rc;
+  }
+  hipLaunchKernelGGL(wire_scan_kernel, dim3(1), dim3(FBM_WIRE_SCAN_THREADS), 0, s, partial, nb, n, out, out_cap, total);
+  if ((rc = check_launch("wire_scan_kernel"))) return rc;
+  if (g) {
+    if (scheme == FBM_WIRE_JL)
+      hipLaunchKernelGGL(wire_emit_jl_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, (const uint32_t*)rows, n, sz, partial, out,
+                         out_cap);
+    else
+      hipLaunchKernelGGL(wire_emit_lom_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, (const uint64_t*)rows, n, partial, out,
+                         out_cap);
+    if ((rc = check_launch("wire_emit_kernel"))) return rc;
+  }
+  return FBM_OK;
+}
+
+int launch_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt,
+                       uint64_t n_ckpt, uint64_t n, void* rows, hipStream_t s) {
+  if (n == 0) return FBM_OK;
+  const uint64_t waves = scheme == FBM_WIRE_JL ? n : n_ckpt;
+  unsigned g = 0;
+  int rc = wire_grid((waves + FBM_WIRE_BLOCK / 64 - 1) / (FBM_WIRE_BLOCK / 64), "fbm_wire_decode", g);
+  if (rc) return rc;
+  if (scheme == FBM_WIRE_JL)
+    hipLaunchKernelGGL(wire_decode_jl_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, base, ckpt, n,
+                       (uint32_t*)rows);
+  else
+    hipLaunchKernelGGL(wire_decode_lom_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, base, ckpt, n_ckpt, n,
+                       (uint64_t*)rows);
+  return check_launch("wire_decode_kernel");
+}
+
+// ---- the same per-item routines on the host (the test build's hooks) ------------------------------
+int host_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total) {
+  uint64_t p = 0;
+  const uint32_t hdr = wire_header_size(n);
+  for (uint32_t k = 0; k < hdr; ++k, ++p)
+    if (p < out_cap) out[p] = wire_header_byte(n, k);
+  for (uint64_t i = 0; i < n; ++i) {
+    if (scheme == FBM_WIRE_JL) {
+      const uint32_t* row = (const uint32_t*)rows + i * 64;
+      const int bits = wire_jl_bits(row);
+      const uint32_t S = wire_jl_size(row, bits);
+      for (uint32_t k = 0; k < S; ++k, ++p)
+        if (p < out_cap) out[p] = wire_jl_byte(row, bits, k);
+    } else {
+      const uint64_t v = ((const uint64_t*)rows)[i];
+      const uint32_t S = wire_native_size(v);
+      for (uint32_t k = 0; k < S; ++k, ++p)
+        if (p < out_cap) out[p] = wire_native_byte(v, S, k);
+    }
+  }
+  *total = p;
+  return p <= out_cap ? FBM_OK : FBM_E_ARG;
+}
+
+void host_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt,
+                      uint64_t n_ckpt, uint64_t n, void* rows) {
+  if (scheme == FBM_WIRE_JL) {
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint64_t voff = ckpt[i] >> 16;
+      const uint32_t vlen = (uint32_t)(ckpt[i] & 0xffff);
+      const bool ok = voff >= base && voff - base <= span_len && span_len - (voff - base) >= vlen && vlen <= 257;
+      for (int j = 0; j < 64; ++j) ((uint32_t*)rows)[i * 64 + j] = ok ? wire_jl_limb(span + (voff - base), vlen, j) : 0u;
+    }
+    return;
+  }
+  constexpr uint64_t GB = FBM_WIRE_LOM_GROUP * FBM_WIRE_NATIVE_MAX;
+  for (uint64_t g = 0; g < n_ckpt; ++g) {
+    uint32_t avail = 0;
+    const uint8_t* buf = span;
+    if (ckpt[g] >= base && ckpt[g] - base < span_len) {
+      const uint64_t left = span_len - (ckpt[g] - base);
+      avail = (uint32_t)(left < GB ? left : GB);
+      buf = span + (ckpt[g] - base);
+    }
+    for (int j = 0; j < FBM_WIRE_LOM_GROUP; ++j)
+      if (g * FBM_WIRE_LOM_GROUP + j < n) ((uint64_t*)rows)[g * FBM_WIRE_LOM_GROUP + j] = wire_lom_group_item(buf, avail, j);
+  }
+}
+
+}  // namespace fbm

@@ -1,0 +1,217 @@
+// fedbiomed_amd -- host scanner of a msgpack message for the reference Serializer's integer arrays
+// (fedbiomed/common/serializer.py:96-110 writes them, :140-149 reads them).  Plain C++, no HIP: the bytes
+// come from the network, so this file also compiles on its own under the host sanitizers.
+//
+// One iterative pass with a bounded nesting depth skips every msgpack object and never reads at or past
+// `len`.  An array of at least min_items items, each of them
+//   * a native unsigned int (positive fixint, cc / cd / ce / cf; minimal or not: the value is the same), or
+//   * the 20-byte map prefix  82 a8 "__type__" a3 "int" a5 "value"  then bin8 / bin16 of 1 <= L <= 257
+//     bytes with a first byte < 0x80 and a value < 2^2048 (L == 257: the first byte is 0),
+// is recorded with its byte span, item count, scheme (FBM_WIRE_LOM when every item is native, else
+// FBM_WIRE_JL) and checkpoints; any other array is walked like every other object and stays msgpack's.
+//
+// Checkpoints (absolute byte offsets into the message):
+//   FBM_WIRE_JL   one per item: (offset of the value's first big-endian byte) << 16 | byte count
+//   FBM_WIRE_LOM  one per FBM_WIRE_LOM_GROUP items: the offset of the group's first item
+// While an array's items are all native only group checkpoints are written; the first map item restarts the
+// array's table per item (one re-walk of the items before it, at most once per array).
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/fbm_secagg.h"
+
+#define FBM_WIRE_MAX_DEPTH 32  // containers open at once; deeper: the scan gives up
+#define FBM_WIRE_PREFIX_LEN 20
+#define FBM_WIRE_SCAN_GAVE_UP 1  // malformed, truncated, trailing bytes or too deep: nothing is recorded
+#define FBM_WIRE_SCAN_FULL 2     // a table of the caller's is too small
+
+static const uint8_t FBM_WIRE_PREFIX[FBM_WIRE_PREFIX_LEN] = {0x82, 0xa8, '_', '_', 't', 'y', 'p', 'e', '_', '_',
+                                                             0xa3, 'i',  'n', 't', 0xa5, 'v', 'a', 'l', 'u', 'e'};
+
+// One accepted item at d[pos..]: returns its byte count (0: not an accepted form, or truncated), the span of
+// its big-endian value bytes and whether it is a native form.
+static inline uint64_t fbm_wire_item(const uint8_t* d, uint64_t pos, uint64_t len, uint64_t* voff, uint32_t* vlen,
+                                     int* native) {
+  if (pos >= len) return 0;
+  const uint64_t left = len - pos;  // >= 1
+  const uint8_t b = d[pos];
+  if (b <= 0x7f) {
+    *voff = pos, *vlen = 1, *native = 1;
+    return 1;
+  }
+  if (b >= 0xcc && b <= 0xcf) {
+    const uint32_t w = 1u << (b - 0xcc);
+    if (left < 1ull + w) return 0;
+    *voff = pos + 1, *vlen = w, *native = 1;
+    return 1ull + w;
+  }
+  if (b != 0x82 || left < FBM_WIRE_PREFIX_LEN + 2 || memcmp(d + pos, FBM_WIRE_PREFIX, FBM_WIRE_PREFIX_LEN) != 0) return 0;
+  const uint64_t p = pos + FBM_WIRE_PREFIX_LEN;  // p + 1 < len
+  uint64_t v;
+  uint32_t L;
+  if (d[p] == 0xc4) {
+    L = d[p + 1], v = p + 2;
+  } else if (d[p] == 0xc5) {
+    if (len - p < 3) return 0;
+    L = ((uint32_t)d[p + 1] << 8) | d[p + 2], v = p + 3;
+  } else {
+    return 0;
+  }
+  if (L < 1 || L > 257 || len - v < L) return 0;
+  if (d[v] >= 0x80 || (L == 257 && d[v] != 0)) return 0;  // a negative value, or one of 2^2048 or more
+  *voff = v, *vlen = L, *native = 0;
+  return v + L - pos;
+}
+
+struct fbm_wire_scan_out {
+  fbm_wire_array* arrays;
+  uint64_t arrays_cap, n_arrays;
+  uint64_t* ckpt;
+  uint64_t ckpt_cap, n_ckpt;
+};
+
+// items [first, first + n) of a candidate array: 1 recorded (*end = one past it), 0 not, -1 a table is full
+static inline int fbm_wire_candidate(const uint8_t* d, uint64_t len, uint64_t begin, uint64_t first, uint64_t n,
+                                     fbm_wire_scan_out* o, uint64_t* end) {
+  if (o->n_arrays >= o->arrays_cap) return -1;
+  const uint64_t ck0 = o->n_ckpt;
+  int lom = 1, native = 0;
+  uint64_t p = first, voff = 0;
+  uint32_t vlen = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (lom && i % FBM_WIRE_LOM_GROUP == 0) {
+      if (o->n_ckpt >= o->ckpt_cap) return -1;
+      o->ckpt[o->n_ckpt++] = p;
+    }
+    const uint64_t c = fbm_wire_item(d, p, len, &voff, &vlen, &native);
+    if (c == 0) {
+      o->n_ckpt = ck0;
+      return 0;
+    }
+    if (lom && !native) {  // the first map item: the table again, per item
+      lom = 0;
+      o->n_ckpt = ck0;
+      uint64_t q = first, qo = 0;
+      uint32_t ql = 0;
+      int qn = 0;
+      for (uint64_t j = 0; j < i; ++j) {
+        const uint64_t cj = fbm_wire_item(d, q, len, &qo, &ql, &qn);  // (accepted once already: cj > 0)
+        if (o->n_ckpt >= o->ckpt_cap) return -1;
+        o->ckpt[o->n_ckpt++] = (qo << 16) | ql;
+        q += cj;
+      }
+    }
+    if (!lom) {
+      if (o->n_ckpt >= o->ckpt_cap) return -1;
+      o->ckpt[o->n_ckpt++] = (voff << 16) | vlen;
+    }
+    p += c;
+  }
+  fbm_wire_array* a = &o->arrays[o->n_arrays++];
+  a->begin = begin, a->end = p, a->n_items = n;
+  a->ckpt_first = ck0, a->ckpt_count = o->n_ckpt - ck0;
+  a->scheme = lom ? FBM_WIRE_LOM : FBM_WIRE_JL, a->pad = 0;
+  *end = p;
+  return 1;
+}
+
+static inline uint64_t fbm_wire_be(const uint8_t* p, int bytes) {
+  uint64_t v = 0;
+  for (int i = 0; i < bytes; ++i) v = (v << 8) | p[i];
+  return v;
+}
+
+// FBM_OK, FBM_WIRE_SCAN_GAVE_UP or FBM_WIRE_SCAN_FULL; on anything but FBM_OK the counts are zero
+static inline int fbm_wire_scan_impl(const uint8_t* d, uint64_t len, uint64_t min_items, fbm_wire_scan_out* o) {
+  uint64_t stack[FBM_WIRE_MAX_DEPTH];  // objects still to read in each open container
+  int depth = 1;
+  uint64_t pos = 0;
+  stack[0] = 1;  // the message is one object
+  o->n_arrays = o->n_ckpt = 0;
+  if (min_items < 1) min_items = 1;
+  while (depth > 0) {
+    if (stack[depth - 1] == 0) {
+      --depth;
+      continue;
+    }
+    --stack[depth - 1];
+    if (pos >= len) goto gave_up;
+    {
+      const uint8_t b = d[pos];
+      const uint64_t left = len - pos;
+      uint64_t skip = 0, children = 0;  // a scalar's whole size / a container's header size and objects
+      int container = 0, is_array = 0;
+      if (b <= 0x7f || b >= 0xe0 || b == 0xc0 || b == 0xc2 || b == 0xc3) {
+        skip = 1;
+      } else if (b <= 0x8f) {
+        container = 1, skip = 1, children = 2ull * (b & 0x0f);
+      } else if (b <= 0x9f) {
+        container = 1, is_array = 1, skip = 1, children = b & 0x0f;
+      } else if (b <= 0xbf) {
+        skip = 1ull + (b & 0x1f);
+      } else {
+        int lb = 0;  // bytes of a length field
+        uint64_t extra = 0;
+        switch (b) {
+          case 0xc4: case 0xd9: lb = 1; break;
+          case 0xc5: case 0xda: lb = 2; break;
+          case 0xc6: case 0xdb: lb = 4; break;
+          case 0xc7: lb = 1, extra = 1; break;
+          case 0xc8: lb = 2, extra = 1; break;
+          case 0xc9: lb = 4, extra = 1; break;
+          case 0xca: case 0xce: case 0xd2: skip = 5; break;
+          case 0xcb: case 0xcf: case 0xd3: skip = 9; break;
+          case 0xcc: case 0xd0: skip = 2; break;
+          case 0xcd: case 0xd1: skip = 3; break;
+          case 0xd4: skip = 3; break;
+          case 0xd5: skip = 4; break;
+          case 0xd6: skip = 6; break;
+          case 0xd7: skip = 10; break;
+          case 0xd8: skip = 18; break;
+          case 0xdc: container = 1, is_array = 1, lb = 2; break;
+          case 0xdd: container = 1, is_array = 1, lb = 4; break;
+          case 0xde: container = 1, lb = 2; break;
+          case 0xdf: container = 1, lb = 4; break;
+          default: goto gave_up;  // 0xc1: never used
+        }
+        if (lb) {
+          if (left < 1ull + lb) goto gave_up;
+          const uint64_t v = fbm_wire_be(d + pos + 1, lb);
+          if (container) {
+            skip = 1ull + lb, children = is_array ? v : 2 * v;
+          } else {
+            skip = 1ull + lb + extra + v;
+          }
+        }
+      }
+      if (left < skip) goto gave_up;
+      if (!container) {
+        pos += skip;
+        continue;
+      }
+      if (is_array && children >= min_items) {
+        uint64_t end = 0;
+        const int r = fbm_wire_candidate(d, len, pos, pos + skip, children, o, &end);
+        if (r < 0) {
+          o->n_arrays = o->n_ckpt = 0;
+          return FBM_WIRE_SCAN_FULL;
+        }
+        if (r > 0) {
+          pos = end;
+          continue;
+        }
+      }
+      pos += skip;
+      if (children) {
+        if (depth >= FBM_WIRE_MAX_DEPTH) goto gave_up;
+        stack[depth++] = children;
+      }
+    }
+  }
+  if (pos != len) goto gave_up;  // trailing bytes: msgpack raises ExtraData
+  return FBM_OK;
+gave_up:
+  o->n_arrays = o->n_ckpt = 0;
+  return FBM_WIRE_SCAN_GAVE_UP;
+}

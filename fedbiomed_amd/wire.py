@@ -24,6 +24,11 @@ working.  With it enabled:
 `from_wire` materialises the Python ints as well, so every consumer that treats the update as
 ``List[int]`` sees exactly the reference's values.
 
+The blob needs the hook on both ends.  Where only one side is patched, `dumps_reference` /
+`loads_reference` (below) write and read the reference's own per-item encoding on the device instead,
+byte for byte what the stock `Serializer` writes, so the peer needs nothing ("One
+patched side"); `reference_stats` counts the updates that took that path and those left to msgpack.
+
 `ChunkAssembler` is the other half of §8(f)2: the gRPC transport streams a serialized message in
 chunks of `MAX_MESSAGE_BYTES_LENGTH` (4 MB) and the receiver rebuilds it with ``reply += chunk``
 (`fedbiomed/transport/server.py:236-239`, `client.py:599-602` in `_call_researcher`), which copies the growing message at
@@ -189,3 +194,176 @@ class ChunkAssembler:
         out = b"".join(self._parts)
         self._parts = []
         return out
+
+
+# ---- one patched side: the reference's own bytes, made and read on the device -----------------------
+# A stock peer speaks only the reference Serializer's encoding (`fedbiomed/common/serializer.py:96-110`,
+# `:140-149`): one msgpack item per ciphertext / element.  `dumps_reference` / `loads_reference` produce and
+# consume exactly those bytes from the packed device form (the C ABI's fbm_wire_encode / fbm_wire_scan /
+# fbm_wire_decode), so only this side needs its two Serializer lines ("One patched side").
+_STATS = {"fast": 0, "fallback": 0}
+_LAST: Dict[str, Any] = {}  # the last call's phases in seconds (tools/wire_ref_ab.py)
+
+
+def reference_stats(reset: bool = False) -> Dict[str, Any]:
+    """Updates that took the device path ("fast") and updates or messages that took msgpack's ("fallback")
+    since the last reset, and the last call's phase times ("last": scan / h2d / kernel / d2h seconds)."""
+    out = dict(_STATS, last=dict(_LAST))
+    if reset:
+        _STATS.update(fast=0, fallback=0)
+        _LAST.clear()
+    return out
+
+
+def _reference_default(obj: Any) -> Dict[str, Any]:
+    """The reference's `Serializer._default` rule for ints (serializer.py:103-110)."""
+    if isinstance(obj, int):
+        return {"__type__": "int", "value": obj.to_bytes(length=(obj.bit_length() + 7) // 8 + 1, byteorder="big",
+                                                         signed=True)}
+    raise TypeError(f"Cannot serialize object of type '{type(obj)}'.")
+
+
+def _encode_rows(scheme: str, rows) -> bytes:
+    """The device call of `reference_bytes` (a seam: the CPU tests put the library's host run here)."""
+    from . import _device as D
+
+    timing: Dict[str, float] = {}
+    data = D.wire_encode(scheme, rows, timing)
+    for k, v in timing.items():
+        _LAST[k] = _LAST.get(k, 0.0) + v
+    return data
+
+
+def _decode_arrays(data: bytes, arrays: list) -> list:
+    """The device call of `loads_reference` (the same seam)."""
+    from . import _device as D
+
+    timing: Dict[str, float] = {}
+    rows = D.wire_decode(data, arrays, timing)
+    _LAST.update(timing)
+    return rows
+
+
+def reference_bytes(update) -> bytes:
+    """Exactly ``msgpack.packb(list_of_ints, default=<reference _default>, strict_types=True)`` for a consistent
+    `EncryptedParams` or a device tensor in either layout (int32 ``[n_ct, 64]``: JL; int64 ``[n]``: LOM), made on
+    the device.  An `EncryptedParams` whose packed form was dropped goes through msgpack like a plain list."""
+    if isinstance(update, EncryptedParams):
+        if update.consistent():
+            _STATS["fast"] += 1
+            return _encode_rows(update.scheme, update.packed)
+        import msgpack
+
+        _STATS["fallback"] += 1
+        return msgpack.packb(list(update), default=_reference_default, strict_types=True)
+    import torch
+
+    if isinstance(update, torch.Tensor) and update.is_cuda:
+        if update.dtype == torch.int32 and update.dim() == 2 and update.shape[1] == 64:
+            scheme = "jl"
+        elif update.dtype == torch.int64 and update.dim() == 1:
+            scheme = "lom"
+        else:
+            raise ValueError("reference_bytes takes int32 [n_ct, 64] (JL) or int64 [n] (LOM) device tensors")
+        _STATS["fast"] += 1
+        return _encode_rows(scheme, update)
+    raise TypeError("reference_bytes takes an EncryptedParams or a device tensor")
+
+
+def dumps_reference(obj: Any, default=None) -> bytes:
+    """`Serializer.dumps` for a message that holds `EncryptedParams`: byte for byte what
+    ``packb(obj, default=default, strict_types=True)`` gives for the same message holding plain lists
+    (`default`: the Serializer's own `_default`; None: the reference's int rule).  Each consistent
+    `EncryptedParams` goes to the packer as a bin of 16 random bytes, which is then replaced by
+    `reference_bytes` of that update; a placeholder that does not occur exactly once (the message itself holds
+    those 18 bytes) is drawn again."""
+    import os
+
+    import msgpack
+
+    _LAST.clear()
+    inner = default or _reference_default
+    for _ in range(8):
+        held: Dict[bytes, EncryptedParams] = {}
+
+        def wrapped(o):
+            if isinstance(o, EncryptedParams):
+                if o.consistent():
+                    tok = os.urandom(16)
+                    held[tok] = o
+                    return tok
+                _STATS["fallback"] += 1
+                return list(o)
+            return inner(o)
+
+        fb = _STATS["fallback"]
+        body = msgpack.packb(obj, default=wrapped, strict_types=True)
+        marks = {tok: b"\xc4\x10" + tok for tok in held}
+        if all(body.count(m) == 1 for m in marks.values()):
+            break
+        _STATS["fallback"] = fb  # (counted again on the retry)
+    else:
+        raise RuntimeError("dumps_reference: no unique placeholder in 8 draws")
+    if not held:
+        return body
+    order = sorted((body.index(m), tok) for tok, m in marks.items())
+    parts, pos = [], 0
+    for at, tok in order:
+        parts += [body[pos:at], reference_bytes(held[tok])]
+        pos = at + 18
+    parts.append(body[pos:])
+    return b"".join(parts)
+
+
+def _hook_reads_ints(object_hook) -> bool:
+    """Whether `object_hook` turns the reference's int map into the int (serializer.py:140-149): only then
+    does an array of those maps unpack to the ints a "jl" `EncryptedParams` holds."""
+    if object_hook is None:
+        return False
+    try:
+        v = object_hook({"__type__": "int", "value": b"\x00\x80" + bytes(8)})
+    except Exception:
+        return False
+    return type(v) is int and v == 1 << 71
+
+
+def loads_reference(data: bytes, object_hook=None, min_items: int = 1024) -> Any:
+    """``msgpack.unpackb(data, object_hook=object_hook, strict_map_key=False)`` with every integer array of at
+    least `min_items` items the host scanner records read on the device: it comes back as an `EncryptedParams`
+    (which compares as the list of ints msgpack would have made) whose ``packed`` is ready for `aggregate` /
+    `begin_aggregate().add`.  Arrays the scanner refuses stay msgpack's; where it records nothing or gives up,
+    this is exactly that call.  (Arrays of the big-int map are taken only when `object_hook` reads that map as
+    the reference's does.)"""
+    import os
+    import time
+
+    import msgpack
+
+    from . import _device as D
+
+    _LAST.clear()
+    t0 = time.perf_counter()
+    arrays = D.wire_scan(data, min_items)
+    _LAST["scan"] = time.perf_counter() - t0
+    if arrays and not _hook_reads_ints(object_hook):
+        arrays = [a for a in arrays if a[3] != "jl"]
+    if not arrays:
+        _STATS["fallback"] += 1
+        return msgpack.unpackb(data, object_hook=object_hook, strict_map_key=False)
+    rows = _decode_arrays(data, arrays)
+    token = "fedbiomed_amd.ref." + os.urandom(12).hex()
+    view = memoryview(data)
+    parts, pos = [], 0
+    for i, (b, e, _, _, _) in enumerate(arrays):
+        parts += [view[pos:b], msgpack.packb({"__type__": token, "value": i})]
+        pos = e
+    parts.append(view[pos:])
+
+    def hook(o):
+        if o.get("__type__") == token:
+            i = o["value"]
+            _STATS["fast"] += 1
+            return EncryptedParams.from_packed(arrays[i][3], rows[i])
+        return o if object_hook is None else object_hook(o)
+
+    return msgpack.unpackb(b"".join(parts), object_hook=hook, strict_map_key=False)

@@ -34,7 +34,8 @@ extern "C" {
 #define FBM_ABI_VERSION 7 /* 7: the test, A/B and profiling hooks left this header for fbm_secagg_test.h (exported by
                              the test build only) -- and, additions only, so still 7: the input dtypes FBM_F16 / FBM_BF16
                              and the *_as entry points (fbm_lom_aggregate_as, fbm_jl_aggregate_as,
-                             fbm_jl_aggregate_factor_as, fbm_dequantize_as); 6: fbm_lom_*_host; 5: fbm_jl_encrypt_factor; 4: fbm_ves_pack takes is_signed; 3: the JL round is an 8192-bit value (FBM_TAU_LIMBS limbs);
+                             fbm_jl_aggregate_factor_as, fbm_dequantize_as), the streaming folds, and the reference Serializer's bytes on the
+                             device (fbm_wire_*); 6: fbm_lom_*_host; 5: fbm_jl_encrypt_factor; 4: fbm_ves_pack takes is_signed; 3: the JL round is an 8192-bit value (FBM_TAU_LIMBS limbs);
                              2 took 16 limbs, 1 a uint64 */
 /* The JL round `tau` of every JL entry point: a HOST pointer to FBM_TAU_LIMBS little-endian 32-bit
  * words, any round below 2^8192 -- FDH.H hashes t = (k << 512) | tau as t.to_bytes(1024, 'big')
@@ -410,6 +411,62 @@ int fbm_ass_split_wide(const uint32_t* secret, uint64_t n, int l_in, int n_share
                        const uint8_t* seed, const uint8_t* nonce, uint64_t elem_offset, uint32_t* shares,
                        void* stream);
 int fbm_ass_reconstruct_wide(const uint32_t* shares, int n_shares, int l, uint64_t n, uint32_t* out, void* stream);
+
+/* ---- the reference Serializer's update bytes, written and read on the device ---------------------
+ * The reference ships an update as a msgpack array of Python ints (fedbiomed/common/serializer.py:96-110,
+ * packb(default=_default, strict_types=True)): a value below 2^64 in its shortest native form (the byte
+ * itself up to 127, else cc / cd / ce / cf + 1 / 2 / 4 / 8 big-endian bytes), a larger one as the map
+ * 82 a8 "__type__" a3 "int" a5 "value" (20 bytes) + a bin of L = ceil(bit_length / 8) + 1 big-endian bytes
+ * (c4 L up to 255, c5 + BE16 from 256 on; the first byte is the reference's sign byte, 00): 280 bytes for a
+ * full-width JL ciphertext.  These entry points write and read exactly those bytes from the device layouts,
+ * so a peer with the stock Serializer sees what Serializer.dumps would have sent (:96-110) and what it
+ * sends is read without a Python object per item (:140-149).  Values of 2^2048 or more and negative values
+ * are outside their domain. */
+#define FBM_WIRE_JL 0         /* rows [n][64] uint32, little-endian limbs (one ciphertext < 2^2048 each) */
+#define FBM_WIRE_LOM 1        /* words [n] uint64 */
+#define FBM_WIRE_LOM_GROUP 64 /* items per checkpoint of a FBM_WIRE_LOM array (one wave decodes a group) */
+
+/* One array the scanner recorded: bytes [begin, end) of the message (header included), its items, its
+ * scheme, and its checkpoints ckpt[ckpt_first .. ckpt_first + ckpt_count) -- all absolute byte offsets into
+ * the message.  FBM_WIRE_JL: one per item, (offset of the value's first big-endian byte) << 16 | byte count
+ * (1..257).  FBM_WIRE_LOM: one per FBM_WIRE_LOM_GROUP items, the offset of the group's first item. */
+typedef struct fbm_wire_array {
+  uint64_t begin, end, n_items, ckpt_first, ckpt_count;
+  int32_t scheme, pad;
+} fbm_wire_array;
+
+/* Encode (serializer.py:96-110).  fbm_wire_encode_bound: the worst-case size of n items' message, 5 + 281 n
+ * (FBM_WIRE_JL) or 5 + 9 n (FBM_WIRE_LOM); fbm_wire_encode_workspace: the device workspace's bytes (both 0
+ * for an unknown scheme).  fbm_wire_encode: rows (device, the scheme's layout, n < 2^32 items) -> out
+ * (device, out_cap >= the bound), the array header in front; *total (device, 8-byte aligned) receives the
+ * message's length: the one small copy the caller makes after the stream is synchronised.  Three passes:
+ * the items' sizes, an exclusive scan of them, the bytes.  Argument errors return FBM_E_ARG before any
+ * device call. */
+uint64_t fbm_wire_encode_bound(int scheme, uint64_t n);
+uint64_t fbm_wire_encode_workspace(int scheme, uint64_t n);
+int fbm_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, void* workspace,
+                    uint64_t* total, void* stream);
+
+/* Host scanner (no device call; serializer.py:140-149 reads what it skips): one iterative pass over the
+ * HOST message data[0, len), every msgpack object skipped, nesting bounded (32 open containers), no byte at
+ * or past len read.  Every array of at least min_items (>= 1) items, each a native unsigned int (minimal or
+ * not) or the exact map form above with 1 <= L <= 257, a first byte < 0x80 and a value < 2^2048, is
+ * recorded in arrays / ckpt (HOST); any other array -- a negative int, a sign byte >= 0x80, a value of 2^2048
+ * or more, swapped or str8 map keys, a float -- is not, and stays msgpack's.  Returns FBM_OK with the
+ * counts; FBM_E_UNSUPPORTED when the scan gives up (a truncated or malformed message, trailing bytes,
+ * nesting past the bound: nothing recorded, the message stays msgpack's); FBM_E_RANGE when arrays_cap or
+ * ckpt_cap is too small (len entries of each always suffice); FBM_E_ARG for a null pointer. */
+int fbm_wire_scan(const uint8_t* data, uint64_t len, uint64_t min_items, fbm_wire_array* arrays, uint64_t arrays_cap,
+                  uint64_t* n_arrays, uint64_t* ckpt, uint64_t ckpt_cap, uint64_t* n_ckpt);
+
+/* Decode (serializer.py:140-149) of one recorded array: span (device) holds the message's bytes
+ * [span_base, span_base + span_len) -- the array's own span, or more --, ckpt (device) the array's n_ckpt
+ * checkpoints as the scanner wrote them (n_items of them for FBM_WIRE_JL, ceil(n_items /
+ * FBM_WIRE_LOM_GROUP) for FBM_WIRE_LOM: anything else is FBM_E_ARG), rows (device) receives n_items
+ * zero-padded 64-limb rows or n_items uint64 words.  The kernels check every read against the span, so a
+ * table that is not the scanner's gives zeros, never a read outside it. */
+int fbm_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                    uint64_t n_ckpt, uint64_t n_items, void* rows, void* stream);
 
 /* Drops the library's host-side caches: the short path's constant C per (N, |key|) -- kept under a
  * SHA-256 digest of (N, |key|), never the key itself, and zeroed here and on eviction -- and the

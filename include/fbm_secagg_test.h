@@ -123,6 +123,13 @@ int fbm_test_schedule(const uint32_t* key64, uint16_t* ops512, int* n_ops, int* 
  * too small. */
 int fbm_test_short_cache(uint32_t* out, int cap_words);
 
+/* host test hooks (no GPU): the per-item routines of fbm_wire_encode / fbm_wire_decode
+ * (fedbiomed_amd/csrc/fbm_wire.hpp, the source the kernels run) over HOST buffers, same arguments and
+ * argument errors; *total is a host word. */
+int fbm_test_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total);
+int fbm_test_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                         uint64_t n_ckpt, uint64_t n_items, void* rows);
+
 /* The LOM aggregate kernel fbm_lom_aggregate launches for n_parties rows of n elements at y (device
  * pointer; its alignment picks the form), as rocprofv3 names it without the "fbm::" namespace, e.g.
  * "lom_aggregate_ws_kernel<2, 4, 8>": the bench keys its committed HBM-traffic profile on it. */
