@@ -1883,17 +1883,48 @@ def wire_encode(scheme: str, rows, timing: Optional[dict] = None) -> bytes:
     return data
 
 
-def wire_decode(data, arrays: list, timing: Optional[dict] = None) -> List[np.ndarray]:
-    """The packed rows of wire_scan's arrays of the message `data` (fbm_wire_decode): their spans and tables go
-    to the device in one staging block, each is decoded there, and the rows come back as uint32 [n, 64] (jl) /
-    uint64 [n] (lom) host arrays."""
+class WireHandle:
+    """One of wire_upload's arrays on the device: its span's bytes and its table inside the upload's block, which
+    the handle keeps alive.  `event` is recorded on the upload's stream behind the copy: every consumer's stream
+    waits for it and is recorded on the block (`_use`).  `release` drops the block; any later use raises."""
+
+    __slots__ = ("scheme", "n", "base", "span_len", "n_ckpt", "device", "event", "_blk", "_span_off", "_ckpt_off")
+
+    def __init__(self, scheme, n, base, span_len, n_ckpt, blk, span_off, ckpt_off, event):
+        self.scheme, self.n, self.base, self.span_len, self.n_ckpt = scheme, n, base, span_len, n_ckpt
+        self.device, self.event, self._blk, self._span_off, self._ckpt_off = blk.device, event, blk, span_off, ckpt_off
+
+    @property
+    def released(self) -> bool:
+        return self._blk is None
+
+    def release(self) -> None:
+        self._blk = None
+
+    def rows_host(self) -> np.ndarray:
+        """The decoded rows copied back: uint32 [n, 64] (jl) / uint64 [n] (lom)."""
+        r = wire_rows_device(self)
+        return to_host(r).numpy().view(np.uint32 if r.dtype == torch.int32 else np.uint64)
+
+    def _use(self) -> Tuple[ctypes.c_void_p, ctypes.c_void_p]:
+        """The span's and the table's device pointers, ordered behind the upload on the current stream."""
+        if self._blk is None:
+            raise RuntimeError("this update's device bytes have been released")
+        st = torch.cuda.current_stream(self.device)
+        st.wait_event(self.event)
+        self._blk.record_stream(st)
+        base = self._blk.data_ptr()
+        return ctypes.c_void_p(base + self._span_off), ctypes.c_void_p(base + self._ckpt_off)
+
+
+def wire_upload(data, arrays: list, timing: Optional[dict] = None) -> List[WireHandle]:
+    """wire_scan's arrays of the message `data` on the device: their spans (each padded to 8 bytes) and then their
+    tables go up in one staging block on the current stream; one WireHandle per array, all on that block."""
     import time
 
     dev = device()
-    lib = N.load()
     buf = np.frombuffer(data, dtype=np.uint8)
     t0 = time.perf_counter()
-    # one staging block: every span (each padded to 8 bytes), then every table
     s_off, c_off, pos = [], [], 0
     for b, e, _, _, _ in arrays:
         s_off.append(pos)
@@ -1908,22 +1939,61 @@ def wire_decode(data, arrays: list, timing: Optional[dict] = None) -> List[np.nd
         hv[co:co + ck.size * 8] = ck.view(np.uint8)
     with torch.cuda.device(dev):
         blk = host.to(dev, non_blocking=host.is_pinned())
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
         if timing is not None:
             torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        outs = []
-        for (b, e, n, scheme, ck), so, co in zip(arrays, s_off, c_off):
-            rows = torch.empty((n, 64), dtype=torch.int32, device=dev) if scheme == "jl" else \
-                torch.empty(n, dtype=torch.int64, device=dev)
-            base = blk.data_ptr()
-            _call(lib.fbm_wire_decode, _WIRE_SCHEME[scheme], ctypes.c_void_p(base + so), e - b, b,
-                  ctypes.c_void_p(base + co), ck.size, n, _ptr(rows), _stream())
-            outs.append(rows)
-        if timing is not None:
-            torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        res = [to_host(r).numpy().view(np.uint32 if r.dtype == torch.int32 else np.uint64) for r in outs]
-        t3 = time.perf_counter()
     if timing is not None:
-        timing.update(h2d=t1 - t0, kernel=t2 - t1, d2h=t3 - t2)
+        timing["h2d"] = time.perf_counter() - t0
+    return [WireHandle(scheme, n, b, e - b, ck.size, blk, so, co, ev)
+            for (b, e, n, scheme, ck), so, co in zip(arrays, s_off, c_off)]
+
+
+def wire_rows_device(handle: WireHandle, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The packed rows of an uploaded array (fbm_wire_decode) as a device tensor, on the current stream: int32
+    [n, 64] (jl) / int64 [n] (lom).  No host copy.  out: a contiguous tensor of that layout to decode into (the
+    caller orders its earlier uses)."""
+    dev = handle.device
+    shape, dtype = ((handle.n, 64), torch.int32) if handle.scheme == "jl" else ((handle.n,), torch.int64)
+    if out is not None and (out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or
+                            out.device != dev):
+        raise ValueError("wire_rows_device: out must be a contiguous tensor of the scheme's layout on the update's device")
+    with torch.cuda.device(dev):
+        span, ckpt = handle._use()
+        rows = torch.empty(shape, dtype=dtype, device=dev) if out is None else out
+        _call(N.load().fbm_wire_decode, _WIRE_SCHEME[handle.scheme], span, handle.span_len, handle.base, ckpt,
+              handle.n_ckpt, handle.n, _ptr(rows), _stream())
+    return rows
+
+
+def wire_fold_lom(handle: WireHandle, acc: torch.Tensor, first: bool) -> torch.Tensor:
+    """An uploaded "lom" array added to a streaming accumulator straight from its bytes (fbm_wire_fold_lom):
+    acc[i] <- (0 if first else acc[i]) + item i mod 2^64 in place, on the current stream.  acc: int64 [n],
+    contiguous (any slice of a larger buffer), on the handle's device."""
+    if handle.scheme != "lom":
+        raise ValueError("wire_fold_lom takes a 'lom' array")
+    if acc.dtype != torch.int64 or tuple(acc.shape) != (handle.n,) or not acc.is_contiguous() or \
+            acc.device != handle.device:
+        raise ValueError("wire_fold_lom takes a contiguous int64 [n] accumulator on the update's device")
+    with torch.cuda.device(handle.device):
+        span, ckpt = handle._use()
+        _call(N.load().fbm_wire_fold_lom, span, handle.span_len, handle.base, ckpt, handle.n_ckpt, handle.n, _ptr(acc),
+              1 if first else 0, _stream())
+    return acc
+
+
+def wire_decode(data, arrays: list, timing: Optional[dict] = None) -> List[np.ndarray]:
+    """The packed rows of wire_scan's arrays of the message `data` (wire_upload, then fbm_wire_decode of each):
+    the rows come back as uint32 [n, 64] (jl) / uint64 [n] (lom) host arrays."""
+    import time
+
+    handles = wire_upload(data, arrays, timing)
+    t1 = time.perf_counter()
+    outs = [wire_rows_device(h) for h in handles]
+    if timing is not None:
+        torch.cuda.synchronize(device())
+    t2 = time.perf_counter()
+    res = [to_host(r).numpy().view(np.uint32 if r.dtype == torch.int32 else np.uint64) for r in outs]
+    if timing is not None:
+        timing.update(kernel=t2 - t1, d2h=time.perf_counter() - t2)
     return res

@@ -145,6 +145,7 @@ SIGNATURES = {
     "fbm_wire_encode": (c_int, [c_int, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]),
     "fbm_wire_scan": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp]),
     "fbm_wire_decode": (c_int, [c_int, c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp, c_vp]),
+    "fbm_wire_fold_lom": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp, c_int, c_vp]),
 }
 WIRE_JL = 0  # FBM_WIRE_JL
 WIRE_LOM = 1  # FBM_WIRE_LOM
@@ -182,6 +183,7 @@ TEST_SIGNATURES = {
     "fbm_test_lom_aggregate_kernel": (c_int, [c_int, c_u64, c_vp, ctypes.c_char_p, c_int]),
     "fbm_test_wire_encode": (c_int, [c_int, c_vp, c_u64, c_vp, c_u64, c_vp]),
     "fbm_test_wire_decode": (c_int, [c_int, c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp]),
+    "fbm_test_wire_fold_lom": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp, c_int]),
     "fbm_prof_enable": (c_int, [c_int]),
     "fbm_prof_report": (c_int, [ctypes.c_char_p, c_int]),
 }

@@ -1499,6 +1499,40 @@ int fbm_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t
                [&] { return launch_wire_decode(scheme, span, span_len, span_base, ckpt, n_ckpt, n_items, rows, s); });
 }
 
+// the checks fbm_wire_fold_lom and its host hook share (n_items > 0)
+static int wire_fold_lom_checks(const uint8_t* span, const uint64_t* ckpt, uint64_t n_ckpt, uint64_t n_items,
+                                const uint64_t* acc) {
+  if (!span || !ckpt || !acc) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  const uint64_t want = (n_items + FBM_WIRE_LOM_GROUP - 1) / FBM_WIRE_LOM_GROUP;
+  if (n_ckpt != want) {
+    set_error("fbm_wire_fold_lom: %llu checkpoints for %llu items (one per %d items: %llu)", (unsigned long long)n_ckpt,
+              (unsigned long long)n_items, FBM_WIRE_LOM_GROUP, (unsigned long long)want);
+    return FBM_E_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(ckpt) % 8) || (reinterpret_cast<uintptr_t>(acc) % 8)) {
+    set_error("fbm_wire_fold_lom: ckpt / acc not aligned to 8 bytes");
+    return FBM_E_ARG;
+  }
+  if ((n_ckpt + 3) / 4 > 0x7fffffffull) {  // four groups per workgroup (launch_wire_fold_lom checks it again)
+    set_error("fbm_wire_fold_lom: %llu items exceed one launch's grid", (unsigned long long)n_items);
+    return FBM_E_UNSUPPORTED;
+  }
+  return FBM_OK;
+}
+
+int fbm_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt, uint64_t n_ckpt,
+                      uint64_t n_items, uint64_t* acc, int first, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n_items == 0) return FBM_OK;
+  int rc = wire_fold_lom_checks(span, ckpt, n_ckpt, n_items, acc);
+  if (rc) return rc;
+  return timed("wire_fold_lom", s,
+               [&] { return launch_wire_fold_lom(span, span_len, span_base, ckpt, n_ckpt, n_items, acc, first, s); });
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------
@@ -1519,6 +1553,14 @@ int fbm_test_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uin
                          uint64_t n_ckpt, uint64_t n_items, void* rows) {
   int rc = wire_decode_checks(scheme, span, ckpt, n_ckpt, n_items, rows);
   if (rc == FBM_OK && n_items) host_wire_decode(scheme, span, span_len, span_base, ckpt, n_ckpt, n_items, rows);
+  return rc;
+}
+
+int fbm_test_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                           uint64_t n_ckpt, uint64_t n_items, uint64_t* acc, int first) {
+  if (n_items == 0) return FBM_OK;
+  int rc = wire_fold_lom_checks(span, ckpt, n_ckpt, n_items, acc);
+  if (rc == FBM_OK) host_wire_fold_lom(span, span_len, span_base, ckpt, n_ckpt, n_items, acc, first);
   return rc;
 }
 

@@ -352,10 +352,14 @@ int launch_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, u
                        uint64_t* total, hipStream_t s);
 int launch_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt,
                        uint64_t n_ckpt, uint64_t n, void* rows, hipStream_t s);
+int launch_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n_ckpt,
+                         uint64_t n, uint64_t* acc, int first, hipStream_t s);
 // the same per-item routines on the host (test hooks)
 int host_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total);
 void host_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt,
                       uint64_t n_ckpt, uint64_t n, void* rows);
+void host_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n_ckpt,
+                        uint64_t n, uint64_t* acc, int first);
 
 // table slots the encrypt/aggregate kernels need for a given grid
 uint64_t jl_table_slots();

@@ -21,6 +21,13 @@
 //                           into LDS with consecutive lanes on consecutive bytes, lane j walks j items
 //                           there (every lane still walking reads the same LDS byte: a broadcast), one
 //                           coalesced 512-byte store of the 64 words
+//   wire_fold_lom_kernel    the same read side joined to lom_fold_kernel's accumulate side (fbm_wire_fold_lom):
+//                           one wave per group, lane j adds its item to acc[g * 64 + j] -- one coalesced
+//                           512-byte load of the accumulator (none on the first call) and one 512-byte
+//                           store; the decoded words never reach HBM.  Algorithmic bytes per item:
+//                           <= 9 + 1/8 (the table) + 8 read and 8 written when continuing, 8 fewer read on
+//                           the first call.  Bound: HBM by these bytes; measured, the walk's instruction
+//                           issue, as for wire_decode_lom_kernel.
 // Every read of the message is checked against its length and every write against the output's capacity,
 // whatever the table holds.
 #include "fbm_internal.hpp"
@@ -235,6 +242,33 @@ __global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_decode_lom_kernel(const u
   if (g < n_groups && i < n) out[i] = wire_lom_group_item(buf[wave], avail, lane);
 }
 
+// acc[i] = (first ? 0 : acc[i]) + item i  mod 2^64.  A group whose checkpoint lies outside the span has avail = 0,
+// so its items are 0: acc keeps its value (continuing) or becomes 0 (first).  acc is only 8-byte aligned.
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_fold_lom_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                       uint64_t base, const uint64_t* __restrict__ ckpt,
+                                                                       uint64_t n_groups, uint64_t n,
+                                                                       uint64_t* __restrict__ acc, int first) {
+  constexpr int GB = FBM_WIRE_LOM_GROUP * FBM_WIRE_NATIVE_MAX;  // a group's bytes at most
+  __shared__ uint8_t buf[FBM_WIRE_BLOCK / 64][GB];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t g = (uint64_t)blockIdx.x * (FBM_WIRE_BLOCK / 64) + wave;
+  const uint64_t i = g * FBM_WIRE_LOM_GROUP + lane;
+  const bool mine = g < n_groups && i < n;
+  uint64_t a = 0;
+  if (mine && !first) a = acc[i];  // issued ahead of the group's bytes: in flight during the walk
+  uint32_t avail = 0;
+  if (g < n_groups) {
+    const uint64_t c = ckpt[g];
+    if (c >= base && c - base < span_len) {
+      const uint64_t goff = c - base, left = span_len - goff;
+      avail = left < (uint64_t)GB ? (uint32_t)left : (uint32_t)GB;
+      for (uint32_t k = lane; k < avail; k += 64) buf[wave][k] = span[goff + k];
+    }
+  }
+  __syncthreads();
+  if (mine) acc[i] = a + wire_lom_group_item(buf[wave], avail, lane);
+}
+
 static int wire_grid(uint64_t blocks, const char* what, unsigned& g) {
   if (blocks > 0x7fffffffull) {
     set_error("%s: %llu workgroups exceed one launch's grid", what, (unsigned long long)blocks);
@@ -300,6 +334,17 @@ int launch_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint6
   return check_launch("wire_decode_kernel");
 }
 
+int launch_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n_ckpt,
+                         uint64_t n, uint64_t* acc, int first, hipStream_t s) {
+  if (n == 0) return FBM_OK;
+  unsigned g = 0;
+  int rc = wire_grid((n_ckpt + FBM_WIRE_BLOCK / 64 - 1) / (FBM_WIRE_BLOCK / 64), "fbm_wire_fold_lom", g);
+  if (rc) return rc;
+  hipLaunchKernelGGL(wire_fold_lom_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, base, ckpt, n_ckpt, n, acc,
+                     first);
+  return check_launch("wire_fold_lom_kernel");
+}
+
 // ---- the same per-item routines on the host (the test build's hooks) ------------------------------
 int host_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total) {
   uint64_t p = 0;
@@ -347,6 +392,11 @@ void host_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64
     for (int j = 0; j < FBM_WIRE_LOM_GROUP; ++j)
       if (g * FBM_WIRE_LOM_GROUP + j < n) ((uint64_t*)rows)[g * FBM_WIRE_LOM_GROUP + j] = wire_lom_group_item(buf, avail, j);
   }
+}
+
+void host_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n_ckpt,
+                        uint64_t n, uint64_t* acc, int first) {
+  wire_fold_lom_groups(span, span_len, base, ckpt, n_ckpt, n, acc, first, FBM_WIRE_LOM_GROUP);
 }
 
 }  // namespace fbm

@@ -107,4 +107,25 @@ FBM_HD uint64_t wire_lom_group_item(const uint8_t* buf, uint32_t avail, int j) {
   return v;
 }
 
+// wire_fold_lom_kernel's work on the host, group by group (host_wire_fold_lom; tools/wire_fold_check.cpp runs it
+// under the host sanitizers): acc[i] = (first ? 0 : acc[i]) + item i, a group whose checkpoint lies outside the
+// span adding 0; `group` = FBM_WIRE_LOM_GROUP.  Reads span[0, span_len), ckpt[0, n_ckpt), acc[0, n) and no more.
+inline void wire_fold_lom_groups(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt,
+                                 uint64_t n_ckpt, uint64_t n, uint64_t* acc, int first, int group) {
+  const uint64_t gb = (uint64_t)group * FBM_WIRE_NATIVE_MAX;  // a group's bytes at most
+  for (uint64_t g = 0; g < n_ckpt; ++g) {
+    uint32_t avail = 0;
+    const uint8_t* buf = span;
+    if (ckpt[g] >= base && ckpt[g] - base < span_len) {
+      const uint64_t left = span_len - (ckpt[g] - base);
+      avail = (uint32_t)(left < gb ? left : gb);
+      buf = span + (ckpt[g] - base);
+    }
+    for (int j = 0; j < group; ++j) {
+      const uint64_t i = g * (uint64_t)group + j;
+      if (i < n) acc[i] = (first ? 0ull : acc[i]) + wire_lom_group_item(buf, avail, j);
+    }
+  }
+}
+
 }  // namespace fbm

@@ -123,6 +123,19 @@ def _check_int_list(node_params) -> None:
             f"should be of type of integers.")
 
 
+def _resident_handle(update, scheme: str):
+    """The device handle of a `wire.ResidentUpdate` reply of this crypter's scheme."""
+    if update.scheme != scheme:
+        raise FedbiomedSecaggCrypterError(
+            f"{ErrorNumbers.FB624.value}: a resident reply of scheme '{update.scheme}' was given to the "
+            f"'{scheme}' aggregation")
+    return update.handle
+
+
+def _any_resident(params) -> bool:
+    return isinstance(params, list) and any(isinstance(p, wire.ResidentUpdate) for p in params)
+
+
 class JlStreamAggregation:
     """Extension (not in the reference): `SecaggCrypter.aggregate` one reply at a time.
 
@@ -163,6 +176,7 @@ class JlStreamAggregation:
         self._checks = []
         self._start_error = None  # what kept the factor from being issued: finish raises it, in the one-shot's place
         self._copy = None
+        self._scratch, self._scratch_ev = None, None  # resident replies' decoded rows: int32 [n, 64], reused
         self._ended = False
 
     @property
@@ -176,17 +190,22 @@ class JlStreamAggregation:
 
     # ---- replies ---------------------------------------------------------------------------------
     def add(self, node_params) -> None:
-        """One node's reply: its List[int] (the reference's form), a `wire.EncryptedParams`, or its
-        ciphertexts as an int32 [n_ct, 64] device tensor."""
+        """One node's reply: its List[int] (the reference's form), a `wire.EncryptedParams`, its ciphertexts as an
+        int32 [n_ct, 64] device tensor, or a `wire.ResidentUpdate` (`wire.loads_reference(resident=True)`):
+        decoded on the device into a scratch block kept for the next reply, never copied to the host; a
+        ResidentUpdate of the other scheme is FB624."""
         if self._ended:
             raise _ended()
+        resident = isinstance(node_params, wire.ResidentUpdate)
+        if resident:  # (the scanner took unsigned integer forms only: no per-item check)
+            handle = _resident_handle(node_params, "jl")
         is_tensor = isinstance(node_params, torch.Tensor)
         if is_tensor:
             if node_params.dtype != torch.int32 or node_params.dim() != 2 or node_params.shape[1] != 64 or \
                     not node_params.is_cuda:
                 raise FedbiomedSecaggCrypterError(
                     f"{ErrorNumbers.FB624.value}: a tensor reply is an int32 [n_ct, 64] device tensor")
-        else:
+        elif not resident:
             _check_int_list(node_params)
         if not isinstance(self._key, int):
             raise TypeError("The key should be type of integer")
@@ -196,18 +215,25 @@ class JlStreamAggregation:
         if self._n_ct == 0 or self._start_error is not None or not isinstance(self._num_nodes, int) or \
                 self._adds > self._num_nodes:
             return  # finish returns [] or raises: nothing to compute
-        dev = node_params.device if is_tensor else D.device()
+        dev = node_params.device if is_tensor else handle.device if resident else D.device()
         with torch.cuda.device(dev):
             if self._acc is None and not self._begin(self._n_ct, dev):
                 return
             m = self._n_ct
-            rows = node_params[:m] if is_tensor else self._upload(node_params, m, dev)
+            if resident:
+                rows = self._decode(handle, dev)[:m]
+            else:
+                rows = node_params[:m] if is_tensor else self._upload(node_params, m, dev)
             chunk = D.jl_chunk_ct()
             seed = self._num_nodes if self._folded == 0 else 0
             for k0 in range(0, m, chunk):  # (as jl_aggregate loops: at most FBM_JL_MAX_CT per library call)
                 k1 = min(m, k0 + chunk)
                 D.jl_fold(self._acc[k0:k1], rows[k0:k1], self._biprime, seed_ops=seed)
             self._folded += 1
+            if resident:
+                self._scratch_ev = torch.cuda.Event()
+                self._scratch_ev.record(torch.cuda.current_stream(dev))
+                return  # (no list to make: a resident reply's caller is not a list caller)
             if self._folded == 1 and not is_tensor and self._pool is None:
                 # a list caller's finish() returns a list: its float objects made now, beside the factor's
                 # exponentiations, their values written in place by finish (prepare_aggregate's pool, made here)
@@ -245,6 +271,18 @@ class JlStreamAggregation:
         self._acc = torch.empty((n_ct, 64), dtype=torch.int32, device=dev)
         return True
 
+    def _decode(self, handle, dev) -> torch.Tensor:
+        """A resident reply's rows, decoded on the device into a scratch block this object keeps for the next
+        reply of the same size.  The block's earlier use (the last reply's folds, perhaps on another stream) is
+        ordered before the decode by an event."""
+        main = torch.cuda.current_stream(dev)
+        if self._scratch is None or self._scratch.shape[0] != handle.n:
+            self._scratch = torch.empty((handle.n, 64), dtype=torch.int32, device=dev)
+        elif self._scratch_ev is not None:
+            main.wait_event(self._scratch_ev)
+        self._scratch.record_stream(main)
+        return D.wire_rows_device(handle, out=self._scratch)
+
     def _upload(self, lst, m, dev) -> torch.Tensor:
         """The first m ciphertexts of one party's list -> a pinned buffer (host threads) -> the device, on a
         copy stream the current stream then waits for.  Both buffers go back to their allocators once the
@@ -268,7 +306,7 @@ class JlStreamAggregation:
     def _scrub(self) -> None:
         own, self._own = self._own, None
         _scrub_prep(own, ("factor",))
-        self._acc = self._factors = self._stripes = self._pool = None
+        self._acc = self._factors = self._stripes = self._pool = self._scratch = None
         self._ended = True
 
     def abort(self) -> None:
@@ -356,7 +394,8 @@ class JlStreamAggregation:
 class LomStreamAggregation:
     """Extension (not in the reference): `SecaggLomCrypter.aggregate` one reply at a time -- the sum modulo
     2^64 kept in one device accumulator ([n] uint64) instead of the [P, n] block.  `add` takes a List[int], a
-    `wire.EncryptedParams` or an int64 [n] device tensor; its type and range errors are the one-shot's,
+    `wire.EncryptedParams`, an int64 [n] device tensor or a `wire.ResidentUpdate` (folded straight from its
+    bytes on the device; one of the other scheme is FB624); its type and range errors are the one-shot's,
     raised at `add`; replies of unequal lengths (the one-shot's numpy conversion refuses them), a bad
     total_sample_size and the device's status words are raised at `finish`.  No reply, or empty ones, make
     `finish` return [].  After `finish` or `abort` every method raises FedbiomedSecaggCrypterError.  All state
@@ -384,6 +423,8 @@ class LomStreamAggregation:
     def add(self, node_params) -> None:
         if self._ended:
             raise _ended()
+        if isinstance(node_params, wire.ResidentUpdate):
+            return self._add_resident(node_params)
         is_tensor = isinstance(node_params, torch.Tensor)
         if is_tensor:
             if node_params.dtype != torch.int64 or node_params.dim() != 1 or not node_params.is_cuda:
@@ -422,6 +463,23 @@ class LomStreamAggregation:
             D.lom_fold(self._acc, row, first)
             if first and not is_tensor and getattr(self._crypter, "_lom_agg_pool", None) is None:
                 self._pool = D.float_pool(n)  # a list caller's output floats, made while replies still arrive
+
+    def _add_resident(self, update) -> None:
+        """A `wire.ResidentUpdate`: folded straight from its bytes on the device (fbm_wire_fold_lom) -- no rows
+        decoded to HBM, no host copy, no per-item check (the scanner took unsigned integer forms only) and, as
+        for a tensor reply, no float objects made ahead of `finish`.  The length rules are a list reply's."""
+        handle = _resident_handle(update, "lom")
+        n = len(update)
+        if self._n is None:
+            self._n = n
+        elif n != self._n:
+            self._ragged = True
+        if self._ragged or n == 0:
+            return
+        first = self._acc is None
+        if first:
+            self._acc = torch.empty(n, dtype=torch.int64, device=handle.device)
+        D.wire_fold_lom(handle, self._acc, first)
 
     def abort(self) -> None:
         if self._ended:
@@ -808,7 +866,16 @@ class SecaggCrypter:
     def aggregate(self, current_round: int, num_nodes: int, params: List[List[int]], key: int, biprime: int,
                   total_sample_size: int, clipping_range: Union[int, None] = None, num_expected_params: int = 1,
                   target_range: Optional[int] = None) -> List[float]:
-        """Decrypts the sum of the parties' ciphertexts (reference `_secagg_crypter.py:139-230`)."""
+        """Decrypts the sum of the parties' ciphertexts (reference `_secagg_crypter.py:139-230`).  Where a reply is
+        a `wire.ResidentUpdate`, the replies go through `begin_aggregate` / `add` / `finish` in their order: the
+        same result bit for bit, with the stream's error sites (a reply's checks as it is added, the rest at
+        the end)."""
+        if _any_resident(params):
+            agg = self.begin_aggregate(current_round, num_nodes, key, biprime, total_sample_size, clipping_range,
+                                       num_expected_params, target_range)
+            for p in params:
+                agg.add(p)
+            return agg.finish()
         start = time.process_time()
         if len(params) != num_nodes:
             raise FedbiomedSecaggCrypterError(
@@ -1109,6 +1176,11 @@ class SecaggLomCrypter(SecaggCrypter):
 
     def aggregate(self, params: List[List[int]], total_sample_size: int, clipping_range: Union[int, None] = None,
                   target_range: Optional[int] = None) -> List[float]:
+        if _any_resident(params):  # as SecaggCrypter.aggregate: the stream, with its error sites
+            agg = self.begin_aggregate(total_sample_size, clipping_range, target_range)
+            for p in params:
+                agg.add(p)
+            return agg.finish()
         start = time.process_time()
         _check_int_lists(params)
         num_nodes = len(params)

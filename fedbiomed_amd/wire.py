@@ -27,7 +27,10 @@ working.  With it enabled:
 The blob needs the hook on both ends.  Where only one side is patched, `dumps_reference` /
 `loads_reference` (below) write and read the reference's own per-item encoding on the device instead,
 byte for byte what the stock `Serializer` writes, so the peer needs nothing ("One
-patched side"); `reference_stats` counts the updates that took that path and those left to msgpack.
+patched side"); `reference_stats` counts the updates that took that path and those left to msgpack.  A researcher
+that only adds a reply to the aggregate reads it with ``loads_reference(..., resident=True)``: the update comes
+back as a `ResidentUpdate` -- its bytes on the device, no rows on the host, no Python ints -- and
+`begin_aggregate().add` / `aggregate` fold it from there.
 
 `ChunkAssembler` is the other half of §8(f)2: the gRPC transport streams a serialized message in
 chunks of `MAX_MESSAGE_BYTES_LENGTH` (4 MB) and the receiver rebuilds it with ``reply += chunk``
@@ -201,18 +204,77 @@ class ChunkAssembler:
 # `:140-149`): one msgpack item per ciphertext / element.  `dumps_reference` / `loads_reference` produce and
 # consume exactly those bytes from the packed device form (the C ABI's fbm_wire_encode / fbm_wire_scan /
 # fbm_wire_decode), so only this side needs its two Serializer lines ("One patched side").
-_STATS = {"fast": 0, "fallback": 0}
+_STATS = {"fast": 0, "fallback": 0, "resident": 0}
 _LAST: Dict[str, Any] = {}  # the last call's phases in seconds (tools/wire_ref_ab.py)
+_PHASE_TIMING = False  # tools/wire_ref_ab.py sets it: the resident upload then synchronises to time its "h2d"
 
 
 def reference_stats(reset: bool = False) -> Dict[str, Any]:
-    """Updates that took the device path ("fast") and updates or messages that took msgpack's ("fallback")
-    since the last reset, and the last call's phase times ("last": scan / h2d / kernel / d2h seconds)."""
+    """Updates that took the device path ("fast"), updates that stayed on the device (`loads_reference` with
+    ``resident=True``: "resident") and updates or messages that took msgpack's ("fallback") since the last
+    reset, and the last call's phase times ("last": scan / h2d / kernel / d2h seconds)."""
     out = dict(_STATS, last=dict(_LAST))
     if reset:
-        _STATS.update(fast=0, fallback=0)
+        _STATS.update(fast=0, fallback=0, resident=0)
         _LAST.clear()
     return out
+
+
+class ResidentUpdate:
+    """An update `loads_reference(..., resident=True)` read: its bytes and the scanner's table on the device, no
+    rows decoded and no Python int made.  `begin_aggregate().add` and `aggregate` fold it from there.  Not a
+    list, but a consumer that treats it as the reference's ``List[int]`` (iteration, indexing, ``==``) still
+    sees exactly those values: the first such use decodes, copies back and builds the ints (`tolist`, once).
+    `release` drops the device bytes; what needs them afterwards raises RuntimeError."""
+
+    __slots__ = ("scheme", "n_items", "_handle", "_values")
+
+    def __init__(self, scheme: str, n_items: int, handle):
+        if scheme not in ("jl", "lom"):
+            raise ValueError("scheme must be 'jl' or 'lom'")
+        self.scheme, self.n_items, self._handle, self._values = scheme, int(n_items), handle, None
+
+    @property
+    def handle(self):
+        """The device handle (`_device.WireHandle`) `_device.wire_fold_lom` / `wire_rows_device` take."""
+        if self._handle is None or self._handle.released:
+            raise RuntimeError("this ResidentUpdate's device bytes have been released")
+        return self._handle
+
+    @property
+    def materialised(self) -> bool:
+        """Whether the Python ints have been made."""
+        return self._values is not None
+
+    def tolist(self) -> list:
+        """The reference's ints: what `EncryptedParams.from_packed` holds for the same rows.  Made once."""
+        if self._values is None:
+            self._values = list(EncryptedParams.from_packed(self.scheme, self.handle.rows_host()))
+        return self._values
+
+    def release(self) -> None:
+        if self._handle is not None:
+            self._handle.release()
+        self._handle = None
+
+    def __len__(self) -> int:
+        return self.n_items
+
+    def __iter__(self):
+        return iter(self.tolist())
+
+    def __getitem__(self, i):
+        return self.tolist()[i]
+
+    def __eq__(self, other):
+        if isinstance(other, ResidentUpdate):
+            other = other.tolist()
+        return self.tolist() == other if isinstance(other, list) else NotImplemented
+
+    __hash__ = None
+
+    def __repr__(self) -> str:
+        return f"ResidentUpdate(scheme={self.scheme!r}, n_items={self.n_items}, materialised={self.materialised})"
 
 
 def _reference_default(obj: Any) -> Dict[str, Any]:
@@ -327,13 +389,29 @@ def _hook_reads_ints(object_hook) -> bool:
     return type(v) is int and v == 1 << 71
 
 
-def loads_reference(data: bytes, object_hook=None, min_items: int = 1024) -> Any:
+def _upload_arrays(data: bytes, arrays: list) -> list:
+    """The device call of `loads_reference(resident=True)` (the same seam): one handle per array, with
+    ``rows_host()``, ``release()`` and ``released``."""
+    from . import _device as D
+
+    if not _PHASE_TIMING:  # nothing waits for the upload here: the consumers' streams do, through its event
+        return D.wire_upload(data, arrays)
+    timing: Dict[str, float] = {}
+    handles = D.wire_upload(data, arrays, timing)
+    _LAST.update(timing)
+    return handles
+
+
+def loads_reference(data: bytes, object_hook=None, min_items: int = 1024, resident: bool = False) -> Any:
     """``msgpack.unpackb(data, object_hook=object_hook, strict_map_key=False)`` with every integer array of at
     least `min_items` items the host scanner records read on the device: it comes back as an `EncryptedParams`
     (which compares as the list of ints msgpack would have made) whose ``packed`` is ready for `aggregate` /
     `begin_aggregate().add`.  Arrays the scanner refuses stay msgpack's; where it records nothing or gives up,
     this is exactly that call.  (Arrays of the big-int map are taken only when `object_hook` reads that map as
-    the reference's does.)"""
+    the reference's does.)
+
+    ``resident=True``: each recorded array comes back as a `ResidentUpdate` instead -- its bytes uploaded, nothing
+    decoded, copied back or made into ints; `begin_aggregate().add` and `aggregate` fold it on the device."""
     import os
     import time
 
@@ -350,7 +428,7 @@ def loads_reference(data: bytes, object_hook=None, min_items: int = 1024) -> Any
     if not arrays:
         _STATS["fallback"] += 1
         return msgpack.unpackb(data, object_hook=object_hook, strict_map_key=False)
-    rows = _decode_arrays(data, arrays)
+    rows = _upload_arrays(data, arrays) if resident else _decode_arrays(data, arrays)
     token = "fedbiomed_amd.ref." + os.urandom(12).hex()
     view = memoryview(data)
     parts, pos = [], 0
@@ -362,6 +440,9 @@ def loads_reference(data: bytes, object_hook=None, min_items: int = 1024) -> Any
     def hook(o):
         if o.get("__type__") == token:
             i = o["value"]
+            if resident:
+                _STATS["resident"] += 1
+                return ResidentUpdate(arrays[i][3], arrays[i][2], rows[i])
             _STATS["fast"] += 1
             return EncryptedParams.from_packed(arrays[i][3], rows[i])
         return o if object_hook is None else object_hook(o)

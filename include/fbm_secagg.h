@@ -468,6 +468,20 @@ int fbm_wire_scan(const uint8_t* data, uint64_t len, uint64_t min_items, fbm_wir
 int fbm_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
                     uint64_t n_ckpt, uint64_t n_items, void* rows, void* stream);
 
+/* Decode and fold in one pass: a recorded FBM_WIRE_LOM array added to a streaming accumulator (fbm_lom_fold's)
+ * straight from its bytes; the decoded words are never written out:
+ *     acc[i] <- (first ? 0 : acc[i]) + item i  mod 2^64,  i < n_items
+ * span / span_len / span_base / ckpt / n_ckpt as fbm_wire_decode's for FBM_WIRE_LOM; acc: device, n_items
+ * uint64 (8-byte aligned: any element offset of a larger buffer), in place; first != 0: its contents are
+ * ignored.  Every read is checked against the span: a group whose checkpoint lies outside it, or an item
+ * that is no native form or runs past the span, counts as 0 (acc[i] keeps its value, or becomes 0 when
+ * first); no access falls outside span, ckpt and acc, whatever the table holds.
+ * n_items == 0 is FBM_OK; then a null pointer, n_ckpt != ceil(n_items / FBM_WIRE_LOM_GROUP) and a ckpt or acc
+ * off an 8-byte boundary are FBM_E_ARG, and more workgroups than one launch's grid FBM_E_UNSUPPORTED -- all
+ * before any kernel. */
+int fbm_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                      uint64_t n_ckpt, uint64_t n_items, uint64_t* acc, int first, void* stream);
+
 /* Drops the library's host-side caches: the short path's constant C per (N, |key|) -- kept under a
  * SHA-256 digest of (N, |key|), never the key itself, and zeroed here and on eviction -- and the
  * per-biprime public parameters.  The reference keeps nothing between calls (a fresh

@@ -129,6 +129,10 @@ int fbm_test_short_cache(uint32_t* out, int cap_words);
 int fbm_test_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total);
 int fbm_test_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
                          uint64_t n_ckpt, uint64_t n_items, void* rows);
+/* fbm_wire_fold_lom over HOST buffers (host_wire_fold_lom, the same per-item routine), same arguments and
+ * argument errors. */
+int fbm_test_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                           uint64_t n_ckpt, uint64_t n_items, uint64_t* acc, int first);
 
 /* The LOM aggregate kernel fbm_lom_aggregate launches for n_parties rows of n elements at y (device
  * pointer; its alignment picks the form), as rocprofv3 names it without the "fbm::" namespace, e.g.

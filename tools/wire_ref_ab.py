@@ -17,6 +17,20 @@ is the summary and the condition fixed in advance: per leg, the slowest new run 
 reference run.  Both sides' outputs are compared before anything is timed.
 
     python tools/wire_ref_ab.py [--elements 10000000] [--runs 5] [--out profiles/wire_reference_ab.jsonl]
+
+--resident: the two "researcher takes one reply" legs instead (profiles/wire_resident_ab.jsonl), same protocol:
+
+  leg          new                                                  reference (what a stock researcher runs)
+  lom_take     loads_reference(bytes, hook, resident=True), add     unpackb(bytes, object_hook=_object_hook), add(list)
+  jl_take      likewise at ceil(10M / 30) ciphertexts
+
+each into a running accumulator (`begin_aggregate()` with one reply already folded in), every run ending in a device
+synchronise; the accumulators of both sides are compared first.  The new side's phases: `scan`, `h2d` (staging +
+upload, synchronised for the timing), `fold` (add + synchronise: the kernels).
+
+--kernels: for a kernel trace (`rocprofv3 --kernel-trace --stats -- python tools/wire_ref_ab.py --kernels`): one LOM
+update's bytes uploaded once, then four launches of wire_fold_lom_kernel (continuing) and four of
+wire_decode_lom_kernel + lom_fold_kernel on the same bytes.
 """
 import argparse
 import gc
@@ -55,12 +69,139 @@ def timed(fn):
     return time.perf_counter() - t0, out
 
 
+def _lom_words(rng, n):
+    return rng.integers(0, 2**64, size=n, dtype=np.uint64)
+
+
+def _jl_rows(rng, n_ct):
+    rows = rng.integers(0, 2**32, size=(n_ct, 64), dtype=np.uint64).astype(np.uint32)
+    rows[:, 63] &= 0x3FFFFFFF  # below 2^2046 <= N^2: a ciphertext's range
+    return rows
+
+
+def kernels(a):
+    """The launches a kernel trace compares (see the module's docstring)."""
+    import torch
+
+    from fedbiomed_amd import _device as D
+
+    dev = D.device()
+    data = msgpack.packb({"node_id": "node-00", "params": _lom_words(np.random.default_rng(2026), a.elements).tolist()})
+    arrays = D.wire_scan(data, 1024)
+    (h,) = D.wire_upload(data, arrays)
+    acc = torch.zeros(h.n, dtype=torch.int64, device=dev)
+    ref = torch.zeros(h.n, dtype=torch.int64, device=dev)
+    rows = torch.empty(h.n, dtype=torch.int64, device=dev)
+    for _ in range(4):
+        D.wire_fold_lom(h, acc, False)
+        torch.cuda.synchronize()
+    for _ in range(4):
+        D.lom_fold(ref, D.wire_rows_device(h, out=rows), False)
+        torch.cuda.synchronize()
+    assert torch.equal(acc, ref)
+    print(json.dumps({"kernels": "4 x wire_fold_lom_kernel, 4 x (wire_decode_lom_kernel + lom_fold_kernel)", "items": h.n}))
+    return 0
+
+
+def resident(a):
+    """The two "researcher takes one reply" legs (see the module's docstring)."""
+    import torch
+
+    from fedbiomed_amd import _device as D
+    from fedbiomed_amd import workload as W
+    from fedbiomed_amd.secagg import SecaggCrypter, SecaggLomCrypter
+
+    dev = D.device()
+    wire._PHASE_TIMING = True
+    rng = np.random.default_rng(2026)
+    n_ct = -(-a.elements // 30)
+    sk0 = -sum(W.jl_user_key(p) for p in range(3))
+    lines, legs = [], {}
+    for scheme in ("lom", "jl"):
+        packed = _lom_words(rng, a.elements) if scheme == "lom" else _jl_rows(rng, n_ct)
+        first = torch.from_numpy(packed.view(np.int64 if scheme == "lom" else np.int32)).to(dev)
+        data = msgpack.packb({"node_id": "node-00", "params": list(wire.EncryptedParams.from_packed(scheme, packed)),
+                              "n": len(packed)}, default=ref_default, strict_types=True)
+        del packed
+
+        def begin():  # a running accumulator: one reply folded in, the JL factor done
+            agg = SecaggLomCrypter(W.LOM_NONCE).begin_aggregate(1000) if scheme == "lom" else \
+                SecaggCrypter().begin_aggregate(3, 64, sk0, W.BIPRIME0, 1000, num_expected_params=a.elements)
+            agg.add(first)
+            torch.cuda.synchronize()
+            return agg
+
+        aggs = {"new": begin(), "reference": begin()}
+        phases = {}
+
+        def new():
+            t0 = time.perf_counter()
+            upd = wire.loads_reference(data, object_hook=ref_hook, resident=True)["params"]
+            phases.update(wire.reference_stats()["last"])
+            t1 = time.perf_counter()
+            aggs["new"].add(upd)
+            torch.cuda.synchronize()
+            phases["fold"] = time.perf_counter() - t1
+            phases["loads"] = t1 - t0
+            return upd
+
+        def ref():
+            lst = msgpack.unpackb(data, object_hook=ref_hook, strict_map_key=False)["params"]
+            aggs["reference"].add(lst)
+            torch.cuda.synchronize()
+            return lst
+
+        upd = new()
+        ref()
+        assert type(upd) is wire.ResidentUpdate and not upd.materialised
+        assert torch.equal(aggs["new"]._acc, aggs["reference"]._acc), f"{scheme}: the accumulators differ"
+        del upd
+        leg = f"{scheme}_take"
+        times = {"new": [], "reference": []}
+        for run in range(a.runs):
+            for impl, fn in (("new", new), ("reference", ref)):
+                dt, out = timed(fn)
+                del out
+                rec = {"leg": leg, "impl": impl, "run": run, "ms": round(dt * 1e3, 3), "items": len(first),
+                       "message_bytes": len(data)}
+                if impl == "new":
+                    rec["phases_ms"] = {k: round(v * 1e3, 3) for k, v in phases.items()}
+                times[impl].append(dt * 1e3)
+                lines.append(rec)
+                print(json.dumps(rec), flush=True)
+        assert torch.equal(aggs["new"]._acc, aggs["reference"]._acc), f"{scheme}: the accumulators differ after the runs"
+        legs[leg] = {"new_ms": [round(t, 3) for t in times["new"]], "reference_ms": [round(t, 3) for t in times["reference"]],
+                     "slowest_new_ms": round(max(times["new"]), 3), "fastest_reference_ms": round(min(times["reference"]), 3),
+                     "holds": max(times["new"]) < min(times["reference"]),
+                     "median_ratio": round(float(np.median(times["reference"]) / np.median(times["new"])), 2)}
+        for g in aggs.values():
+            g.abort()
+        del aggs, first, data
+    st = wire.reference_stats()
+    summary = {"summary": legs, "condition": "per leg: slowest new run < fastest reference run",
+               "holds": all(v["holds"] for v in legs.values()), "elements": a.elements, "runs": a.runs,
+               "resident": st["resident"], "fallback": st["fallback"], "msgpack": ".".join(map(str, msgpack.version))}
+    lines.append(summary)
+    print(json.dumps(summary), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.writelines(json.dumps(ln) + "\n" for ln in lines)
+    return 0 if summary["holds"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--elements", type=int, default=10_000_000)
     ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wire_reference_ab.jsonl"))
+    ap.add_argument("--resident", action="store_true")
+    ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "wire_resident_ab.jsonl" if a.resident else "wire_reference_ab.jsonl")
+    if a.kernels:
+        return kernels(a)
+    if a.resident:
+        return resident(a)
 
     from fedbiomed_amd import _device as D
 
