@@ -170,6 +170,7 @@ TEST_SIGNATURES = {
     "fbm_test_split_consts": (c_int, [c_vp] * 11),
     "fbm_jl_engine_for": (c_int, [c_u64]),
     "fbm_test_true_div_big": (c_int, [c_vp, c_u64, c_vp, c_int, c_int, c_vp]),
+    "fbm_test_true_div_u128": (c_int, [c_vp, c_u64, c_u64, c_vp]),
     "fbm_test_widen16": (c_int, [ctypes.c_uint16, c_int, c_vp]),
     "fbm_test_narrow": (c_int, [c_dbl, c_int, c_vp]),
     "fbm_test_modinv": (c_int, [c_vp, c_vp, c_vp, c_vp]),

@@ -1615,6 +1615,16 @@ int fbm_test_true_div_big(const uint64_t* x, uint64_t n, const uint32_t* k, int 
   return FBM_OK;
 }
 
+int fbm_test_true_div_u128(const uint64_t* x, uint64_t n, uint64_t k, double* out) {
+  if (k == 0 || (n > 0 && (!x || !out))) {
+    set_error("fbm_test_true_div_u128: null pointer or zero divisor");
+    return FBM_E_ARG;
+  }
+  for (uint64_t i = 0; i < n; ++i)
+    out[i] = fbm_true_div_u128(((unsigned __int128)x[2 * i + 1] << 64) | x[2 * i], k);
+  return FBM_OK;
+}
+
 int fbm_test_widen16(uint16_t bits, int dtype, double* out) {
   if (!out || (dtype != FBM_F16 && dtype != FBM_BF16)) {
     set_error("fbm_test_widen16: dtype must be FBM_F16 or FBM_BF16, out not NULL");

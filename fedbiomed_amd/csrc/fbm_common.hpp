@@ -59,7 +59,7 @@ FBM_HD uint32_t fbm_bitlen128(uint64_t hi, uint64_t lo) {
   return 0u;
 }
 
-// Python `a / b` for non-negative ints a (< 2^100) and b (1 <= b < 2^64): the correctly
+// Python `a / b` for non-negative ints a (< 2^128) and b (1 <= b < 2^64): the correctly
 // rounded (round-half-even) double of the exact quotient -- CPython's long_true_divide.
 // Fast path when both operands are exact doubles (IEEE division is correctly rounded).
 FBM_HD double fbm_true_div_u128(unsigned __int128 a, uint64_t b) {

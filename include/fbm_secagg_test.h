@@ -23,6 +23,10 @@ extern "C" {
 
 /* host test hook (no GPU): fbm_int_true_div_big's per-value arithmetic on host arrays. */
 int fbm_test_true_div_big(const uint64_t* x, uint64_t n, const uint32_t* k, int k_words, int negative, double* out);
+/* host test hook (no GPU): the narrow-divisor routine of the average step (fbm_true_div_u128,
+ * fedbiomed_amd/csrc/fbm_common.hpp: the source the LOM aggregate, the JL decode and fbm_int_ops run) on host
+ * arrays -- out[i] = x[i] / k, Python's int / int, for n (lo, hi) pairs x[i] < 2^128 and 1 <= k < 2^64. */
+int fbm_test_true_div_u128(const uint64_t* x, uint64_t n, uint64_t k, double* out);
 
 /* host test hooks (no GPU): the conversions of the 16-bit inputs and the narrow outputs, the same
  * host/device source the kernels run (fedbiomed_amd/csrc/fbm_common.hpp).  fbm_test_widen16: *out = the exact

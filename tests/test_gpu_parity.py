@@ -47,16 +47,20 @@ def test_true_division_golden(golden, dev):
     # average step e / W for e < 2^64 through the LOM aggregate kernel (one party, sums = e)
     from fedbiomed_amd import _device as D
 
+    asserted = 0
     for case in golden["quantize"]["true_div"]:
         e, w = I(case["e"]), I(case["w"])
         if e >= 2**64:
             continue
         Y = D.u64_to_device([[e]], dev)
-        # out = -c + step * trunc(e/w): pick c, T so that out == trunc(e/w) exactly when it is small
-        out, _ = D.lom_aggregate(Y, w, clip=1, target=3)  # step = 2/2 = 1.0, -c = -1
+        # out = -c + step * trunc(e/w) with c = 2^52, T = 2^53 + 1: step = 2^53 / 2^53 = 1.0, -c = -2^52, so
+        # out == trunc(q) - 2^52 exactly for every q < 2^64 (an integer below 2^53, or a multiple of q's ulp)
         q = F(case["q"])
-        if q < 2**53:
-            assert out.item() == -1.0 + float(int(q)), (e, w)
+        assert q < 2.0**64, (e, w)
+        out, _ = D.lom_aggregate(Y, w, clip=2**52, target=2**53 + 1)
+        assert fbits(out.item()) == fbits(float(int(q)) - 2.0**52), (e, w)
+        asserted += 1
+    assert asserted >= 100
 
 
 def test_quantize_reference_tests(dev):
