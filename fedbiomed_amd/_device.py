@@ -19,7 +19,7 @@ import operator
 import os
 import sys
 import threading
-from typing import List, Optional, Sequence, Tuple
+from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -1886,20 +1886,25 @@ def wire_encode(scheme: str, rows, timing: Optional[dict] = None) -> bytes:
 class WireHandle:
     """One of wire_upload's arrays on the device: its span's bytes and its table inside the upload's block, which
     the handle keeps alive.  `event` is recorded on the upload's stream behind the copy: every consumer's stream
-    waits for it and is recorded on the block (`_use`).  `release` drops the block; any later use raises."""
+    waits for it and is recorded on the block (`_use`).  `release` drops the block; any later use raises.
 
-    __slots__ = ("scheme", "n", "base", "span_len", "n_ckpt", "device", "event", "_blk", "_span_off", "_ckpt_off")
+    An array wire_scan_resident left to the device tokenizer has its span inside the uploaded message and its table
+    in a tensor of its own (`tab`), which the tokenizer wrote: the handle keeps both alive, `event` lies behind the
+    upload and the tokenizer, consumers' streams are recorded on both, `release` drops both."""
 
-    def __init__(self, scheme, n, base, span_len, n_ckpt, blk, span_off, ckpt_off, event):
+    __slots__ = ("scheme", "n", "base", "span_len", "n_ckpt", "device", "event", "_blk", "_span_off", "_ckpt_off", "_tab")
+
+    def __init__(self, scheme, n, base, span_len, n_ckpt, blk, span_off, ckpt_off, event, tab=None):
         self.scheme, self.n, self.base, self.span_len, self.n_ckpt = scheme, n, base, span_len, n_ckpt
         self.device, self.event, self._blk, self._span_off, self._ckpt_off = blk.device, event, blk, span_off, ckpt_off
+        self._tab = tab
 
     @property
     def released(self) -> bool:
         return self._blk is None
 
     def release(self) -> None:
-        self._blk = None
+        self._blk = self._tab = None
 
     def rows_host(self) -> np.ndarray:
         """The decoded rows copied back: uint32 [n, 64] (jl) / uint64 [n] (lom)."""
@@ -1914,6 +1919,9 @@ class WireHandle:
         st.wait_event(self.event)
         self._blk.record_stream(st)
         base = self._blk.data_ptr()
+        if self._tab is not None:
+            self._tab.record_stream(st)
+            return ctypes.c_void_p(base + self._span_off), ctypes.c_void_p(self._tab.data_ptr())
         return ctypes.c_void_p(base + self._span_off), ctypes.c_void_p(base + self._ckpt_off)
 
 
@@ -1947,6 +1955,111 @@ def wire_upload(data, arrays: list, timing: Optional[dict] = None) -> List[WireH
         timing["h2d"] = time.perf_counter() - t0
     return [WireHandle(scheme, n, b, e - b, ck.size, blk, so, co, ev)
             for (b, e, n, scheme, ck), so, co in zip(arrays, s_off, c_off)]
+
+
+def wire_scan_deferred(data, min_items: int, defer_items: int, resolved) -> Tuple[str, Any]:
+    """One pass of fbm_wire_scan_deferred over a message, no device call: ("pending", (begin, first, n_items)) for
+    the deferral candidate that `resolved` (end offsets, 0: walk it on the host) does not answer yet, else ("done",
+    arrays) with wire_scan's list -- the checkpoints of an array left to the device are None -- or ("done", None)
+    where the scan gives up."""
+    lib = N.load()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    n = buf.size
+    n_arr, n_ck = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    res = np.array(list(resolved), dtype=np.uint64)
+    pend = N.WirePending()
+    for a_cap, c_cap in ((1024, n // 8 + 1024), (n // max(int(min_items), 1) + 1, n + 16)):
+        arrays = (N.WireArray * a_cap)()
+        ckpt = np.empty(c_cap, dtype=np.uint64)
+        rc = lib.fbm_wire_scan_deferred(_np_ptr(buf) if n else None, n, max(int(min_items), 1), max(int(defer_items), 0),
+                                        _np_ptr(res) if res.size else None, res.size, ctypes.addressof(arrays), a_cap,
+                                        ctypes.addressof(n_arr), _np_ptr(ckpt), c_cap, ctypes.addressof(n_ck),
+                                        ctypes.addressof(pend))
+        if rc == N.FBM_E_RANGE:
+            continue
+        if rc == N.WIRE_PENDING:
+            return "pending", (int(pend.begin), int(pend.first), int(pend.n_items))
+        if rc == N.FBM_E_UNSUPPORTED:
+            return "done", None
+        if rc != N.FBM_OK:
+            _raise(rc)
+        return "done", [(int(a.begin), int(a.end), int(a.n_items), _WIRE_NAME[a.scheme],
+                         None if a.pad else ckpt[a.ckpt_first:a.ckpt_first + a.ckpt_count]) for a in arrays[:n_arr.value]]
+    return "done", None
+
+
+def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[dict] = None,
+                       counts: Optional[dict] = None, sync_phases: bool = False) -> Tuple[Optional[list], dict]:
+    """wire_scan with the arrays of at least `defer_items` native items tokenized on the device
+    (fbm_wire_scan_deferred + fbm_wire_tokenize_lom).  At the first such array the message from that array's
+    header to its end goes up once, through a pinned buffer on the current stream; the tokenizer runs behind the
+    upload, its two result words come back in one small synchronous copy and the scanner runs again with the
+    answer.  An array the tokenizer refuses (not all native, cut off, outside its domain) is walked on the host.
+    Returns (arrays, handles): wire_scan's list -- checkpoints None where the table is on the device -- and a
+    WireHandle per such array under its index; (None, {}) where the scan gives up.  No device call while no array
+    qualifies.  timing: receives scan / h2d / devscan seconds (sync_phases: the upload is synchronised, so that h2d
+    is its time and not its enqueue); counts: device_scan / device_scan_refused are incremented."""
+    import time
+
+    lib = N.load()
+    size = len(data)
+    resolved: list = []
+    tables: dict = {}  # an array's begin -> its table on the device
+    blk, blk_base, dev = None, 0, None
+    t_scan = t_h2d = t_dev = 0.0
+    while True:
+        t0 = time.perf_counter()
+        kind, val = wire_scan_deferred(data, min_items, defer_items, resolved)
+        t_scan += time.perf_counter() - t0
+        if kind != "pending":
+            arrays = val
+            break
+        begin, first, n_items = val
+        t0 = time.perf_counter()
+        if blk is None:
+            dev, blk_base = device(), begin
+            host = host_empty(size - begin, torch.uint8)
+            host.numpy()[...] = np.frombuffer(data, dtype=np.uint8)[begin:]
+            with torch.cuda.device(dev):
+                blk = host.to(dev, non_blocking=host.is_pinned())
+                if sync_phases:
+                    torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        t_h2d += t1 - t0
+        n_ck = (n_items + N.WIRE_LOM_GROUP - 1) // N.WIRE_LOM_GROUP
+        span_len = size - blk_base
+        with torch.cuda.device(dev):
+            tab = torch.empty(n_ck, dtype=torch.int64, device=dev)
+            res = torch.empty(2, dtype=torch.int64, device=dev)
+            ws = torch.empty(int(lib.fbm_wire_tokenize_workspace(span_len)), dtype=torch.uint8, device=dev)
+            rc = lib.fbm_wire_tokenize_lom(_ptr(blk), span_len, blk_base, first, n_items, _ptr(tab), n_ck, _ptr(res),
+                                           _ptr(ws), _stream())
+            if rc not in (N.FBM_OK, N.FBM_E_UNSUPPORTED):
+                _raise(rc)
+            got, end = (0, 0) if rc else res.cpu().tolist()  # the one small copy; synchronises the stream
+        if rc == N.FBM_OK and got == n_items:
+            resolved.append(end)
+            tables[begin] = tab
+        else:
+            resolved.append(0)
+        if counts is not None:
+            key = "device_scan" if resolved[-1] else "device_scan_refused"
+            counts[key] = counts.get(key, 0) + 1
+        t_dev += time.perf_counter() - t1
+    if timing is not None:
+        timing.update(scan=t_scan)
+        if blk is not None:
+            timing.update(h2d=t_h2d, devscan=t_dev)
+    handles: dict = {}
+    if arrays and tables:
+        with torch.cuda.device(dev):
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+        for i, (b, e, n, scheme, ck) in enumerate(arrays):
+            if ck is None:
+                tab = tables[b]
+                handles[i] = WireHandle(scheme, n, b, e - b, tab.numel(), blk, b - blk_base, 0, ev, tab)
+    return arrays, handles
 
 
 def wire_rows_device(handle: WireHandle, out: Optional[torch.Tensor] = None) -> torch.Tensor:

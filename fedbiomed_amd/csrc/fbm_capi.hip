@@ -1533,6 +1533,82 @@ int fbm_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base
                [&] { return launch_wire_fold_lom(span, span_len, span_base, ckpt, n_ckpt, n_items, acc, first, s); });
 }
 
+uint64_t fbm_wire_tokenize_workspace(uint64_t span_len) { return wire_tokenize_workspace(span_len); }
+
+// the checks fbm_wire_tokenize_lom and its host hook share (n_items > 0)
+static int wire_tokenize_checks(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first, uint64_t n_items,
+                                const uint64_t* ckpt, uint64_t n_ckpt, const uint64_t* result, const void* workspace) {
+  if (!span || !ckpt || !result || !workspace) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  const uint64_t want = (n_items + FBM_WIRE_LOM_GROUP - 1) / FBM_WIRE_LOM_GROUP;
+  if (n_ckpt != want) {
+    set_error("fbm_wire_tokenize_lom: %llu checkpoints for %llu items (one per %d items: %llu)", (unsigned long long)n_ckpt,
+              (unsigned long long)n_items, FBM_WIRE_LOM_GROUP, (unsigned long long)want);
+    return FBM_E_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(ckpt) % 8) || (reinterpret_cast<uintptr_t>(result) % 8) ||
+      (reinterpret_cast<uintptr_t>(workspace) % 8)) {
+    set_error("fbm_wire_tokenize_lom: ckpt / result / workspace not aligned to 8 bytes");
+    return FBM_E_ARG;
+  }
+  if (first < span_base || first - span_base >= span_len) {
+    set_error("fbm_wire_tokenize_lom: first=%llu outside the span [%llu, %llu + %llu)", (unsigned long long)first,
+              (unsigned long long)span_base, (unsigned long long)span_base, (unsigned long long)span_len);
+    return FBM_E_ARG;
+  }
+  if (n_items > 0xffffffffull) {
+    set_error("fbm_wire_tokenize_lom: %llu items exceed a msgpack array", (unsigned long long)n_items);
+    return FBM_E_UNSUPPORTED;
+  }
+  if (span_len > (1ull << 62) || !wire_tokenize_fits(span_len)) {
+    set_error("fbm_wire_tokenize_lom: a span of %llu bytes exceeds one launch's grid", (unsigned long long)span_len);
+    return FBM_E_UNSUPPORTED;
+  }
+  return FBM_OK;
+}
+
+int fbm_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first, uint64_t n_items,
+                          uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n_items == 0) return FBM_OK;
+  int rc = wire_tokenize_checks(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace);
+  if (rc) return rc;
+  return timed("wire_tokenize_lom", s, [&] {
+    return launch_wire_tokenize_lom(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace, s);
+  });
+}
+
+int fbm_wire_scan_deferred(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items,
+                           const uint64_t* resolved, uint64_t n_resolved, fbm_wire_array* arrays, uint64_t arrays_cap,
+                           uint64_t* n_arrays, uint64_t* ckpt, uint64_t ckpt_cap, uint64_t* n_ckpt,
+                           fbm_wire_pending* pending) {
+  if ((len > 0 && !data) || !n_arrays || !n_ckpt || (arrays_cap > 0 && !arrays) || (ckpt_cap > 0 && !ckpt) ||
+      (defer_items > 0 && (!pending || (n_resolved > 0 && !resolved)))) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  fbm_wire_scan_out o = {arrays, arrays_cap, 0, ckpt, ckpt_cap, 0};
+  const fbm_wire_defer df = {defer_items, resolved, n_resolved, pending};
+  const int r = fbm_wire_scan_run(data, len, min_items, &o, &df);
+  *n_arrays = o.n_arrays, *n_ckpt = o.n_ckpt;
+  if (r == FBM_WIRE_SCAN_PENDING) return FBM_WIRE_PENDING;
+  if (r == FBM_WIRE_SCAN_BAD_END) {
+    set_error("fbm_wire_scan_deferred: a resolved end offset outside (first, len]");
+    return FBM_E_ARG;
+  }
+  if (r == FBM_WIRE_SCAN_GAVE_UP) {
+    set_error("fbm_wire_scan: not one well-formed msgpack object within the nesting bound");
+    return FBM_E_UNSUPPORTED;
+  }
+  if (r == FBM_WIRE_SCAN_FULL) {
+    set_error("fbm_wire_scan: arrays_cap / ckpt_cap too small");
+    return FBM_E_RANGE;
+  }
+  return FBM_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------
@@ -1561,6 +1637,14 @@ int fbm_test_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span
   if (n_items == 0) return FBM_OK;
   int rc = wire_fold_lom_checks(span, ckpt, n_ckpt, n_items, acc);
   if (rc == FBM_OK) host_wire_fold_lom(span, span_len, span_base, ckpt, n_ckpt, n_items, acc, first);
+  return rc;
+}
+
+int fbm_test_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
+                               uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  if (n_items == 0) return FBM_OK;
+  int rc = wire_tokenize_checks(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace);
+  if (rc == FBM_OK) host_wire_tokenize_lom(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace);
   return rc;
 }
 

@@ -360,6 +360,14 @@ void host_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64
                       uint64_t n_ckpt, uint64_t n, void* rows);
 void host_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n_ckpt,
                         uint64_t n, uint64_t* acc, int first);
+// fbm_wire_tokenize_lom: the workspace's bytes, whether the span's tiles fit one launch's grid, the three launches,
+// and the same three passes over host buffers
+uint64_t wire_tokenize_workspace(uint64_t span_len);
+bool wire_tokenize_fits(uint64_t span_len);
+int launch_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                             uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s);
+void host_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                            uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
 
 // table slots the encrypt/aggregate kernels need for a given grid
 uint64_t jl_table_slots();

@@ -28,6 +28,8 @@
 //                           <= 9 + 1/8 (the table) + 8 read and 8 written when continuing, 8 fewer read on
 //                           the first call.  Bound: HBM by these bytes; measured, the walk's instruction
 //                           issue, as for wire_decode_lom_kernel.
+//   wire_tok_*_kernel      the FBM_WIRE_LOM table itself, made on the device from the array's bytes
+//                           (fbm_wire_tokenize_lom): see "tokenize" below
 // Every read of the message is checked against its length and every write against the output's capacity,
 // whatever the table holds.
 #include "fbm_internal.hpp"
@@ -269,6 +271,140 @@ __global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_fold_lom_kernel(const uin
   if (mine) acc[i] = a + wire_lom_group_item(buf[wave], avail, lane);
 }
 
+// ---- tokenize: the table of an all-native array made on the device (fbm_wire_tokenize_lom) ---------
+// fbm_wire.hpp has the automaton and the stream's cut into sub-blocks and tiles.  Three launches:
+//   1. wire_tok_maps_kernel   one wave per tile (4 KiB; four tiles per workgroup): the tile's aligned dwords into
+//                             LDS, consecutive lanes consecutive dwords; lane j reads sub-block j's 16 words back
+//                             (rows 17 words apart: 32 different banks) and walks them once, backwards, for its map;
+//                             lanes 0..9 then follow one entry phase each through the 64 maps -> maps[tile]
+//   2. wire_tok_scan_kernel   one workgroup: thread t composes its run of tiles' maps, thread 0 chains the 256 runs
+//                             from the stream's entry phase, every thread then steps through its run again and
+//                             writes each tile's entry state; the count of whole items -> result[0]
+//   3. wire_tok_emit_kernel   pass 1's staging and maps again, the tile's entry state chained through them (every
+//                             lane reads the same LDS word: a broadcast), then lane j walks its sub-block forwards
+//                             from its own entry state: at most one group's first item and at most the last item
+//                             start there -- one 8-byte store each
+// Algorithmic bytes: the stream read twice, 48 bytes per tile written and read back, 8 per 64 items written.
+// Bound: not HBM -- per 4 KiB tile a wave issues 64 backward steps of about 50 instructions in each of passes 1
+// and 3, the forward walk in pass 3, and a chain of 64 dependent LDS reads; the scan kernel is its runs' dependent
+// loads (DESIGN.md 4.2 has the measured times).
+#define FBM_WIRE_TOK_WAVES (FBM_WIRE_BLOCK / 64)  // tiles per workgroup
+#define FBM_WIRE_TOK_ROW 17                       // words between two sub-blocks in LDS
+static_assert(FBM_WIRE_TOK_SUB == 64 && FBM_WIRE_TOK_SUBS == 64 && FBM_WIRE_LOM_GROUP == 64, "one lane per sub-block");
+static_assert(FBM_WIRE_TOK_SCAN_THREADS == FBM_WIRE_SCAN_THREADS, "the host run cuts the tiles into the kernel's runs");
+
+// a tile's words into sh_tile, then this lane's sub-block into w[16], its valid bytes and its map into sh_map;
+// every wave of the workgroup comes through here (two barriers), a wave past the last tile on zeros
+__device__ __forceinline__ int wire_tok_stage(const uint8_t* __restrict__ span, uint64_t span_len, int64_t tbase,
+                                              uint32_t* sh_tile, uint16_t* sh_map, uint32_t* w) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int r = 0; r < FBM_WIRE_TOK_TILE / 4 / 64; ++r) {
+    const int d = r * 64 + lane;
+    const int64_t off = tbase + 4 * d;
+    uint32_t v;
+    if (off >= 0 && (uint64_t)off + 4 <= span_len)
+      v = *reinterpret_cast<const uint32_t*>(span + off);  // (span + tbase is 4-byte aligned)
+    else
+      v = wire_tok_word(span, span_len, off);
+    sh_tile[(d >> 4) * FBM_WIRE_TOK_ROW + (d & 15)] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 16; ++i) w[i] = sh_tile[lane * FBM_WIRE_TOK_ROW + i];
+  const int valid = wire_tok_valid(span_len, tbase + (int64_t)FBM_WIRE_TOK_SUB * lane);
+  uint32_t g[9];
+  wire_tok_block_map(w, valid, g);
+#pragma unroll
+  for (int p = 0; p < 9; ++p) sh_map[lane * FBM_WIRE_TOK_MAP + p] = (uint16_t)g[p];
+  sh_map[lane * FBM_WIRE_TOK_MAP + 9] = (uint16_t)FBM_WIRE_TOK_BAD;
+  __syncthreads();
+  return valid;
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK, 4) wire_tok_maps_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                       int64_t origin, uint64_t tiles,
+                                                                       uint32_t* __restrict__ maps) {
+  __shared__ uint32_t sh_tile[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOK_SUBS * FBM_WIRE_TOK_ROW];
+  __shared__ uint16_t sh_map[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOK_SUBS * FBM_WIRE_TOK_MAP];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t tile = (uint64_t)blockIdx.x * FBM_WIRE_TOK_WAVES + wave;
+  uint32_t w[16];
+  wire_tok_stage(span, span_len, origin + (int64_t)(tile * FBM_WIRE_TOK_TILE), sh_tile[wave], sh_map[wave], w);
+  if (tile >= tiles || lane >= FBM_WIRE_TOK_MAP) return;
+  uint64_t st = (uint64_t)lane;
+#pragma unroll 1
+  for (int t = 0; t < FBM_WIRE_TOK_SUBS; ++t) st = wire_tok_step(st, sh_map[wave] + t * FBM_WIRE_TOK_MAP);
+  maps[tile * FBM_WIRE_TOK_MAP + lane] = (uint32_t)st;  // <= 4096 items << 4
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tok_scan_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
+                                                                              uint32_t head, uint64_t n,
+                                                                              uint64_t* __restrict__ entry,
+                                                                              uint64_t* __restrict__ result) {
+  __shared__ uint64_t comp[FBM_WIRE_SCAN_THREADS][FBM_WIRE_TOK_MAP];
+  __shared__ uint64_t ent[FBM_WIRE_SCAN_THREADS];
+  const int t = threadIdx.x;
+  uint64_t b0, b1;
+  wire_tok_run(tiles, t, &b0, &b1);
+  uint64_t run[9];
+#pragma unroll
+  for (int p = 0; p < 9; ++p) run[p] = (uint64_t)p;
+  for (uint64_t b = b0; b < b1; ++b) {
+#pragma unroll
+    for (int p = 0; p < 9; ++p) run[p] = wire_tok_step(run[p], maps + b * FBM_WIRE_TOK_MAP);
+  }
+#pragma unroll
+  for (int p = 0; p < 9; ++p) comp[t][p] = run[p];
+  comp[t][9] = FBM_WIRE_TOK_BAD;
+  __syncthreads();
+  if (t == 0) {
+    uint64_t st = head;
+    for (int u = 0; u < FBM_WIRE_SCAN_THREADS; ++u) {
+      ent[u] = st;
+      st = wire_tok_step(st, comp[u]);
+    }
+    result[0] = wire_tok_whole_items(st, n);
+    result[1] = 0;  // wire_tok_emit_kernel writes the end where item n - 1 lies wholly inside the span
+  }
+  __syncthreads();
+  uint64_t st = ent[t];
+  for (uint64_t b = b0; b < b1; ++b) {
+    entry[b] = st;
+    st = wire_tok_step(st, maps + b * FBM_WIRE_TOK_MAP);
+  }
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK, 4) wire_tok_emit_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                       int64_t origin, uint64_t tiles,
+                                                                       const uint64_t* __restrict__ entry, uint64_t base,
+                                                                       uint64_t n, uint64_t* __restrict__ ckpt,
+                                                                       uint64_t n_ckpt, uint64_t* __restrict__ result) {
+  __shared__ uint32_t sh_tile[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOK_SUBS * FBM_WIRE_TOK_ROW];
+  __shared__ uint16_t sh_map[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOK_SUBS * FBM_WIRE_TOK_MAP];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t tile = (uint64_t)blockIdx.x * FBM_WIRE_TOK_WAVES + wave;
+  const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+  uint32_t w[16];
+  const int valid = wire_tok_stage(span, span_len, tbase, sh_tile[wave], sh_map[wave], w);
+  if (tile >= tiles) return;
+  uint64_t st = entry[tile], mine = 0;
+#pragma unroll 1  // (unrolled, the 64 comparisons with the lane are all made first and outgrow the registers)
+  for (int t = 0; t < FBM_WIRE_TOK_SUBS; ++t) {
+    if (t == lane) mine = st;
+    st = wire_tok_step(st, sh_map[wave] + t * FBM_WIRE_TOK_MAP);
+  }
+  if ((mine & 15) == FBM_WIRE_TOK_BAD) return;
+  int ck, end;
+  wire_tok_block_walk(sh_tile[wave] + lane * FBM_WIRE_TOK_ROW, valid, (uint32_t)(mine & 15), mine >> 4, n, &ck, &end);
+  const int64_t sub = tbase + (int64_t)FBM_WIRE_TOK_SUB * lane;  // (an item starts at or behind `first`: sub + ck >= 0)
+  if (ck >= 0) {
+    const uint64_t group = ((mine >> 4) + FBM_WIRE_LOM_GROUP - 1) / FBM_WIRE_LOM_GROUP;
+    if (group < n_ckpt) ckpt[group] = base + (uint64_t)(sub + ck);
+  }
+  if (end >= 0 && (uint64_t)(sub + end) <= span_len) result[1] = base + (uint64_t)(sub + end);
+}
+
 static int wire_grid(uint64_t blocks, const char* what, unsigned& g) {
   if (blocks > 0x7fffffffull) {
     set_error("%s: %llu workgroups exceed one launch's grid", what, (unsigned long long)blocks);
@@ -345,6 +481,32 @@ int launch_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, 
   return check_launch("wire_fold_lom_kernel");
 }
 
+uint64_t wire_tokenize_workspace(uint64_t span_len) {
+  const uint64_t tiles = (span_len + 3 + FBM_WIRE_TOK_TILE - 1) / FBM_WIRE_TOK_TILE;  // whatever the alignment
+  return wire_tok_maps_at(tiles) + (tiles * FBM_WIRE_TOK_MAP * 4 + 255) / 256 * 256 + 256;
+}
+// more workgroups than one launch's grid: the caller's check before any device call
+bool wire_tokenize_fits(uint64_t span_len) {
+  return ((span_len + 3 + FBM_WIRE_TOK_TILE - 1) / FBM_WIRE_TOK_TILE + FBM_WIRE_TOK_WAVES - 1) / FBM_WIRE_TOK_WAVES <= 0x7fffffffull;
+}
+
+int launch_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                             uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s) {
+  const wire_tok_cut c = wire_tok_cut_of(span, span_len, first - base);
+  unsigned g = 0;
+  int rc = wire_grid((c.tiles + FBM_WIRE_TOK_WAVES - 1) / FBM_WIRE_TOK_WAVES, "fbm_wire_tokenize_lom", g);
+  if (rc) return rc;
+  uint64_t* entry = reinterpret_cast<uint64_t*>(workspace);
+  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(c.tiles));
+  hipLaunchKernelGGL(wire_tok_maps_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, c.origin, c.tiles, maps);
+  if ((rc = check_launch("wire_tok_maps_kernel"))) return rc;
+  hipLaunchKernelGGL(wire_tok_scan_kernel, dim3(1), dim3(FBM_WIRE_SCAN_THREADS), 0, s, maps, c.tiles, c.head, n, entry, result);
+  if ((rc = check_launch("wire_tok_scan_kernel"))) return rc;
+  hipLaunchKernelGGL(wire_tok_emit_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, c.origin, c.tiles, entry, base,
+                     n, ckpt, n_ckpt, result);
+  return check_launch("wire_tok_emit_kernel");
+}
+
 // ---- the same per-item routines on the host (the test build's hooks) ------------------------------
 int host_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total) {
   uint64_t p = 0;
@@ -397,6 +559,12 @@ void host_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64
 void host_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n_ckpt,
                         uint64_t n, uint64_t* acc, int first) {
   wire_fold_lom_groups(span, span_len, base, ckpt, n_ckpt, n, acc, first, FBM_WIRE_LOM_GROUP);
+}
+
+
+void host_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                            uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  wire_tokenize_host(span, span_len, base, first, n, ckpt, n_ckpt, result, workspace);
 }
 
 }  // namespace fbm

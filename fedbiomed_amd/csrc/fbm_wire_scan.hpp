@@ -15,6 +15,10 @@
 //   FBM_WIRE_LOM  one per FBM_WIRE_LOM_GROUP items: the offset of the group's first item
 // While an array's items are all native only group checkpoints are written; the first map item restarts the
 // array's table per item (one re-walk of the items before it, at most once per array).
+//
+// fbm_wire_scan_deferred is the same pass (fbm_wire_scan_run) with one more branch: a large array whose first byte is
+// a native form is not walked here when the caller brings its end offset from the device tokenizer
+// (fbm_wire_tokenize_lom); see fbm_wire_defer below.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -25,6 +29,9 @@
 #define FBM_WIRE_PREFIX_LEN 20
 #define FBM_WIRE_SCAN_GAVE_UP 1  // malformed, truncated, trailing bytes or too deep: nothing is recorded
 #define FBM_WIRE_SCAN_FULL 2     // a table of the caller's is too small
+#define FBM_WIRE_SCAN_PENDING 3  // a deferral candidate without an answer yet: `pending` is filled, nothing is recorded
+#define FBM_WIRE_SCAN_BAD_END 4  // a resolved end offset that is not behind the array's first item and within the message
+#define FBM_WIRE_MAX_DEFERRED 8  // deferral candidates per message; later ones are walked here
 
 static const uint8_t FBM_WIRE_PREFIX[FBM_WIRE_PREFIX_LEN] = {0x82, 0xa8, '_', '_', 't', 'y', 'p', 'e', '_', '_',
                                                              0xa3, 'i',  'n', 't', 0xa5, 'v', 'a', 'l', 'u', 'e'};
@@ -122,8 +129,24 @@ static inline uint64_t fbm_wire_be(const uint8_t* p, int bytes) {
   return v;
 }
 
-// FBM_OK, FBM_WIRE_SCAN_GAVE_UP or FBM_WIRE_SCAN_FULL; on anything but FBM_OK the counts are zero
-static inline int fbm_wire_scan_impl(const uint8_t* d, uint64_t len, uint64_t min_items, fbm_wire_scan_out* o) {
+// What fbm_wire_scan_deferred adds to the pass: an array of at least max(min_items, defer_items) items whose first
+// byte is a native form is a deferral candidate (an array with more items than bytes left is none: no table is
+// ever sized by it).  The k-th candidate, k < FBM_WIRE_MAX_DEFERRED: resolved[k] != 0 is its end offset from
+// elsewhere (the device tokenizer) -- it is recorded as FBM_WIRE_LOM with no checkpoints and pad = 1, and the
+// pass goes on behind it; resolved[k] == 0: walked here like every other; k >= n_resolved: the pass stops with
+// FBM_WIRE_SCAN_PENDING and *pending says which array the caller is to resolve before it runs the pass again.
+struct fbm_wire_defer {
+  uint64_t defer_items;  // 0: no array is a candidate
+  const uint64_t* resolved;
+  uint64_t n_resolved;
+  fbm_wire_pending* pending;
+};
+
+// FBM_OK, FBM_WIRE_SCAN_GAVE_UP or FBM_WIRE_SCAN_FULL, with df also FBM_WIRE_SCAN_PENDING or FBM_WIRE_SCAN_BAD_END; on
+// anything but FBM_OK the counts are zero.  df == nullptr: fbm_wire_scan's pass.
+static inline int fbm_wire_scan_run(const uint8_t* d, uint64_t len, uint64_t min_items, fbm_wire_scan_out* o,
+                                    const fbm_wire_defer* df) {
+  uint64_t candidates = 0;  // deferral candidates met so far
   uint64_t stack[FBM_WIRE_MAX_DEPTH];  // objects still to read in each open container
   int depth = 1;
   uint64_t pos = 0;
@@ -190,6 +213,33 @@ static inline int fbm_wire_scan_impl(const uint8_t* d, uint64_t len, uint64_t mi
         pos += skip;
         continue;
       }
+      if (is_array && children >= min_items && df && df->defer_items && children >= df->defer_items &&
+          candidates < FBM_WIRE_MAX_DEFERRED && children <= left - skip &&
+          (d[pos + skip] <= 0x7f || (d[pos + skip] >= 0xcc && d[pos + skip] <= 0xcf))) {
+        const uint64_t k = candidates++;
+        if (k >= df->n_resolved) {
+          df->pending->begin = pos, df->pending->first = pos + skip, df->pending->n_items = children;
+          o->n_arrays = o->n_ckpt = 0;
+          return FBM_WIRE_SCAN_PENDING;
+        }
+        const uint64_t end = df->resolved[k];
+        if (end) {
+          if (end <= pos + skip || end > len) {
+            o->n_arrays = o->n_ckpt = 0;
+            return FBM_WIRE_SCAN_BAD_END;
+          }
+          if (o->n_arrays >= o->arrays_cap) {
+            o->n_arrays = o->n_ckpt = 0;
+            return FBM_WIRE_SCAN_FULL;
+          }
+          fbm_wire_array* a = &o->arrays[o->n_arrays++];
+          a->begin = pos, a->end = end, a->n_items = children;
+          a->ckpt_first = o->n_ckpt, a->ckpt_count = 0;
+          a->scheme = FBM_WIRE_LOM, a->pad = 1;  // the table is on the device
+          pos = end;
+          continue;
+        }
+      }
       if (is_array && children >= min_items) {
         uint64_t end = 0;
         const int r = fbm_wire_candidate(d, len, pos, pos + skip, children, o, &end);
@@ -214,4 +264,8 @@ static inline int fbm_wire_scan_impl(const uint8_t* d, uint64_t len, uint64_t mi
 gave_up:
   o->n_arrays = o->n_ckpt = 0;
   return FBM_WIRE_SCAN_GAVE_UP;
+}
+
+static inline int fbm_wire_scan_impl(const uint8_t* d, uint64_t len, uint64_t min_items, fbm_wire_scan_out* o) {
+  return fbm_wire_scan_run(d, len, min_items, o, nullptr);
 }

@@ -35,7 +35,7 @@ extern "C" {
                              the test build only) -- and, additions only, so still 7: the input dtypes FBM_F16 / FBM_BF16
                              and the *_as entry points (fbm_lom_aggregate_as, fbm_jl_aggregate_as,
                              fbm_jl_aggregate_factor_as, fbm_dequantize_as), the streaming folds, and the reference Serializer's bytes on the
-                             device (fbm_wire_*); 6: fbm_lom_*_host; 5: fbm_jl_encrypt_factor; 4: fbm_ves_pack takes is_signed; 3: the JL round is an 8192-bit value (FBM_TAU_LIMBS limbs);
+                             device (fbm_wire_*, the device tokenizer fbm_wire_tokenize_* and fbm_wire_scan_deferred among them); 6: fbm_lom_*_host; 5: fbm_jl_encrypt_factor; 4: fbm_ves_pack takes is_signed; 3: the JL round is an 8192-bit value (FBM_TAU_LIMBS limbs);
                              2 took 16 limbs, 1 a uint64 */
 /* The JL round `tau` of every JL entry point: a HOST pointer to FBM_TAU_LIMBS little-endian 32-bit
  * words, any round below 2^8192 -- FDH.H hashes t = (k << 512) | tau as t.to_bytes(1024, 'big')
@@ -429,7 +429,8 @@ int fbm_ass_reconstruct_wide(const uint32_t* shares, int n_shares, int l, uint64
 /* One array the scanner recorded: bytes [begin, end) of the message (header included), its items, its
  * scheme, and its checkpoints ckpt[ckpt_first .. ckpt_first + ckpt_count) -- all absolute byte offsets into
  * the message.  FBM_WIRE_JL: one per item, (offset of the value's first big-endian byte) << 16 | byte count
- * (1..257).  FBM_WIRE_LOM: one per FBM_WIRE_LOM_GROUP items, the offset of the group's first item. */
+ * (1..257).  FBM_WIRE_LOM: one per FBM_WIRE_LOM_GROUP items, the offset of the group's first item.  pad is 0,
+ * or 1 where fbm_wire_scan_deferred left the array's table to the device (ckpt_count is then 0). */
 typedef struct fbm_wire_array {
   uint64_t begin, end, n_items, ckpt_first, ckpt_count;
   int32_t scheme, pad;
@@ -481,6 +482,51 @@ int fbm_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t
  * before any kernel. */
 int fbm_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
                       uint64_t n_ckpt, uint64_t n_items, uint64_t* acc, int first, void* stream);
+
+/* The table of an all-native array made on the device, so that the host never steps through its items (these
+ * three arrived under ABI 7 as well).  The start of an item depends on every length before it: a 9-state
+ * automaton over bytes (payload bytes still to skip, plus one absorbing state for a byte that starts no native
+ * form) whose transition maps compose, so the walk runs as a scan -- a map per 64-byte block and per 4 KiB tile,
+ * a scan of the tiles' maps, and a last pass that walks each block from its now known entry state.
+ *
+ * fbm_wire_tokenize_lom: span (device) holds the message's bytes [span_base, span_base + span_len); first is the
+ * absolute offset of item 0; ckpt (device, n_ckpt = ceil(n_items / FBM_WIRE_LOM_GROUP) words), result (device, 2
+ * words) and workspace (device, fbm_wire_tokenize_workspace(span_len) bytes) are 8-byte aligned.  On the stream:
+ *   result[0]  the leading items that are native forms lying wholly inside the span, at most n_items.  Counting
+ *              stops at the first byte that starts no native form and at an item the span's end cuts off; only
+ *              the chain from `first` decides what starts an item (a payload byte cc, cf or 82 starts none)
+ *   result[1]  where result[0] == n_items: the absolute offset one past item n_items - 1 -- that item's end,
+ *              whatever follows it; else 0
+ *   ckpt[g]    where result[0] == n_items: the absolute offset of item 64 g, word for word the table
+ *              fbm_wire_scan writes for the same array; else unspecified
+ * No byte outside the span is read and nothing outside ckpt, result and workspace is written, whatever the
+ * bytes are.  n_items == 0 is FBM_OK (nothing runs).  Then, before any device call: a null pointer, n_ckpt !=
+ * ceil(n_items / FBM_WIRE_LOM_GROUP), a ckpt, result or workspace off an 8-byte boundary and a first outside
+ * the span are FBM_E_ARG; n_items >= 2^32 and more workgroups than one launch's grid FBM_E_UNSUPPORTED. */
+uint64_t fbm_wire_tokenize_workspace(uint64_t span_len);
+int fbm_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
+                          uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace,
+                          void* stream);
+
+/* fbm_wire_scan with the large all-native arrays left to fbm_wire_tokenize_lom: the same pass (no device call),
+ * except that an array of at least max(min_items, defer_items) items whose first byte is a native form is a
+ * deferral candidate.  For the k-th candidate of the message (k < 8; later ones are walked on the host):
+ *   k < n_resolved, resolved[k] != 0   its end offset, as result[1] gave it (first < end <= len, else FBM_E_ARG):
+ *                                      recorded as FBM_WIRE_LOM with ckpt_count = 0 and pad = 1 -- its table is
+ *                                      on the device -- and the pass goes on at that offset
+ *   k < n_resolved, resolved[k] == 0   walked on the host exactly as fbm_wire_scan does (the tokenizer refused it)
+ *   k >= n_resolved                    FBM_WIRE_PENDING: *pending is the array to resolve, nothing is recorded
+ * Stateless: the caller resolves the pending array and calls again with one more entry; a resolved array is
+ * skipped, so each further pass costs the message's remainder.  defer_items == 0 is fbm_wire_scan exactly (resolved
+ * and pending may then be null).  Every other return value as fbm_wire_scan's. */
+#define FBM_WIRE_PENDING 1
+typedef struct fbm_wire_pending {
+  uint64_t begin, first, n_items; /* the array's header, its first item, its items */
+} fbm_wire_pending;
+int fbm_wire_scan_deferred(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items,
+                           const uint64_t* resolved, uint64_t n_resolved, fbm_wire_array* arrays, uint64_t arrays_cap,
+                           uint64_t* n_arrays, uint64_t* ckpt, uint64_t ckpt_cap, uint64_t* n_ckpt,
+                           fbm_wire_pending* pending);
 
 /* Drops the library's host-side caches: the short path's constant C per (N, |key|) -- kept under a
  * SHA-256 digest of (N, |key|), never the key itself, and zeroed here and on eviction -- and the

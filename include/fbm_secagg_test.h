@@ -137,6 +137,10 @@ int fbm_test_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uin
  * argument errors. */
 int fbm_test_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
                            uint64_t n_ckpt, uint64_t n_items, uint64_t* acc, int first);
+/* fbm_wire_tokenize_lom over HOST buffers: the kernels' three passes tile by tile through the same per-block
+ * routines (host_wire_tokenize_lom), same arguments and argument errors. */
+int fbm_test_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
+                               uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
 
 /* The LOM aggregate kernel fbm_lom_aggregate launches for n_parties rows of n elements at y (device
  * pointer; its alignment picks the form), as rocprofv3 names it without the "fbm::" namespace, e.g.

@@ -25,12 +25,20 @@ reference run.  Both sides' outputs are compared before anything is timed.
   jl_take      likewise at ceil(10M / 30) ciphertexts
 
 each into a running accumulator (`begin_aggregate()` with one reply already folded in), every run ending in a device
-synchronise; the accumulators of both sides are compared first.  The new side's phases: `scan`, `h2d` (staging +
-upload, synchronised for the timing), `fold` (add + synchronise: the kernels).
+synchronise; the accumulators of both sides are compared first.  The new side's phases: `scan` (the host scanner's
+passes), `h2d` (staging + upload, synchronised for the timing), `devscan` (the device tokenizer and the copy of its
+two result words, where an array took that route), `fold` (add + synchronise: the kernels).
+--device-scan-min-items N sets `loads_reference`'s keyword (default: the module's `wire.DEVICE_SCAN_MIN_ITEMS`).
+
+--devscan: the LOM take leg with the device scan forced on against the device scan disabled (the host scanner's
+walk), alternating, --runs of each, at every item count 2^10 .. 2^24 (profiles/wire_devscan_ab.jsonl).  The last line
+names the smallest power of two from which on the device route's median take is the faster one: the value for
+`wire.DEVICE_SCAN_MIN_ITEMS` on that box.
 
 --kernels: for a kernel trace (`rocprofv3 --kernel-trace --stats -- python tools/wire_ref_ab.py --kernels`): one LOM
 update's bytes uploaded once, then four launches of wire_fold_lom_kernel (continuing) and four of
-wire_decode_lom_kernel + lom_fold_kernel on the same bytes.
+wire_decode_lom_kernel + lom_fold_kernel on the same bytes, then four reads of the message with the device scan
+forced on (wire_tok_maps_kernel, wire_tok_scan_kernel, wire_tok_emit_kernel; the printed line has the stream's bytes).
 """
 import argparse
 import gc
@@ -99,7 +107,86 @@ def kernels(a):
         D.lom_fold(ref, D.wire_rows_device(h, out=rows), False)
         torch.cuda.synchronize()
     assert torch.equal(acc, ref)
-    print(json.dumps({"kernels": "4 x wire_fold_lom_kernel, 4 x (wire_decode_lom_kernel + lom_fold_kernel)", "items": h.n}))
+    for _ in range(4):
+        upd = wire.loads_reference(data, resident=True, device_scan_min_items=1)["params"]
+        torch.cuda.synchronize()
+    assert wire.reference_stats()["device_scan"] == 4 and torch.equal(D.wire_rows_device(upd.handle), rows)
+    print(json.dumps({"kernels": "4 x wire_fold_lom_kernel, 4 x (wire_decode_lom_kernel + lom_fold_kernel), "
+                                 "4 x (wire_tok_maps_kernel + wire_tok_scan_kernel + wire_tok_emit_kernel)", "items": h.n,
+                      "tokenized_stream_bytes": len(data) - upd.handle.base}))
+    return 0
+
+
+def devscan(a):
+    """The sweep that fixes wire.DEVICE_SCAN_MIN_ITEMS (see the module's docstring)."""
+    import torch
+
+    from fedbiomed_amd import _device as D
+    from fedbiomed_amd import workload as W
+    from fedbiomed_amd.secagg import SecaggLomCrypter
+
+    dev = D.device()
+    wire._PHASE_TIMING = False  # nothing but the take is timed: no synchronise inside it
+    rng = np.random.default_rng(2026)
+    routes = (("device", 1), ("host", 2**62))
+    lines, medians = [], {}
+    for k in range(10, 25):
+        n = 1 << k
+        words = _lom_words(rng, n)
+        first = torch.from_numpy(words.view(np.int64)).to(dev)
+        data = msgpack.packb({"node_id": "node-00", "params": words.tolist(), "n": n})
+        del words
+        aggs = {}
+        for impl, _ in routes:
+            aggs[impl] = SecaggLomCrypter(W.LOM_NONCE).begin_aggregate(1000)
+            aggs[impl].add(first)
+        torch.cuda.synchronize()
+
+        def take(impl, dmin):
+            upd = wire.loads_reference(data, object_hook=ref_hook, resident=True, device_scan_min_items=dmin)["params"]
+            aggs[impl].add(upd)
+            torch.cuda.synchronize()
+            return upd
+
+        wire.reference_stats(reset=True)
+        for impl, dmin in routes:  # warm-up, and both routes' accumulators compared
+            del_me = take(impl, dmin)
+            assert type(del_me) is wire.ResidentUpdate and not del_me.materialised
+            del del_me
+        st = wire.reference_stats()
+        assert (st["device_scan"], st["device_scan_refused"], st["resident"]) == (1, 0, 2), st
+        assert torch.equal(aggs["device"]._acc, aggs["host"]._acc), f"2^{k}: the accumulators differ"
+        times = {impl: [] for impl, _ in routes}
+        for run in range(a.runs):
+            for impl, dmin in routes:
+                dt, out = timed(lambda: take(impl, dmin))
+                del out
+                rec = {"leg": "lom_take_sweep", "impl": impl, "items": n, "run": run, "ms": round(dt * 1e3, 3),
+                       "message_bytes": len(data),
+                       "phases_ms": {p: round(v * 1e3, 3) for p, v in wire.reference_stats()["last"].items()}}
+                times[impl].append(dt * 1e3)
+                lines.append(rec)
+                print(json.dumps(rec), flush=True)
+        assert torch.equal(aggs["device"]._acc, aggs["host"]._acc), f"2^{k}: the accumulators differ after the runs"
+        medians[n] = {impl: round(float(np.median(t)), 3) for impl, t in times.items()}
+        medians[n].update(device_max=round(max(times["device"]), 3), host_min=round(min(times["host"]), 3))
+        for g in aggs.values():
+            g.abort()
+        del aggs, first, data
+    sizes = sorted(medians)
+    chosen = None
+    for n in reversed(sizes):  # the smallest power of two from which on the device route is the faster one
+        if medians[n]["device"] < medians[n]["host"]:
+            chosen = n
+        else:
+            break
+    summary = {"summary": {str(n): medians[n] for n in sizes}, "device_scan_min_items": chosen, "runs": a.runs,
+               "rule": "smallest 2^k such that the device route's median take is below the host route's at 2^k and above"}
+    lines.append(summary)
+    print(json.dumps(summary), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.writelines(json.dumps(ln) + "\n" for ln in lines)
     return 0
 
 
@@ -113,6 +200,7 @@ def resident(a):
 
     dev = D.device()
     wire._PHASE_TIMING = True
+    scan_kw = {} if a.device_scan_min_items is None else {"device_scan_min_items": a.device_scan_min_items}
     rng = np.random.default_rng(2026)
     n_ct = -(-a.elements // 30)
     sk0 = -sum(W.jl_user_key(p) for p in range(3))
@@ -136,7 +224,8 @@ def resident(a):
 
         def new():
             t0 = time.perf_counter()
-            upd = wire.loads_reference(data, object_hook=ref_hook, resident=True)["params"]
+            upd = wire.loads_reference(data, object_hook=ref_hook, resident=True, **scan_kw)["params"]
+            phases.clear()
             phases.update(wire.reference_stats()["last"])
             t1 = time.perf_counter()
             aggs["new"].add(upd)
@@ -180,7 +269,8 @@ def resident(a):
     st = wire.reference_stats()
     summary = {"summary": legs, "condition": "per leg: slowest new run < fastest reference run",
                "holds": all(v["holds"] for v in legs.values()), "elements": a.elements, "runs": a.runs,
-               "resident": st["resident"], "fallback": st["fallback"], "msgpack": ".".join(map(str, msgpack.version))}
+               "resident": st["resident"], "fallback": st["fallback"], "device_scan": st.get("device_scan", 0),
+               "device_scan_refused": st.get("device_scan_refused", 0), "msgpack": ".".join(map(str, msgpack.version))}
     lines.append(summary)
     print(json.dumps(summary), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -195,11 +285,16 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--resident", action="store_true")
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--devscan", action="store_true")
+    ap.add_argument("--device-scan-min-items", type=int, default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "wire_resident_ab.jsonl" if a.resident else "wire_reference_ab.jsonl")
+    a.out = a.out or os.path.join(ROOT, "profiles", "wire_devscan_ab.jsonl" if a.devscan else
+                                  "wire_resident_ab.jsonl" if a.resident else "wire_reference_ab.jsonl")
     if a.kernels:
         return kernels(a)
+    if a.devscan:
+        return devscan(a)
     if a.resident:
         return resident(a)
 
