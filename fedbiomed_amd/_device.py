@@ -1957,28 +1957,31 @@ def wire_upload(data, arrays: list, timing: Optional[dict] = None) -> List[WireH
             for (b, e, n, scheme, ck), so, co in zip(arrays, s_off, c_off)]
 
 
-def wire_scan_deferred(data, min_items: int, defer_items: int, resolved) -> Tuple[str, Any]:
-    """One pass of fbm_wire_scan_deferred over a message, no device call: ("pending", (begin, first, n_items)) for
-    the deferral candidate that `resolved` (end offsets, 0: walk it on the host) does not answer yet, else ("done",
-    arrays) with wire_scan's list -- the checkpoints of an array left to the device are None -- or ("done", None)
-    where the scan gives up."""
+def wire_scan_deferred(data, min_items: int, defer_items: int, resolved, defer_jl_items: int = 0) -> Tuple[str, Any]:
+    """One pass of fbm_wire_scan_deferred2 over a message, no device call: ("pending", (begin, first, n_items)) for
+    the deferral candidate that `resolved` (end offsets, 0: walk it on the host) does not answer yet -- with
+    `defer_jl_items` the arrays of big-int maps are candidates too and the tuple has the candidate's scheme as a
+    fourth entry --, else ("done", arrays) with wire_scan's list -- the checkpoints of an array left to the device
+    are None -- or ("done", None) where the scan gives up."""
     lib = N.load()
     buf = np.frombuffer(data, dtype=np.uint8)
     n = buf.size
     n_arr, n_ck = ctypes.c_uint64(0), ctypes.c_uint64(0)
     res = np.array(list(resolved), dtype=np.uint64)
-    pend = N.WirePending()
+    pend = N.WirePending2()
+    defer_jl_items = max(int(defer_jl_items), 0)
     for a_cap, c_cap in ((1024, n // 8 + 1024), (n // max(int(min_items), 1) + 1, n + 16)):
         arrays = (N.WireArray * a_cap)()
         ckpt = np.empty(c_cap, dtype=np.uint64)
-        rc = lib.fbm_wire_scan_deferred(_np_ptr(buf) if n else None, n, max(int(min_items), 1), max(int(defer_items), 0),
-                                        _np_ptr(res) if res.size else None, res.size, ctypes.addressof(arrays), a_cap,
-                                        ctypes.addressof(n_arr), _np_ptr(ckpt), c_cap, ctypes.addressof(n_ck),
-                                        ctypes.addressof(pend))
+        rc = lib.fbm_wire_scan_deferred2(_np_ptr(buf) if n else None, n, max(int(min_items), 1), max(int(defer_items), 0),
+                                         defer_jl_items, _np_ptr(res) if res.size else None, res.size,
+                                         ctypes.addressof(arrays), a_cap, ctypes.addressof(n_arr), _np_ptr(ckpt), c_cap,
+                                         ctypes.addressof(n_ck), ctypes.addressof(pend))
         if rc == N.FBM_E_RANGE:
             continue
         if rc == N.WIRE_PENDING:
-            return "pending", (int(pend.begin), int(pend.first), int(pend.n_items))
+            found = (int(pend.begin), int(pend.first), int(pend.n_items))
+            return "pending", found + (_WIRE_NAME[pend.scheme],) if defer_jl_items else found
         if rc == N.FBM_E_UNSUPPORTED:
             return "done", None
         if rc != N.FBM_OK:
@@ -1989,16 +1992,19 @@ def wire_scan_deferred(data, min_items: int, defer_items: int, resolved) -> Tupl
 
 
 def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[dict] = None,
-                       counts: Optional[dict] = None, sync_phases: bool = False) -> Tuple[Optional[list], dict]:
-    """wire_scan with the arrays of at least `defer_items` native items tokenized on the device
-    (fbm_wire_scan_deferred + fbm_wire_tokenize_lom).  At the first such array the message from that array's
+                       counts: Optional[dict] = None, sync_phases: bool = False,
+                       defer_jl_items: int = 0) -> Tuple[Optional[list], dict]:
+    """wire_scan with the arrays of at least `defer_items` native items, and with `defer_jl_items` (0: none) those
+    of at least that many big-int maps, tokenized on the device (fbm_wire_scan_deferred2 + fbm_wire_tokenize_lom /
+    fbm_wire_tokenize_jl; a "jl" array's table has a word per item).  At the first such array the message from that array's
     header to its end goes up once, through a pinned buffer on the current stream; the tokenizer runs behind the
     upload, its two result words come back in one small synchronous copy and the scanner runs again with the
     answer.  An array the tokenizer refuses (not all native, cut off, outside its domain) is walked on the host.
     Returns (arrays, handles): wire_scan's list -- checkpoints None where the table is on the device -- and a
     WireHandle per such array under its index; (None, {}) where the scan gives up.  No device call while no array
     qualifies.  timing: receives scan / h2d / devscan seconds (sync_phases: the upload is synchronised, so that h2d
-    is its time and not its enqueue); counts: device_scan / device_scan_refused are incremented."""
+    is its time and not its enqueue); counts: device_scan / device_scan_refused are incremented for a "lom" array,
+    device_scan_jl / device_scan_jl_refused for a "jl" one."""
     import time
 
     lib = N.load()
@@ -2009,12 +2015,13 @@ def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[
     t_scan = t_h2d = t_dev = 0.0
     while True:
         t0 = time.perf_counter()
-        kind, val = wire_scan_deferred(data, min_items, defer_items, resolved)
+        kind, val = wire_scan_deferred(data, min_items, defer_items, resolved, defer_jl_items)
         t_scan += time.perf_counter() - t0
         if kind != "pending":
             arrays = val
             break
-        begin, first, n_items = val
+        begin, first, n_items = val[:3]
+        jl = len(val) > 3 and val[3] == "jl"
         t0 = time.perf_counter()
         if blk is None:
             dev, blk_base = device(), begin
@@ -2026,14 +2033,15 @@ def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[
                     torch.cuda.synchronize()
         t1 = time.perf_counter()
         t_h2d += t1 - t0
-        n_ck = (n_items + N.WIRE_LOM_GROUP - 1) // N.WIRE_LOM_GROUP
+        n_ck = n_items if jl else (n_items + N.WIRE_LOM_GROUP - 1) // N.WIRE_LOM_GROUP
         span_len = size - blk_base
+        ws_bytes, tokenize = (lib.fbm_wire_tokenize_jl_workspace, lib.fbm_wire_tokenize_jl) if jl else \
+            (lib.fbm_wire_tokenize_workspace, lib.fbm_wire_tokenize_lom)
         with torch.cuda.device(dev):
             tab = torch.empty(n_ck, dtype=torch.int64, device=dev)
             res = torch.empty(2, dtype=torch.int64, device=dev)
-            ws = torch.empty(int(lib.fbm_wire_tokenize_workspace(span_len)), dtype=torch.uint8, device=dev)
-            rc = lib.fbm_wire_tokenize_lom(_ptr(blk), span_len, blk_base, first, n_items, _ptr(tab), n_ck, _ptr(res),
-                                           _ptr(ws), _stream())
+            ws = torch.empty(int(ws_bytes(span_len)), dtype=torch.uint8, device=dev)
+            rc = tokenize(_ptr(blk), span_len, blk_base, first, n_items, _ptr(tab), n_ck, _ptr(res), _ptr(ws), _stream())
             if rc not in (N.FBM_OK, N.FBM_E_UNSUPPORTED):
                 _raise(rc)
             got, end = (0, 0) if rc else res.cpu().tolist()  # the one small copy; synchronises the stream
@@ -2043,7 +2051,7 @@ def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[
         else:
             resolved.append(0)
         if counts is not None:
-            key = "device_scan" if resolved[-1] else "device_scan_refused"
+            key = ("device_scan_jl" if jl else "device_scan") + ("" if resolved[-1] else "_refused")
             counts[key] = counts.get(key, 0) + 1
         t_dev += time.perf_counter() - t1
     if timing is not None:

@@ -149,6 +149,10 @@ SIGNATURES = {
     "fbm_wire_tokenize_workspace": (c_u64, [c_u64]),
     "fbm_wire_tokenize_lom": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]),
     "fbm_wire_scan_deferred": (c_int, [c_vp, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp]),
+    "fbm_wire_tokenize_jl_workspace": (c_u64, [c_u64]),
+    "fbm_wire_tokenize_jl": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]),
+    "fbm_wire_scan_deferred2": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp,
+                                        c_vp]),
 }
 WIRE_JL = 0  # FBM_WIRE_JL
 WIRE_LOM = 1  # FBM_WIRE_LOM
@@ -161,6 +165,11 @@ WIRE_PENDING = 1  # FBM_WIRE_PENDING
 class WirePending(ctypes.Structure):
     """fbm_wire_pending: the array fbm_wire_scan_deferred wants resolved."""
     _fields_ = [("begin", c_u64), ("first", c_u64), ("n_items", c_u64)]
+
+
+class WirePending2(ctypes.Structure):
+    """fbm_wire_pending2: the array fbm_wire_scan_deferred2 wants resolved, with its scheme."""
+    _fields_ = [("begin", c_u64), ("first", c_u64), ("n_items", c_u64), ("scheme", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
 class WireArray(ctypes.Structure):
@@ -197,6 +206,7 @@ TEST_SIGNATURES = {
     "fbm_test_wire_decode": (c_int, [c_int, c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp]),
     "fbm_test_wire_fold_lom": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp, c_int]),
     "fbm_test_wire_tokenize_lom": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
+    "fbm_test_wire_tokenize_jl": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
     "fbm_prof_enable": (c_int, [c_int]),
     "fbm_prof_report": (c_int, [ctypes.c_char_p, c_int]),
 }

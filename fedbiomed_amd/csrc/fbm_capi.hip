@@ -1535,17 +1535,19 @@ int fbm_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base
 
 uint64_t fbm_wire_tokenize_workspace(uint64_t span_len) { return wire_tokenize_workspace(span_len); }
 
-// the checks fbm_wire_tokenize_lom and its host hook share (n_items > 0)
+// the checks fbm_wire_tokenize_lom / fbm_wire_tokenize_jl and their host hooks share (n_items > 0); `group`: items per
+// table word.  (The messages name the LOM entry point for both.)
 static int wire_tokenize_checks(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first, uint64_t n_items,
-                                const uint64_t* ckpt, uint64_t n_ckpt, const uint64_t* result, const void* workspace) {
+                                const uint64_t* ckpt, uint64_t n_ckpt, const uint64_t* result, const void* workspace,
+                                int group = FBM_WIRE_LOM_GROUP) {
   if (!span || !ckpt || !result || !workspace) {
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
-  const uint64_t want = (n_items + FBM_WIRE_LOM_GROUP - 1) / FBM_WIRE_LOM_GROUP;
+  const uint64_t want = (n_items + group - 1) / group;
   if (n_ckpt != want) {
     set_error("fbm_wire_tokenize_lom: %llu checkpoints for %llu items (one per %d items: %llu)", (unsigned long long)n_ckpt,
-              (unsigned long long)n_items, FBM_WIRE_LOM_GROUP, (unsigned long long)want);
+              (unsigned long long)n_items, group, (unsigned long long)want);
     return FBM_E_ARG;
   }
   if ((reinterpret_cast<uintptr_t>(ckpt) % 8) || (reinterpret_cast<uintptr_t>(result) % 8) ||
@@ -1580,17 +1582,41 @@ int fbm_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t span_
   });
 }
 
+uint64_t fbm_wire_tokenize_jl_workspace(uint64_t span_len) { return wire_tokenize_jl_workspace(span_len); }
+
+int fbm_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first, uint64_t n_items,
+                         uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n_items == 0) return FBM_OK;
+  int rc = wire_tokenize_checks(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace, 1);
+  if (rc) return rc;
+  return timed("wire_tokenize_jl", s, [&] {
+    return launch_wire_tokenize_jl(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace, s);
+  });
+}
+
 int fbm_wire_scan_deferred(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items,
                            const uint64_t* resolved, uint64_t n_resolved, fbm_wire_array* arrays, uint64_t arrays_cap,
                            uint64_t* n_arrays, uint64_t* ckpt, uint64_t ckpt_cap, uint64_t* n_ckpt,
                            fbm_wire_pending* pending) {
+  fbm_wire_pending2 p2 = {0, 0, 0, 0, 0};
+  const int rc = fbm_wire_scan_deferred2(data, len, min_items, defer_items, 0, resolved, n_resolved, arrays, arrays_cap,
+                                         n_arrays, ckpt, ckpt_cap, n_ckpt, defer_items > 0 && !pending ? nullptr : &p2);
+  if (rc == FBM_WIRE_PENDING) pending->begin = p2.begin, pending->first = p2.first, pending->n_items = p2.n_items;
+  return rc;
+}
+
+int fbm_wire_scan_deferred2(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items,
+                            uint64_t defer_items_jl, const uint64_t* resolved, uint64_t n_resolved,
+                            fbm_wire_array* arrays, uint64_t arrays_cap, uint64_t* n_arrays, uint64_t* ckpt,
+                            uint64_t ckpt_cap, uint64_t* n_ckpt, fbm_wire_pending2* pending) {
   if ((len > 0 && !data) || !n_arrays || !n_ckpt || (arrays_cap > 0 && !arrays) || (ckpt_cap > 0 && !ckpt) ||
-      (defer_items > 0 && (!pending || (n_resolved > 0 && !resolved)))) {
+      ((defer_items > 0 || defer_items_jl > 0) && (!pending || (n_resolved > 0 && !resolved)))) {
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
   fbm_wire_scan_out o = {arrays, arrays_cap, 0, ckpt, ckpt_cap, 0};
-  const fbm_wire_defer df = {defer_items, resolved, n_resolved, pending};
+  const fbm_wire_defer df = {defer_items, resolved, n_resolved, nullptr, defer_items_jl, pending};
   const int r = fbm_wire_scan_run(data, len, min_items, &o, &df);
   *n_arrays = o.n_arrays, *n_ckpt = o.n_ckpt;
   if (r == FBM_WIRE_SCAN_PENDING) return FBM_WIRE_PENDING;
@@ -1637,6 +1663,14 @@ int fbm_test_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span
   if (n_items == 0) return FBM_OK;
   int rc = wire_fold_lom_checks(span, ckpt, n_ckpt, n_items, acc);
   if (rc == FBM_OK) host_wire_fold_lom(span, span_len, span_base, ckpt, n_ckpt, n_items, acc, first);
+  return rc;
+}
+
+int fbm_test_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
+                              uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  if (n_items == 0) return FBM_OK;
+  int rc = wire_tokenize_checks(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace, 1);
+  if (rc == FBM_OK) host_wire_tokenize_jl(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace);
   return rc;
 }
 

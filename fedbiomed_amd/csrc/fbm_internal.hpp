@@ -363,6 +363,12 @@ void host_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, c
 // fbm_wire_tokenize_lom: the workspace's bytes, whether the span's tiles fit one launch's grid, the three launches,
 // and the same three passes over host buffers
 uint64_t wire_tokenize_workspace(uint64_t span_len);
+// fbm_wire_tokenize_jl: the same for an array of big-int maps (the tiles are the LOM tokenizer's: wire_tokenize_fits)
+uint64_t wire_tokenize_jl_workspace(uint64_t span_len);
+int launch_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                            uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s);
+void host_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                           uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
 bool wire_tokenize_fits(uint64_t span_len);
 int launch_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
                              uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s);

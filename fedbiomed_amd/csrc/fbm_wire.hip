@@ -30,6 +30,7 @@
 //                           issue, as for wire_decode_lom_kernel.
 //   wire_tok_*_kernel      the FBM_WIRE_LOM table itself, made on the device from the array's bytes
 //                           (fbm_wire_tokenize_lom): see "tokenize" below
+//   wire_tokj_*_kernel     the FBM_WIRE_JL table of an array of big-int maps (fbm_wire_tokenize_jl): "tokenize (JL)"
 // Every read of the message is checked against its length and every write against the output's capacity,
 // whatever the table holds.
 #include "fbm_internal.hpp"
@@ -405,6 +406,140 @@ __global__ void __launch_bounds__(FBM_WIRE_BLOCK, 4) wire_tok_emit_kernel(const 
   if (end >= 0 && (uint64_t)(sub + end) <= span_len) result[1] = base + (uint64_t)(sub + end);
 }
 
+// ---- tokenize (JL): the table of an array of big-int maps made on the device (fbm_wire_tokenize_jl) -----------
+// fbm_wire.hpp has the item's step, the tile's transfer map and the running state.  The stream is cut into the LOM
+// tokenizer's tiles (wire_tok_cut_of); one wave per tile, four tiles per workgroup.  Three launches:
+//   1. wire_tokj_maps_kernel  the tile's aligned dwords and the 24 bytes behind it into LDS, consecutive lanes
+//                             consecutive dwords; lane l tests the entry offsets l, l + 64, .. < 280 for the prefix
+//                             (a ballot packs the <= 14 matches into slots) and follows the chain of each match
+//                             through the tile -> maps[tile], 16 words
+//   2. wire_tokj_scan_kernel  one workgroup: thread t follows every entry of its run's first tile through the run,
+//                             thread 0 chains the 256 runs from the stream's entry offset, every thread then steps
+//                             through its run again and writes each tile's entry state; the items -> result[0]
+//   3. wire_tokj_emit_kernel  pass 1's staging again; lane 0 walks the tile's <= 179 items from its entry state and
+//                             leaves their table words in LDS, the wave stores them as consecutive 8-byte words
+// Algorithmic bytes: the stream read twice, 72 bytes per tile written and read back, 8 per item written.
+// LDS: FBM_WIRE_TOK_WAVES staged tiles of FBM_WIRE_TOKJ_WORDS words (pass 1: 16512 bytes); pass 3 adds
+// FBM_WIRE_TOKJ_ITEMS 8-byte words and two 4-byte words per wave (22272 bytes); pass 2 FBM_WIRE_TOKJ_SLOTS + 1 8-byte
+// words per thread (34816 bytes).  Bound: not HBM -- a tile's chain is a dependent walk of about 15 items by one
+// lane, each step seven LDS reads (DESIGN.md 4.2 has the measured times).
+static_assert(FBM_WIRE_TOKJ_REACH <= 5 * 64, "five rounds of 64 lanes cover the entry offsets");
+
+// a tile's words and the header bytes behind it into sh_tile; every wave of the workgroup comes through here (one
+// barrier), a wave past the last tile on zeros.  span + tbase is 4-byte aligned.
+__device__ __forceinline__ void wire_tokj_stage(const uint8_t* __restrict__ span, uint64_t span_len, int64_t tbase,
+                                                uint32_t* sh_tile) {
+  const int lane = threadIdx.x & 63;
+  for (int d = lane; d < FBM_WIRE_TOKJ_WORDS; d += 64) {
+    const int64_t off = tbase + 4 * d;
+    uint32_t v;
+    if (off >= 0 && (uint64_t)off + 4 <= span_len)
+      v = *reinterpret_cast<const uint32_t*>(span + off);
+    else
+      v = wire_tok_word(span, span_len, off);
+    sh_tile[d] = v;
+  }
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_tokj_maps_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                        int64_t origin, uint64_t tiles,
+                                                                        uint32_t* __restrict__ maps) {
+  __shared__ uint32_t sh_tile[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOKJ_WORDS];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t tile = (uint64_t)blockIdx.x * FBM_WIRE_TOK_WAVES + wave;
+  const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+  wire_tokj_stage(span, span_len, tbase, sh_tile[wave]);
+  if (tile >= tiles) return;  // (the whole wave)
+  const uint32_t* w = sh_tile[wave];
+  const int64_t left = (int64_t)span_len - tbase;
+  uint32_t used = 0;
+#pragma unroll 1
+  for (int r = 0; r < (FBM_WIRE_TOKJ_REACH + 63) / 64; ++r) {
+    const uint32_t e = (uint32_t)(r * 64 + lane);
+    const bool match = e < FBM_WIRE_TOKJ_REACH && wire_tokj_prefix(w, e);
+    const uint64_t found = __ballot(match);
+    if (match) {
+      const uint32_t slot = used + (uint32_t)__builtin_popcountll(found & ((1ull << lane) - 1ull));
+      if (slot < FBM_WIRE_TOKJ_SLOTS) {  // (always: matches are 20 bytes apart)
+        uint32_t items = 0;
+        const uint32_t exit = wire_tokj_chain(w, e, left, &items);
+        maps[tile * FBM_WIRE_TOKJ_SLOTS + slot] = wire_tokj_entry(e, exit, items);
+      }
+    }
+    used += (uint32_t)__builtin_popcountll(found);
+  }
+  if (lane < FBM_WIRE_TOKJ_SLOTS && (uint32_t)lane >= used) maps[tile * FBM_WIRE_TOKJ_SLOTS + lane] = ~0u;
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tokj_scan_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
+                                                                               uint32_t head, uint64_t n,
+                                                                               uint64_t* __restrict__ entry,
+                                                                               uint64_t* __restrict__ result) {
+  __shared__ uint64_t comp[FBM_WIRE_TOKJ_SLOTS][FBM_WIRE_SCAN_THREADS];  // [slot][thread]: consecutive threads, consecutive banks
+  __shared__ uint64_t ent[FBM_WIRE_SCAN_THREADS];
+  const int t = threadIdx.x;
+  uint64_t b0, b1;
+  wire_tok_run(tiles, t, &b0, &b1);
+#pragma unroll 1
+  for (int k = 0; k < FBM_WIRE_TOKJ_SLOTS; ++k) {
+    uint64_t s = FBM_WIRE_TOKJ_GONE;
+    if (b0 < b1) {
+      const uint32_t m = maps[b0 * FBM_WIRE_TOKJ_SLOTS + k];
+      if (m != ~0u) {
+        s = (uint64_t)(m & 0x1ffu);
+        for (uint64_t b = b0; b < b1 && (s & 0xffffull) != FBM_WIRE_TOKJ_GONE; ++b) s = wire_tokj_apply(s, maps + b * FBM_WIRE_TOKJ_SLOTS);
+      }
+    }
+    comp[k][t] = s;
+  }
+  __syncthreads();
+  if (t == 0) {
+    uint64_t st = head;
+    for (int u = 0; u < FBM_WIRE_SCAN_THREADS; ++u) {
+      ent[u] = st;
+      uint64_t c0, c1;
+      wire_tok_run(tiles, u, &c0, &c1);
+      if (c0 < c1) st = wire_tokj_apply_run(st, maps + c0 * FBM_WIRE_TOKJ_SLOTS, &comp[0][u], FBM_WIRE_SCAN_THREADS);
+    }
+    result[0] = (st >> 16) < n ? (st >> 16) : n;
+    result[1] = 0;  // wire_tokj_emit_kernel writes the end where item n - 1 is one of the chain's
+  }
+  __syncthreads();
+  uint64_t st = ent[t];
+  for (uint64_t b = b0; b < b1; ++b) {
+    entry[b] = st;
+    st = wire_tokj_apply(st, maps + b * FBM_WIRE_TOKJ_SLOTS);
+  }
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_tokj_emit_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                        int64_t origin, uint64_t tiles,
+                                                                        const uint64_t* __restrict__ entry, uint64_t base,
+                                                                        uint64_t n, uint64_t* __restrict__ ckpt,
+                                                                        uint64_t n_ckpt, uint64_t* __restrict__ result) {
+  __shared__ uint32_t sh_tile[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOKJ_WORDS];
+  __shared__ uint64_t sh_out[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOKJ_ITEMS];
+  __shared__ int sh_meta[FBM_WIRE_TOK_WAVES][2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t tile = (uint64_t)blockIdx.x * FBM_WIRE_TOK_WAVES + wave;
+  const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+  wire_tokj_stage(span, span_len, tbase, sh_tile[wave]);
+  const uint64_t st = tile < tiles ? entry[tile] : FBM_WIRE_TOKJ_GONE;
+  if (lane == 0) {
+    int end = -1;
+    const uint32_t cnt = wire_tokj_emit_walk(sh_tile[wave], st, (int64_t)span_len - tbase, (int64_t)base + tbase, n, sh_out[wave], &end);
+    sh_meta[wave][0] = (int)cnt, sh_meta[wave][1] = end;
+  }
+  __syncthreads();
+  const uint32_t cnt = (uint32_t)sh_meta[wave][0];
+  const int end = sh_meta[wave][1];
+  const uint64_t k0 = st >> 16;
+  for (uint32_t j = lane; j < cnt; j += 64)
+    if (k0 + j < n_ckpt) ckpt[k0 + j] = sh_out[wave][j];
+  if (lane == 0 && end >= 0) result[1] = (uint64_t)((int64_t)base + tbase + end);
+}
+
 static int wire_grid(uint64_t blocks, const char* what, unsigned& g) {
   if (blocks > 0x7fffffffull) {
     set_error("%s: %llu workgroups exceed one launch's grid", what, (unsigned long long)blocks);
@@ -507,6 +642,28 @@ int launch_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t ba
   return check_launch("wire_tok_emit_kernel");
 }
 
+uint64_t wire_tokenize_jl_workspace(uint64_t span_len) {
+  const uint64_t tiles = (span_len + 3 + FBM_WIRE_TOK_TILE - 1) / FBM_WIRE_TOK_TILE;  // whatever the alignment
+  return (wire_tokj_workspace_of(tiles) + 255) / 256 * 256 + 256;
+}
+
+int launch_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                            uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s) {
+  const wire_tok_cut c = wire_tok_cut_of(span, span_len, first - base);
+  unsigned g = 0;
+  int rc = wire_grid((c.tiles + FBM_WIRE_TOK_WAVES - 1) / FBM_WIRE_TOK_WAVES, "fbm_wire_tokenize_jl", g);
+  if (rc) return rc;
+  uint64_t* entry = reinterpret_cast<uint64_t*>(workspace);
+  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(c.tiles));
+  hipLaunchKernelGGL(wire_tokj_maps_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, c.origin, c.tiles, maps);
+  if ((rc = check_launch("wire_tokj_maps_kernel"))) return rc;
+  hipLaunchKernelGGL(wire_tokj_scan_kernel, dim3(1), dim3(FBM_WIRE_SCAN_THREADS), 0, s, maps, c.tiles, c.head, n, entry, result);
+  if ((rc = check_launch("wire_tokj_scan_kernel"))) return rc;
+  hipLaunchKernelGGL(wire_tokj_emit_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, c.origin, c.tiles, entry, base,
+                     n, ckpt, n_ckpt, result);
+  return check_launch("wire_tokj_emit_kernel");
+}
+
 // ---- the same per-item routines on the host (the test build's hooks) ------------------------------
 int host_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total) {
   uint64_t p = 0;
@@ -565,6 +722,11 @@ void host_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, c
 void host_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
                             uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
   wire_tokenize_host(span, span_len, base, first, n, ckpt, n_ckpt, result, workspace);
+}
+
+void host_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                           uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  wire_tokenize_jl_host(span, span_len, base, first, n, ckpt, n_ckpt, result, workspace);
 }
 
 }  // namespace fbm

@@ -328,4 +328,184 @@ inline void wire_tokenize_host(const uint8_t* span, uint64_t span_len, uint64_t 
   }
 }
 
+// ---- tokenize (JL): where the values of an array of big-int maps start ------------------------------
+// An item is 23..280 bytes and its size is a function of the 24 bytes at its start (the 20-byte prefix, c4 L or
+// c5 BE16 L, the value's first byte), so whether an accepted item starts at a byte and how long it is can be
+// asked of any position on its own.  With tiles of FBM_WIRE_TOK_TILE >= 280 bytes, cut as the LOM stream is cut
+// (wire_tok_cut_of), the chain of items that enters a tile at offset e < 280 leaves it at an offset < 280 into the
+// next one: a tile's transfer map takes an entry offset to (exit offset, items completed in between), or to "dead"
+// with the items completed before the position that holds no accepted item.  Only an entry offset at which the
+// whole prefix stands can start anything, and the prefix holds 82 at its head alone, so two such offsets are at
+// least 20 bytes apart: at most 14 of them in [0, 280).  A map is FBM_WIRE_TOKJ_SLOTS packed words,
+//   entry offset | exit offset << 9 | items << 18      (an unused slot: all ones; a dead exit: FBM_WIRE_TOKJ_DEAD)
+// and maps compose by looking the exit offset up among the next map's entries; an offset that is not there is dead.
+// A running state is  items << 16 | offset  (offset FBM_WIRE_TOKJ_GONE: dead, the items stay).  An item the span's
+// end cuts off is no item: the chain dies in front of it, so the items of a state are all whole.
+#define FBM_WIRE_TOKJ_REACH 280                                   // = FBM_WIRE_ITEM_MAX: entry and exit offsets lie below
+#define FBM_WIRE_TOKJ_SLOTS 16                                    // words of a tile's map (14 entries at most)
+#define FBM_WIRE_TOKJ_HEAD 24                                     // bytes that decide an item's size
+#define FBM_WIRE_TOKJ_WORDS ((FBM_WIRE_TOK_TILE + FBM_WIRE_TOKJ_HEAD) / 4 + 2)  // a staged tile: its words, a header across its end
+#define FBM_WIRE_TOKJ_ITEMS ((FBM_WIRE_TOK_TILE + 22) / 23)       // items that start in one tile at most: 179
+#define FBM_WIRE_TOKJ_DEAD 0x1ffu                                 // a map entry's exit: the chain ended in the tile
+#define FBM_WIRE_TOKJ_GONE 0xffffull                              // a state's offset: the chain has ended
+static_assert(FBM_WIRE_TOK_TILE >= FBM_WIRE_TOKJ_REACH && FBM_WIRE_TOKJ_REACH == FBM_WIRE_ITEM_MAX, "a chain skips no tile");
+static_assert(FBM_WIRE_TOKJ_ITEMS < 256 && FBM_WIRE_TOKJ_REACH < (int)FBM_WIRE_TOKJ_DEAD, "a map entry's fields");
+static_assert((FBM_WIRE_TOKJ_REACH + 19) / 20 <= FBM_WIRE_TOKJ_SLOTS, "prefix matches are 20 bytes apart");
+
+// the 4 bytes at byte offset `off` of a staged tile (w: its aligned words) as a little-endian word
+FBM_HD uint32_t wire_tokj_u32(const uint32_t* w, uint32_t off) {
+  const uint32_t q = off >> 2, sh = 8 * (off & 3);
+  const uint64_t two = (uint64_t)w[q] | ((uint64_t)w[q + 1] << 32);
+  return (uint32_t)(two >> sh);
+}
+// whether the 20-byte prefix stands at offset `off` of a staged tile
+FBM_HD bool wire_tokj_prefix(const uint32_t* w, uint32_t off) {
+  return wire_tokj_u32(w, off) == 0x5f5fa882u && wire_tokj_u32(w, off + 4) == 0x65707974u &&
+         wire_tokj_u32(w, off + 8) == 0x69a35f5fu && wire_tokj_u32(w, off + 12) == 0x76a5746eu &&
+         wire_tokj_u32(w, off + 16) == 0x65756c61u;
+}
+// The item at offset `off` (< FBM_WIRE_TOK_TILE) of a staged tile, `left` bytes of the span being left from there
+// (<= 0: none): its size, 0 where fbm_wire_item accepts no map form there or the item runs past the span; *L its
+// value's bytes.  Reads the staged words only (bytes outside the span are staged as 0).
+FBM_HD uint32_t wire_tokj_step(const uint32_t* w, uint32_t off, int64_t left, uint32_t* L) {
+  if (!wire_tokj_prefix(w, off)) return 0;
+  const uint32_t h = wire_tokj_u32(w, off + 20);  // c4 L v0 .. / c5 Lhi Llo v0
+  const uint32_t b = h & 0xffu;
+  uint32_t len, hdr, v0;
+  if (b == 0xc4u)
+    len = (h >> 8) & 0xffu, hdr = 22, v0 = (h >> 16) & 0xffu;
+  else if (b == 0xc5u)
+    len = ((h >> 8) & 0xffu) << 8 | ((h >> 16) & 0xffu), hdr = 23, v0 = h >> 24;
+  else
+    return 0;
+  if (len < 1 || len > 257 || (int64_t)(hdr + len) > left) return 0;
+  if (v0 >= 0x80u || (len == 257 && v0 != 0)) return 0;  // a negative value, or one of 2^2048 or more
+  *L = len;
+  return hdr + len;
+}
+// The chain that enters a staged tile at offset `e` (`left` bytes of the span from the tile's first byte on): the
+// offset into the next tile at which it leaves, or FBM_WIRE_TOKJ_DEAD; *items the items completed on the way.
+FBM_HD uint32_t wire_tokj_chain(const uint32_t* w, uint32_t e, int64_t left, uint32_t* items) {
+  uint32_t off = e, c = 0, L = 0;
+  while (off < FBM_WIRE_TOK_TILE) {
+    const uint32_t s = wire_tokj_step(w, off, left - (int64_t)off, &L);
+    if (s == 0) {
+      *items = c;
+      return FBM_WIRE_TOKJ_DEAD;
+    }
+    off += s, ++c;
+  }
+  *items = c;
+  return off - FBM_WIRE_TOK_TILE;
+}
+FBM_HD uint32_t wire_tokj_entry(uint32_t e, uint32_t exit, uint32_t items) { return e | exit << 9 | items << 18; }
+// a state stepped through one map (FBM_WIRE_TOKJ_SLOTS words)
+FBM_HD uint64_t wire_tokj_apply(uint64_t state, const uint32_t* map) {
+  const uint64_t off = state & 0xffffull;
+  if (off == FBM_WIRE_TOKJ_GONE) return state;
+  for (int k = 0; k < FBM_WIRE_TOKJ_SLOTS; ++k) {
+    const uint32_t m = map[k];
+    if ((m & 0x1ffu) == off) {  // (an unused slot's entry offset is 511: never an offset)
+      const uint32_t exit = (m >> 9) & 0x1ffu;
+      return ((state >> 16) + (m >> 18 & 0xffu)) << 16 | (exit == FBM_WIRE_TOKJ_DEAD ? FBM_WIRE_TOKJ_GONE : (uint64_t)exit);
+    }
+  }
+  return state | FBM_WIRE_TOKJ_GONE;
+}
+// a state stepped through a run of tiles whose composite from each of its first map's entries is comp[]
+FBM_HD uint64_t wire_tokj_apply_run(uint64_t state, const uint32_t* first_map, const uint64_t* comp, int stride) {
+  const uint64_t off = state & 0xffffull;
+  if (off == FBM_WIRE_TOKJ_GONE) return state;
+  for (int k = 0; k < FBM_WIRE_TOKJ_SLOTS; ++k)
+    if ((first_map[k] & 0x1ffu) == off) {
+      const uint64_t c = comp[k * stride];
+      return ((state >> 16) + (c >> 16)) << 16 | (c & 0xffffull);
+    }
+  return state | FBM_WIRE_TOKJ_GONE;
+}
+// The emit walk of one staged tile from its entry state: word j of `out` (FBM_WIRE_TOKJ_ITEMS words) is the table's
+// word of item (state >> 16) + j -- (absolute offset of the value's first byte) << 16 | L --; returns how many;
+// *end_off the tile offset one past item n - 1 where that item is among them, else -1.  abs0 = the absolute offset
+// of the tile's first byte (as a signed value: the first tile may begin up to 3 bytes in front of the span).
+FBM_HD uint32_t wire_tokj_emit_walk(const uint32_t* w, uint64_t state, int64_t left, int64_t abs0, uint64_t n, uint64_t* out,
+                                    int* end_off) {
+  const uint64_t k0 = state >> 16;
+  uint32_t off = (uint32_t)(state & 0xffffull), c = 0, L = 0;
+  *end_off = -1;
+  if (off == (uint32_t)FBM_WIRE_TOKJ_GONE) return 0;
+  while (off < FBM_WIRE_TOK_TILE && c < FBM_WIRE_TOKJ_ITEMS && k0 + c < n) {
+    const uint32_t s = wire_tokj_step(w, off, left - (int64_t)off, &L);
+    if (s == 0) break;
+    out[c] = (uint64_t)(abs0 + (int64_t)(off + s - L)) << 16 | L;
+    off += s;
+    if (k0 + c == n - 1) *end_off = (int)off;
+    ++c;
+  }
+  return c;
+}
+
+// workspace: every tile's entry state (u64 each, rounded up to 256 bytes), then every tile's map
+inline uint64_t wire_tokj_workspace_of(uint64_t tiles) { return wire_tok_maps_at(tiles) + tiles * FBM_WIRE_TOKJ_SLOTS * 4; }
+
+// one tile staged on the host as the kernels stage it
+inline void wire_tokj_host_stage(const uint8_t* span, uint64_t span_len, int64_t tbase, uint32_t* w) {
+  for (int d = 0; d < FBM_WIRE_TOKJ_WORDS; ++d) w[d] = wire_tok_word(span, span_len, tbase + 4 * d);
+}
+inline void wire_tokj_host_map(const uint32_t* w, int64_t left, uint32_t* map) {
+  int slot = 0;
+  for (int k = 0; k < FBM_WIRE_TOKJ_SLOTS; ++k) map[k] = ~0u;
+  for (uint32_t e = 0; e < FBM_WIRE_TOKJ_REACH; ++e)
+    if (wire_tokj_prefix(w, e) && slot < FBM_WIRE_TOKJ_SLOTS) {
+      uint32_t items = 0;
+      const uint32_t exit = wire_tokj_chain(w, e, left, &items);
+      map[slot++] = wire_tokj_entry(e, exit, items);
+    }
+}
+
+// fbm_wire_tokenize_jl's three kernels (fbm_wire.hip) over host buffers, tile by tile and run by run as the kernels
+// cut them, through the same routines (host_wire_tokenize_jl; tools/wire_tokenize_jl_check.cpp runs it under the host
+// sanitizers).  Reads span[0, span_len) and no more; writes ckpt[0, n_ckpt), result[0, 2) and the workspace.
+inline void wire_tokenize_jl_host(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                                  uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  const wire_tok_cut c = wire_tok_cut_of(span, span_len, first - base);
+  uint64_t* entry = reinterpret_cast<uint64_t*>(workspace);
+  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(c.tiles));
+  uint32_t w[FBM_WIRE_TOKJ_WORDS];
+  for (uint64_t tile = 0; tile < c.tiles; ++tile) {  // wire_tokj_maps_kernel
+    const int64_t tbase = c.origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+    wire_tokj_host_stage(span, span_len, tbase, w);
+    wire_tokj_host_map(w, (int64_t)span_len - tbase, maps + tile * FBM_WIRE_TOKJ_SLOTS);
+  }
+  uint64_t st = c.head;  // wire_tokj_scan_kernel
+  for (int t = 0; t < FBM_WIRE_TOK_SCAN_THREADS; ++t) {
+    uint64_t b0, b1, comp[FBM_WIRE_TOKJ_SLOTS];
+    wire_tok_run(c.tiles, t, &b0, &b1);
+    if (b0 == b1) continue;
+    for (int k = 0; k < FBM_WIRE_TOKJ_SLOTS; ++k) {
+      const uint32_t m = maps[b0 * FBM_WIRE_TOKJ_SLOTS + k];
+      uint64_t s = m == ~0u ? FBM_WIRE_TOKJ_GONE : (uint64_t)(m & 0x1ffu);
+      for (uint64_t b = b0; b < b1; ++b) s = wire_tokj_apply(s, maps + b * FBM_WIRE_TOKJ_SLOTS);
+      comp[k] = s;
+    }
+    uint64_t in = st;
+    for (uint64_t b = b0; b < b1; ++b) {
+      entry[b] = in;
+      in = wire_tokj_apply(in, maps + b * FBM_WIRE_TOKJ_SLOTS);
+    }
+    st = wire_tokj_apply_run(st, maps + b0 * FBM_WIRE_TOKJ_SLOTS, comp, 1);  // (= in)
+  }
+  result[0] = (st >> 16) < n ? (st >> 16) : n;
+  result[1] = 0;
+  uint64_t out[FBM_WIRE_TOKJ_ITEMS];
+  for (uint64_t tile = 0; tile < c.tiles; ++tile) {  // wire_tokj_emit_kernel
+    const int64_t tbase = c.origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+    wire_tokj_host_stage(span, span_len, tbase, w);
+    int end = -1;
+    const uint32_t cnt = wire_tokj_emit_walk(w, entry[tile], (int64_t)span_len - tbase, (int64_t)base + tbase, n, out, &end);
+    for (uint32_t j = 0; j < cnt; ++j)
+      if ((entry[tile] >> 16) + j < n_ckpt) ckpt[(entry[tile] >> 16) + j] = out[j];
+    if (end >= 0) result[1] = (uint64_t)((int64_t)base + tbase + end);
+  }
+}
+
 }  // namespace fbm

@@ -18,7 +18,8 @@
 //
 // fbm_wire_scan_deferred is the same pass (fbm_wire_scan_run) with one more branch: a large array whose first byte is
 // a native form is not walked here when the caller brings its end offset from the device tokenizer
-// (fbm_wire_tokenize_lom); see fbm_wire_defer below.
+// (fbm_wire_tokenize_lom); fbm_wire_scan_deferred2 does the same for a large array of big-int maps
+// (fbm_wire_tokenize_jl); see fbm_wire_defer below.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -135,12 +136,20 @@ static inline uint64_t fbm_wire_be(const uint8_t* p, int bytes) {
 // elsewhere (the device tokenizer) -- it is recorded as FBM_WIRE_LOM with no checkpoints and pad = 1, and the
 // pass goes on behind it; resolved[k] == 0: walked here like every other; k >= n_resolved: the pass stops with
 // FBM_WIRE_SCAN_PENDING and *pending says which array the caller is to resolve before it runs the pass again.
+//
+// fbm_wire_scan_deferred2 adds the arrays of big-int maps: an array of at least max(min_items, defer_items_jl) items
+// whose first item begins with the whole 20-byte prefix and c4 / c5, and whose items at their smallest (23 bytes
+// each) fit the bytes left, is a candidate too (for fbm_wire_tokenize_jl).  Candidates of both kinds take the
+// message's FBM_WIRE_MAX_DEFERRED slots in order of appearance; a resolved one is recorded under its own scheme.
 struct fbm_wire_defer {
-  uint64_t defer_items;  // 0: no array is a candidate
+  uint64_t defer_items;  // 0: no all-native array is a candidate
   const uint64_t* resolved;
   uint64_t n_resolved;
-  fbm_wire_pending* pending;
+  fbm_wire_pending* pending;    // either may be null
+  uint64_t defer_items_jl;      // 0: no array of maps is a candidate
+  fbm_wire_pending2* pending2;  // as pending, with the candidate's scheme
 };
+#define FBM_WIRE_JL_ITEM_MIN 23  // the smallest map item: prefix, c4 01, one byte
 
 // FBM_OK, FBM_WIRE_SCAN_GAVE_UP or FBM_WIRE_SCAN_FULL, with df also FBM_WIRE_SCAN_PENDING or FBM_WIRE_SCAN_BAD_END; on
 // anything but FBM_OK the counts are zero.  df == nullptr: fbm_wire_scan's pass.
@@ -213,12 +222,25 @@ static inline int fbm_wire_scan_run(const uint8_t* d, uint64_t len, uint64_t min
         pos += skip;
         continue;
       }
-      if (is_array && children >= min_items && df && df->defer_items && children >= df->defer_items &&
-          candidates < FBM_WIRE_MAX_DEFERRED && children <= left - skip &&
-          (d[pos + skip] <= 0x7f || (d[pos + skip] >= 0xcc && d[pos + skip] <= 0xcf))) {
+      int cand = -1;  // the scheme a deferral candidate is recorded under
+      if (is_array && children >= min_items && df && candidates < FBM_WIRE_MAX_DEFERRED) {
+        const uint64_t body = left - skip;
+        if (df->defer_items && children >= df->defer_items && children <= body &&
+            (d[pos + skip] <= 0x7f || (d[pos + skip] >= 0xcc && d[pos + skip] <= 0xcf)))
+          cand = FBM_WIRE_LOM;
+        else if (df->defer_items_jl && children >= df->defer_items_jl && children <= body / FBM_WIRE_JL_ITEM_MIN &&
+                 memcmp(d + pos + skip, FBM_WIRE_PREFIX, FBM_WIRE_PREFIX_LEN) == 0 &&
+                 (d[pos + skip + FBM_WIRE_PREFIX_LEN] == 0xc4 || d[pos + skip + FBM_WIRE_PREFIX_LEN] == 0xc5))
+          cand = FBM_WIRE_JL;  // (children >= 1 and 23 children <= body: the 21 bytes compared lie inside the message)
+      }
+      if (cand >= 0) {
         const uint64_t k = candidates++;
         if (k >= df->n_resolved) {
-          df->pending->begin = pos, df->pending->first = pos + skip, df->pending->n_items = children;
+          if (df->pending) df->pending->begin = pos, df->pending->first = pos + skip, df->pending->n_items = children;
+          if (df->pending2) {
+            df->pending2->begin = pos, df->pending2->first = pos + skip, df->pending2->n_items = children;
+            df->pending2->scheme = cand, df->pending2->pad = 0;
+          }
           o->n_arrays = o->n_ckpt = 0;
           return FBM_WIRE_SCAN_PENDING;
         }
@@ -235,7 +257,7 @@ static inline int fbm_wire_scan_run(const uint8_t* d, uint64_t len, uint64_t min
           fbm_wire_array* a = &o->arrays[o->n_arrays++];
           a->begin = pos, a->end = end, a->n_items = children;
           a->ckpt_first = o->n_ckpt, a->ckpt_count = 0;
-          a->scheme = FBM_WIRE_LOM, a->pad = 1;  // the table is on the device
+          a->scheme = cand, a->pad = 1;  // the table is on the device
           pos = end;
           continue;
         }

@@ -204,12 +204,18 @@ class ChunkAssembler:
 # `:140-149`): one msgpack item per ciphertext / element.  `dumps_reference` / `loads_reference` produce and
 # consume exactly those bytes from the packed device form (the C ABI's fbm_wire_encode / fbm_wire_scan /
 # fbm_wire_decode), so only this side needs its two Serializer lines ("One patched side").
-_STATS = {"fast": 0, "fallback": 0, "resident": 0, "device_scan": 0, "device_scan_refused": 0}
+_STATS = {"fast": 0, "fallback": 0, "resident": 0, "device_scan": 0, "device_scan_refused": 0, "device_scan_jl": 0,
+          "device_scan_jl_refused": 0}
 # `loads_reference(resident=True)` leaves an all-native array of at least this many items to the device tokenizer
 # (fbm_wire_tokenize_lom) instead of the host scanner's walk: the smallest power of two from which on the device
 # route's take was the faster one on an MI355X (tools/wire_ref_ab.py --devscan, profiles/wire_devscan_ab.jsonl,
 # 0.71 ms against 0.76 here, 1.3 against 2.8 at 2^20, 10.1 against 38.1 at 2^24).
 DEVICE_SCAN_MIN_ITEMS = 1 << 16
+# The same for an array of at least this many big-int maps (a JL update; fbm_wire_tokenize_jl): the smallest power of
+# two from which on the device route's median take was the lower one (tools/wire_ref_ab.py --devscan-jl,
+# profiles/wire_devscan_jl_ab.jsonl, DESIGN.md 4.2: 0.95 ms against 1.00 here, 2.8 against 4.0 at 2^17, 8.8 against
+# 14.6 at 2^19).
+DEVICE_SCAN_JL_MIN_ITEMS = 1 << 14
 _LAST: Dict[str, Any] = {}  # the last call's phases in seconds (tools/wire_ref_ab.py)
 _PHASE_TIMING = False  # tools/wire_ref_ab.py sets it: the resident upload then synchronises to time its "h2d"
 
@@ -218,11 +224,13 @@ def reference_stats(reset: bool = False) -> Dict[str, Any]:
     """Updates that took the device path ("fast"), updates that stayed on the device (`loads_reference` with
     ``resident=True``: "resident") and updates or messages that took msgpack's ("fallback") since the last
     reset, the arrays whose table the device made ("device_scan") and those its tokenizer refused, which the host
-    scanner then walked ("device_scan_refused"), and the last call's phase times ("last": scan / h2d / devscan /
-    kernel / d2h seconds)."""
+    scanner then walked ("device_scan_refused") -- both count all-native arrays; "device_scan_jl" and
+    "device_scan_jl_refused" count the arrays of big-int maps in the same way --, and the last call's phase times
+    ("last": scan / h2d / devscan / kernel / d2h seconds; devscan covers both tokenizers)."""
     out = dict(_STATS, last=dict(_LAST))
     if reset:
-        _STATS.update(fast=0, fallback=0, resident=0, device_scan=0, device_scan_refused=0)
+        _STATS.update(fast=0, fallback=0, resident=0, device_scan=0, device_scan_refused=0, device_scan_jl=0,
+                      device_scan_jl_refused=0)
         _LAST.clear()
     return out
 
@@ -409,18 +417,19 @@ def _upload_arrays(data: bytes, arrays: list) -> list:
     return handles
 
 
-def _scan_resident(data: bytes, min_items: int, defer_items: int):
+def _scan_resident(data: bytes, min_items: int, defer_items: int, defer_jl_items: int = 0):
     """The scan of `loads_reference(resident=True)` (the same seam): `_device.wire_scan_resident`'s (arrays, handles)."""
     from . import _device as D
 
     timing: Dict[str, float] = {}
-    out = D.wire_scan_resident(data, min_items, defer_items, timing, _STATS, sync_phases=_PHASE_TIMING)
+    out = D.wire_scan_resident(data, min_items, defer_items, timing, _STATS, sync_phases=_PHASE_TIMING,
+                               defer_jl_items=defer_jl_items)
     _LAST.update(timing)
     return out
 
 
 def loads_reference(data: bytes, object_hook=None, min_items: int = 1024, resident: bool = False,
-                    device_scan_min_items: Optional[int] = None) -> Any:
+                    device_scan_min_items: Optional[int] = None, device_scan_jl_min_items: Optional[int] = None) -> Any:
     """``msgpack.unpackb(data, object_hook=object_hook, strict_map_key=False)`` with every integer array of at
     least `min_items` items the host scanner records read on the device: it comes back as an `EncryptedParams`
     (which compares as the list of ints msgpack would have made) whose ``packed`` is ready for `aggregate` /
@@ -434,7 +443,10 @@ def loads_reference(data: bytes, object_hook=None, min_items: int = 1024, reside
     size disables it) is not walked by the host scanner: the message goes up from that array's header on and the
     device finds the items' starts (`reference_stats` counts "device_scan"); what its tokenizer refuses -- an array
     that is not all native, such as a JL update whose first ciphertext is below 2^64 -- takes the host walk as
-    before ("device_scan_refused").  ``resident=False`` keeps the host scan: its cost is the Python ints."""
+    before ("device_scan_refused").  An array of at least `device_scan_jl_min_items` big-int maps (None:
+    `DEVICE_SCAN_JL_MIN_ITEMS`) goes the same way through the tokenizer for that form ("device_scan_jl"; a mixed
+    array is refused and walked on the host: "device_scan_jl_refused") -- only where `object_hook` reads the map as
+    the reference's does.  ``resident=False`` keeps the host scan: its cost is the Python ints."""
     import os
     import time
 
@@ -446,13 +458,15 @@ def loads_reference(data: bytes, object_hook=None, min_items: int = 1024, reside
     held: Dict[int, Any] = {}  # the arrays the device tokenized: index -> handle
     if resident:
         dmin = DEVICE_SCAN_MIN_ITEMS if device_scan_min_items is None else int(device_scan_min_items)
-        arrays, held = _scan_resident(data, min_items, max(dmin, 1))
+        jmin = DEVICE_SCAN_JL_MIN_ITEMS if device_scan_jl_min_items is None else int(device_scan_jl_min_items)
+        # (an array of maps is this library's only under a hook that reads them: otherwise it never goes up)
+        arrays, held = _scan_resident(data, min_items, max(dmin, 1), max(jmin, 1) if _hook_reads_ints(object_hook) else 0)
     else:
         t0 = time.perf_counter()
         arrays = D.wire_scan(data, min_items)
         _LAST["scan"] = time.perf_counter() - t0
     if arrays and not _hook_reads_ints(object_hook):
-        keep = [i for i, a in enumerate(arrays) if a[3] != "jl"]  # (a tokenized array is "lom": it stays)
+        keep = [i for i, a in enumerate(arrays) if a[3] != "jl"]  # (a tokenized "jl" array exists only under such a hook)
         arrays, held = [arrays[i] for i in keep], {k: held[i] for k, i in enumerate(keep) if i in held}
     if not arrays:
         _STATS["fallback"] += 1

@@ -430,7 +430,8 @@ int fbm_ass_reconstruct_wide(const uint32_t* shares, int n_shares, int l, uint64
  * scheme, and its checkpoints ckpt[ckpt_first .. ckpt_first + ckpt_count) -- all absolute byte offsets into
  * the message.  FBM_WIRE_JL: one per item, (offset of the value's first big-endian byte) << 16 | byte count
  * (1..257).  FBM_WIRE_LOM: one per FBM_WIRE_LOM_GROUP items, the offset of the group's first item.  pad is 0,
- * or 1 where fbm_wire_scan_deferred left the array's table to the device (ckpt_count is then 0). */
+ * or 1 where fbm_wire_scan_deferred / fbm_wire_scan_deferred2 left the array's table to the device (ckpt_count is
+ * then 0). */
 typedef struct fbm_wire_array {
   uint64_t begin, end, n_items, ckpt_first, ckpt_count;
   int32_t scheme, pad;
@@ -527,6 +528,47 @@ int fbm_wire_scan_deferred(const uint8_t* data, uint64_t len, uint64_t min_items
                            const uint64_t* resolved, uint64_t n_resolved, fbm_wire_array* arrays, uint64_t arrays_cap,
                            uint64_t* n_arrays, uint64_t* ckpt, uint64_t ckpt_cap, uint64_t* n_ckpt,
                            fbm_wire_pending* pending);
+
+/* The table of an array of big-int maps made on the device (additions under ABI 7, like the three above).  An item
+ * is 23..280 bytes and its size is a function of the 24 bytes at its start, so a 4 KiB tile's transfer map -- entry
+ * offset < 280 to exit offset < 280 and the items between, at most 14 live entries -- is made per tile, the maps are
+ * scanned from the entry `first` gives, and a last pass walks each tile from its now known entry.
+ *
+ * fbm_wire_tokenize_jl: span (device) holds the message's bytes [span_base, span_base + span_len); first is the
+ * absolute offset of item 0; ckpt (device, n_ckpt = n_items words), result (device, 2 words) and workspace (device,
+ * fbm_wire_tokenize_jl_workspace(span_len) bytes) are 8-byte aligned.  On the stream:
+ *   result[0]  the leading items, at most n_items, that the host scanner accepts as the map form -- the exact 20-byte
+ *              prefix, c4 L or c5 BE16 L (minimal or not), 1 <= L <= 257, a first value byte < 0x80 that is 0 where
+ *              L == 257 -- and that lie wholly inside the span.  Counting stops at the first position that holds no
+ *              such item, a native int included; only the chain from `first` decides what starts an item (a payload
+ *              that holds a whole item's bytes starts none)
+ *   result[1]  where result[0] == n_items: the absolute offset one past item n_items - 1, whatever follows it; else 0
+ *   ckpt[i]    where result[0] == n_items: (offset of the value's first byte) << 16 | L, word for word the table
+ *              fbm_wire_scan writes for the same array; else unspecified
+ * No byte outside the span is read and nothing outside ckpt, result and workspace is written, whatever the bytes
+ * are.  n_items == 0 is FBM_OK (nothing runs).  Then, before any device call: a null pointer, n_ckpt != n_items, a
+ * ckpt, result or workspace off an 8-byte boundary and a first outside the span are FBM_E_ARG; n_items >= 2^32 and
+ * more workgroups than one launch's grid FBM_E_UNSUPPORTED. */
+uint64_t fbm_wire_tokenize_jl_workspace(uint64_t span_len);
+int fbm_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
+                         uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace,
+                         void* stream);
+
+/* fbm_wire_scan_deferred with the large arrays of big-int maps left to fbm_wire_tokenize_jl as well: an array of at
+ * least max(min_items, defer_items_jl) items whose first item begins with the whole 20-byte prefix and c4 / c5, and
+ * with 23 n_items <= the bytes left, is a candidate too.  Candidates of both kinds share the message's 8 slots in
+ * order of appearance; a resolved one is recorded under its own scheme (ckpt_count = 0, pad = 1), one answered with
+ * 0 is walked on the host, an unanswered one returns FBM_WIRE_PENDING with pending->scheme set (FBM_WIRE_JL /
+ * FBM_WIRE_LOM).  defer_items_lom as fbm_wire_scan_deferred's defer_items; defer_items_jl == 0 is that function
+ * exactly.  pending may be null only where both thresholds are 0. */
+typedef struct fbm_wire_pending2 {
+  uint64_t begin, first, n_items; /* the array's header, its first item, its items */
+  int32_t scheme, pad;
+} fbm_wire_pending2;
+int fbm_wire_scan_deferred2(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
+                            uint64_t defer_items_jl, const uint64_t* resolved, uint64_t n_resolved,
+                            fbm_wire_array* arrays, uint64_t arrays_cap, uint64_t* n_arrays, uint64_t* ckpt,
+                            uint64_t ckpt_cap, uint64_t* n_ckpt, fbm_wire_pending2* pending);
 
 /* Drops the library's host-side caches: the short path's constant C per (N, |key|) -- kept under a
  * SHA-256 digest of (N, |key|), never the key itself, and zeroed here and on eviction -- and the

@@ -139,6 +139,9 @@ int fbm_test_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span
                            uint64_t n_ckpt, uint64_t n_items, uint64_t* acc, int first);
 /* fbm_wire_tokenize_lom over HOST buffers: the kernels' three passes tile by tile through the same per-block
  * routines (host_wire_tokenize_lom), same arguments and argument errors. */
+/* fbm_wire_tokenize_jl over HOST buffers, in the same way (host_wire_tokenize_jl). */
+int fbm_test_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
+                              uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
 int fbm_test_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
                                uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
 

@@ -28,17 +28,24 @@ each into a running accumulator (`begin_aggregate()` with one reply already fold
 synchronise; the accumulators of both sides are compared first.  The new side's phases: `scan` (the host scanner's
 passes), `h2d` (staging + upload, synchronised for the timing), `devscan` (the device tokenizer and the copy of its
 two result words, where an array took that route), `fold` (add + synchronise: the kernels).
---device-scan-min-items N sets `loads_reference`'s keyword (default: the module's `wire.DEVICE_SCAN_MIN_ITEMS`).
+--device-scan-min-items N sets `loads_reference`'s keyword (default: the module's `wire.DEVICE_SCAN_MIN_ITEMS`),
+--device-scan-jl-min-items N the one of the JL leg (default: `wire.DEVICE_SCAN_JL_MIN_ITEMS`).
 
 --devscan: the LOM take leg with the device scan forced on against the device scan disabled (the host scanner's
 walk), alternating, --runs of each, at every item count 2^10 .. 2^24 (profiles/wire_devscan_ab.jsonl).  The last line
 names the smallest power of two from which on the device route's median take is the faster one: the value for
 `wire.DEVICE_SCAN_MIN_ITEMS` on that box.
 
+--devscan-jl: the same sweep for the JL take leg (`device_scan_jl_min_items` forced on against disabled) at every
+ciphertext count 2^8 .. 2^19, the updates' bytes made by `wire.dumps_reference` (profiles/wire_devscan_jl_ab.jsonl);
+the last line names the value for `wire.DEVICE_SCAN_JL_MIN_ITEMS`.
+
 --kernels: for a kernel trace (`rocprofv3 --kernel-trace --stats -- python tools/wire_ref_ab.py --kernels`): one LOM
 update's bytes uploaded once, then four launches of wire_fold_lom_kernel (continuing) and four of
 wire_decode_lom_kernel + lom_fold_kernel on the same bytes, then four reads of the message with the device scan
-forced on (wire_tok_maps_kernel, wire_tok_scan_kernel, wire_tok_emit_kernel; the printed line has the stream's bytes).
+forced on (wire_tok_maps_kernel, wire_tok_scan_kernel, wire_tok_emit_kernel; the printed line has the stream's bytes),
+then four reads of a JL update of ceil(elements / 30) ciphertexts with the JL device scan forced on
+(wire_tokj_maps_kernel, wire_tokj_scan_kernel, wire_tokj_emit_kernel; a second line).
 """
 import argparse
 import gc
@@ -114,36 +121,62 @@ def kernels(a):
     print(json.dumps({"kernels": "4 x wire_fold_lom_kernel, 4 x (wire_decode_lom_kernel + lom_fold_kernel), "
                                  "4 x (wire_tok_maps_kernel + wire_tok_scan_kernel + wire_tok_emit_kernel)", "items": h.n,
                       "tokenized_stream_bytes": len(data) - upd.handle.base}))
+    del upd, h, acc, ref, rows, data
+    packed = _jl_rows(np.random.default_rng(2027), -(-a.elements // 30))
+    data = wire.dumps_reference({"node_id": "node-00", "params": wire.EncryptedParams.from_packed("jl", packed)},
+                                default=ref_default)
+    want = D.wire_decode(data, D.wire_scan(data, 1024))[0]
+    assert np.array_equal(want, packed)
+    wire.reference_stats(reset=True)
+    for _ in range(4):
+        upd = wire.loads_reference(data, object_hook=ref_hook, resident=True, device_scan_jl_min_items=1)["params"]
+        torch.cuda.synchronize()
+    assert wire.reference_stats()["device_scan_jl"] == 4 and np.array_equal(upd.handle.rows_host(), packed)
+    print(json.dumps({"kernels": "4 x (wire_tokj_maps_kernel + wire_tokj_scan_kernel + wire_tokj_emit_kernel)",
+                      "items": upd.handle.n, "tokenized_stream_bytes": len(data) - upd.handle.base}))
     return 0
 
 
-def devscan(a):
-    """The sweep that fixes wire.DEVICE_SCAN_MIN_ITEMS (see the module's docstring)."""
+def devscan(a, jl=False):
+    """The sweep that fixes wire.DEVICE_SCAN_MIN_ITEMS, or with jl wire.DEVICE_SCAN_JL_MIN_ITEMS (see the module's
+    docstring)."""
     import torch
 
     from fedbiomed_amd import _device as D
     from fedbiomed_amd import workload as W
-    from fedbiomed_amd.secagg import SecaggLomCrypter
+    from fedbiomed_amd.secagg import SecaggCrypter, SecaggLomCrypter
 
     dev = D.device()
     wire._PHASE_TIMING = False  # nothing but the take is timed: no synchronise inside it
     rng = np.random.default_rng(2026)
     routes = (("device", 1), ("host", 2**62))
+    keyword = "device_scan_jl_min_items" if jl else "device_scan_min_items"
+    counter = "device_scan_jl" if jl else "device_scan"
+    sk0 = -sum(W.jl_user_key(p) for p in range(3))
     lines, medians = [], {}
-    for k in range(10, 25):
+    for k in (range(8, 20) if jl else range(10, 25)):
         n = 1 << k
-        words = _lom_words(rng, n)
-        first = torch.from_numpy(words.view(np.int64)).to(dev)
-        data = msgpack.packb({"node_id": "node-00", "params": words.tolist(), "n": n})
+        if jl:
+            words = _jl_rows(rng, n)
+            first = torch.from_numpy(words.view(np.int32)).to(dev)
+            data = wire.dumps_reference({"node_id": "node-00", "params": wire.EncryptedParams.from_packed("jl", words),
+                                         "n": n}, default=ref_default)
+        else:
+            words = _lom_words(rng, n)
+            first = torch.from_numpy(words.view(np.int64)).to(dev)
+            data = msgpack.packb({"node_id": "node-00", "params": words.tolist(), "n": n})
         del words
         aggs = {}
         for impl, _ in routes:
-            aggs[impl] = SecaggLomCrypter(W.LOM_NONCE).begin_aggregate(1000)
+            aggs[impl] = SecaggCrypter().begin_aggregate(3, 64, sk0, W.BIPRIME0, 1000, num_expected_params=30 * n) if jl else \
+                SecaggLomCrypter(W.LOM_NONCE).begin_aggregate(1000)
             aggs[impl].add(first)
         torch.cuda.synchronize()
 
         def take(impl, dmin):
-            upd = wire.loads_reference(data, object_hook=ref_hook, resident=True, device_scan_min_items=dmin)["params"]
+            # (jl: the sweep starts below loads_reference's default min_items, so both routes lower it)
+            upd = wire.loads_reference(data, object_hook=ref_hook, resident=True, min_items=256 if jl else 1024,
+                                       **{keyword: dmin})["params"]
             aggs[impl].add(upd)
             torch.cuda.synchronize()
             return upd
@@ -154,14 +187,14 @@ def devscan(a):
             assert type(del_me) is wire.ResidentUpdate and not del_me.materialised
             del del_me
         st = wire.reference_stats()
-        assert (st["device_scan"], st["device_scan_refused"], st["resident"]) == (1, 0, 2), st
+        assert (st[counter], st[counter + "_refused"], st["resident"]) == (1, 0, 2), st
         assert torch.equal(aggs["device"]._acc, aggs["host"]._acc), f"2^{k}: the accumulators differ"
         times = {impl: [] for impl, _ in routes}
         for run in range(a.runs):
             for impl, dmin in routes:
                 dt, out = timed(lambda: take(impl, dmin))
                 del out
-                rec = {"leg": "lom_take_sweep", "impl": impl, "items": n, "run": run, "ms": round(dt * 1e3, 3),
+                rec = {"leg": "jl_take_sweep" if jl else "lom_take_sweep", "impl": impl, "items": n, "run": run, "ms": round(dt * 1e3, 3),
                        "message_bytes": len(data),
                        "phases_ms": {p: round(v * 1e3, 3) for p, v in wire.reference_stats()["last"].items()}}
                 times[impl].append(dt * 1e3)
@@ -180,7 +213,7 @@ def devscan(a):
             chosen = n
         else:
             break
-    summary = {"summary": {str(n): medians[n] for n in sizes}, "device_scan_min_items": chosen, "runs": a.runs,
+    summary = {"summary": {str(n): medians[n] for n in sizes}, keyword: chosen, "runs": a.runs,
                "rule": "smallest 2^k such that the device route's median take is below the host route's at 2^k and above"}
     lines.append(summary)
     print(json.dumps(summary), flush=True)
@@ -201,6 +234,8 @@ def resident(a):
     dev = D.device()
     wire._PHASE_TIMING = True
     scan_kw = {} if a.device_scan_min_items is None else {"device_scan_min_items": a.device_scan_min_items}
+    if a.device_scan_jl_min_items is not None:
+        scan_kw["device_scan_jl_min_items"] = a.device_scan_jl_min_items
     rng = np.random.default_rng(2026)
     n_ct = -(-a.elements // 30)
     sk0 = -sum(W.jl_user_key(p) for p in range(3))
@@ -270,7 +305,9 @@ def resident(a):
     summary = {"summary": legs, "condition": "per leg: slowest new run < fastest reference run",
                "holds": all(v["holds"] for v in legs.values()), "elements": a.elements, "runs": a.runs,
                "resident": st["resident"], "fallback": st["fallback"], "device_scan": st.get("device_scan", 0),
-               "device_scan_refused": st.get("device_scan_refused", 0), "msgpack": ".".join(map(str, msgpack.version))}
+               "device_scan_refused": st.get("device_scan_refused", 0), "device_scan_jl": st.get("device_scan_jl", 0),
+               "device_scan_jl_refused": st.get("device_scan_jl_refused", 0), "scan_keywords": scan_kw,
+               "msgpack": ".".join(map(str, msgpack.version))}
     lines.append(summary)
     print(json.dumps(summary), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -286,15 +323,18 @@ def main():
     ap.add_argument("--resident", action="store_true")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--devscan", action="store_true")
+    ap.add_argument("--devscan-jl", action="store_true")
     ap.add_argument("--device-scan-min-items", type=int, default=None)
+    ap.add_argument("--device-scan-jl-min-items", type=int, default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "wire_devscan_ab.jsonl" if a.devscan else
+    a.out = a.out or os.path.join(ROOT, "profiles", "wire_devscan_jl_ab.jsonl" if a.devscan_jl else
+                                  "wire_devscan_ab.jsonl" if a.devscan else
                                   "wire_resident_ab.jsonl" if a.resident else "wire_reference_ab.jsonl")
     if a.kernels:
         return kernels(a)
-    if a.devscan:
-        return devscan(a)
+    if a.devscan or a.devscan_jl:
+        return devscan(a, jl=a.devscan_jl)
     if a.resident:
         return resident(a)
 
