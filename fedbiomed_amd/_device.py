@@ -2070,6 +2070,130 @@ def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[
     return arrays, handles
 
 
+def wire_scan_prefix(data, min_items: int, defer_items: int, defer_jl_items: int = 0) -> Tuple[str, Any]:
+    """fbm_wire_scan_prefix over the first bytes of a message, no device call: ("pending", (begin, first, n_items,
+    scheme)) once they hold the message's first deferral candidate, ("more", None) while they do not decide,
+    ("none", None) where they are a whole message without one and ("bad", None) where no further byte mends them."""
+    lib = N.load()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    pend = N.WirePending2()
+    rc = lib.fbm_wire_scan_prefix(_np_ptr(buf) if buf.size else None, buf.size, max(int(min_items), 1), max(int(defer_items), 0),
+                                  max(int(defer_jl_items), 0), ctypes.addressof(pend))
+    if rc == N.WIRE_PENDING:
+        return "pending", (int(pend.begin), int(pend.first), int(pend.n_items), _WIRE_NAME[pend.scheme])
+    if rc == N.WIRE_MORE:
+        return "more", None
+    if rc == N.FBM_E_UNSUPPORTED:
+        return "bad", None
+    if rc != N.FBM_OK:
+        _raise(rc)
+    return "none", None
+
+
+def wire_stream_step(begin: int, first: int, cap: int, offset: int, nbytes: int, last: bool):
+    """What a streamed message's chunk [offset, offset + nbytes) asks of the block that holds the message from `begin`
+    on, `cap` bounding the message: None where it does not fit or the message ends in front of item 0 (the stream is
+    over), else (lo, end, avail, feed) -- the chunk's bytes [lo, end) go to the block's [lo - begin, end - begin),
+    and with `feed` the tokenizer is fed avail = end - begin bytes."""
+    end = offset + nbytes
+    if end > cap:
+        return None
+    avail = end - begin
+    feed = avail > 0 and (last or avail > first - begin)
+    if last and not (feed and avail > first - begin):
+        return None
+    return max(offset, begin), end, avail, feed
+
+
+WIRE_STREAM_SLOTS = 4  # pinned staging buffers of one chunk each: a chunk's copy has three more chunks' time to finish
+
+
+class WireStream:
+    """One message's deferral candidate received chunk by chunk (fbm_wire_stream_begin / fbm_wire_stream_feed): a
+    device block for the message from the array's header (`begin`) to `cap`, the bound of the message's length; `push`
+    copies a chunk's share of it into a pinned staging buffer and from there into the block, then feeds the
+    tokenizer what has become final -- all on `ctx`'s stream, which the caller owns and keeps from message to message
+    with the staging ring (`ctx`: a dict this class fills).  Nothing synchronises the device before `result`; a
+    staging buffer is waited for only where its own copy, WIRE_STREAM_SLOTS chunks ago, has not finished."""
+
+    def __init__(self, scheme: str, begin: int, first: int, n_items: int, cap: int, ctx: dict):
+        self.scheme, self.begin, self.first, self.n, self.cap = scheme, begin, first, n_items, cap
+        self.failed, self._ctx, self._lib = False, ctx, N.load()
+        self.device = dev = device()
+        self.n_ckpt = n_items if scheme == "jl" else (n_items + N.WIRE_LOM_GROUP - 1) // N.WIRE_LOM_GROUP
+        with torch.cuda.device(dev):
+            if ctx.get("stream") is None:
+                ctx["stream"], ctx["ring"], ctx["at"] = torch.cuda.Stream(dev), [], 0
+            self.stream = ctx["stream"]
+            with torch.cuda.stream(self.stream):
+                sch = _WIRE_SCHEME[scheme]
+                self.blk = torch.empty(cap - begin, dtype=torch.uint8, device=dev)
+                self.tab = torch.empty(self.n_ckpt, dtype=torch.int64, device=dev)
+                self.state = torch.empty(N.WIRE_STREAM_STATE_WORDS, dtype=torch.int64, device=dev)
+                self.ws = torch.empty(int(self._lib.fbm_wire_stream_workspace(sch, cap - begin)), dtype=torch.uint8, device=dev)
+                _call(self._lib.fbm_wire_stream_begin, sch, first, n_items, _ptr(self.state),
+                      ctypes.c_void_p(self.stream.cuda_stream))
+
+    def _slot(self, nbytes: int) -> torch.Tensor:
+        ring, at = self._ctx["ring"], self._ctx["at"]
+        if len(ring) < WIRE_STREAM_SLOTS:
+            ring.append([host_empty(max(nbytes, 1), torch.uint8), None])
+            at = len(ring) - 1
+        slot = ring[at]
+        if slot[1] is not None:
+            slot[1].synchronize()  # (this buffer's last copy: done long ago unless chunks arrive faster than they go up)
+        if slot[0].numel() < nbytes:
+            slot[0] = host_empty(nbytes, torch.uint8)
+        self._ctx["at"] = (at + 1) % WIRE_STREAM_SLOTS
+        return slot
+
+    def push(self, chunk, offset: int, last: bool) -> bool:
+        """The message's bytes [offset, offset + len(chunk)): False (and the stream is over) where they pass `cap` or
+        the tokenizer's arguments are refused."""
+        if self.failed:
+            return False
+        step = wire_stream_step(self.begin, self.first, self.cap, offset, len(chunk), last)
+        if step is None:
+            self.failed = True
+            return False
+        lo, end, avail, feed = step
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            if end > lo:
+                n = end - lo
+                slot = self._slot(n)
+                slot[0].numpy()[:n] = np.frombuffer(chunk, dtype=np.uint8)[lo - offset:]
+                self.blk[lo - self.begin:end - self.begin].copy_(slot[0][:n], non_blocking=True)
+                slot[1] = torch.cuda.Event()
+                slot[1].record(self.stream)
+            if feed:
+                rc = self._lib.fbm_wire_stream_feed(_WIRE_SCHEME[self.scheme], _ptr(self.blk), self.begin, avail, 1 if last else 0,
+                                                    _ptr(self.tab), self.n_ckpt, _ptr(self.state), _ptr(self.ws),
+                                                    ctypes.c_void_p(self.stream.cuda_stream))
+                if rc != N.FBM_OK:
+                    self.failed = True
+                    if rc not in (N.FBM_E_ARG, N.FBM_E_UNSUPPORTED):
+                        _raise(rc)
+                    return False
+            if last:
+                self.event = torch.cuda.Event()
+                self.event.record(self.stream)
+        return True
+
+    def result(self) -> Tuple[int, int]:
+        """The tokenizer's two result words behind the last feed: the path's one synchronising copy."""
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            got, end = self.state[3:5].cpu().tolist()
+        return int(got), int(end)
+
+    def handle(self, end: int) -> WireHandle:
+        """The accepted array [begin, end) as wire_scan_resident hands its arrays out: on the block and the table."""
+        return WireHandle(self.scheme, self.n, self.begin, end - self.begin, self.n_ckpt, self.blk, 0, 0, self.event, self.tab)
+
+    def abort(self) -> None:
+        self.failed = True
+        self.blk = self.tab = self.ws = None
+
+
 def wire_rows_device(handle: WireHandle, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The packed rows of an uploaded array (fbm_wire_decode) as a device tensor, on the current stream: int32
     [n, 64] (jl) / int64 [n] (lom).  No host copy.  out: a contiguous tensor of that layout to decode into (the

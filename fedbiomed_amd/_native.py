@@ -153,7 +153,14 @@ SIGNATURES = {
     "fbm_wire_tokenize_jl": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]),
     "fbm_wire_scan_deferred2": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp,
                                         c_vp]),
+    # the tokenizers as resumable scans and the host's prefix scanner (additions to ABI 7)
+    "fbm_wire_stream_workspace": (c_u64, [c_int, c_u64]),
+    "fbm_wire_stream_begin": (c_int, [c_int, c_u64, c_u64, c_vp, c_vp]),
+    "fbm_wire_stream_feed": (c_int, [c_int, c_vp, c_u64, c_u64, c_int, c_vp, c_u64, c_vp, c_vp, c_vp]),
+    "fbm_wire_scan_prefix": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp]),
 }
+WIRE_MORE = 2  # FBM_WIRE_MORE
+WIRE_STREAM_STATE_WORDS = 16  # FBM_WIRE_STREAM_STATE_WORDS
 WIRE_JL = 0  # FBM_WIRE_JL
 WIRE_LOM = 1  # FBM_WIRE_LOM
 WIRE_LOM_GROUP = 64  # FBM_WIRE_LOM_GROUP
@@ -207,6 +214,8 @@ TEST_SIGNATURES = {
     "fbm_test_wire_fold_lom": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp, c_int]),
     "fbm_test_wire_tokenize_lom": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
     "fbm_test_wire_tokenize_jl": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
+    "fbm_test_wire_stream_begin": (c_int, [c_int, c_u64, c_u64, c_vp]),
+    "fbm_test_wire_stream_feed": (c_int, [c_int, c_vp, c_u64, c_u64, c_int, c_vp, c_u64, c_vp, c_vp]),
     "fbm_prof_enable": (c_int, [c_int]),
     "fbm_prof_report": (c_int, [ctypes.c_char_p, c_int]),
 }

@@ -1635,6 +1635,159 @@ int fbm_wire_scan_deferred2(const uint8_t* data, uint64_t len, uint64_t min_item
   return FBM_OK;
 }
 
+int fbm_wire_scan_prefix(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
+                         uint64_t defer_items_jl, fbm_wire_pending2* pending) {
+  if ((len > 0 && !data) || !pending) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  const int r = fbm_wire_scan_prefix_run(data, len, min_items, defer_items_lom, defer_items_jl, pending);
+  if (r == FBM_WIRE_SCAN_PENDING) return FBM_WIRE_PENDING;
+  if (r == FBM_WIRE_SCAN_MORE) return FBM_WIRE_MORE;
+  if (r == FBM_WIRE_SCAN_GAVE_UP) {
+    set_error("fbm_wire_scan: not one well-formed msgpack object within the nesting bound");
+    return FBM_E_UNSUPPORTED;
+  }
+  return FBM_OK;
+}
+
+}  // extern "C"
+
+// The host's records of the streams fbm_wire_stream_begin opened on device states, under the state's address: a feed
+// plans its launches from its record (the device's copy is not read back).  A begin on a state that has a record takes
+// it over, the last feed frees it; with FBM_WIRE_STREAMS_OPEN unfinished streams open, a further begin takes the slot of
+// the one begun longest ago (every record carries its begin's serial number) -- a stream that was begun and never fed
+// to its end goes that way -- and a feed whose record is gone is FBM_E_ARG.
+#define FBM_WIRE_STREAMS_OPEN 64
+namespace {
+struct wire_stream_rec {
+  uint64_t* state;
+  uint64_t begun;  // the serial number of its begin
+  uint64_t rec[FBM_WIRE_STREAM_STATE_WORDS];
+};
+std::mutex g_wire_streams_mu;
+wire_stream_rec g_wire_streams[FBM_WIRE_STREAMS_OPEN];
+uint64_t g_wire_streams_begun = 0;
+
+wire_stream_rec* wire_stream_find(uint64_t* state) {  // (the mutex held)
+  for (auto& r : g_wire_streams)
+    if (r.state == state) return &r;
+  return nullptr;
+}
+}  // namespace
+
+// the argument checks fbm_wire_stream_begin / _feed and their host hooks share
+static int wire_stream_begin_checks(int scheme, uint64_t n_items, const uint64_t* state) {
+  if (scheme != FBM_WIRE_JL && scheme != FBM_WIRE_LOM) {
+    set_error("fbm_wire_stream_begin: scheme=%d must be FBM_WIRE_JL or FBM_WIRE_LOM", scheme);
+    return FBM_E_ARG;
+  }
+  if (!state || reinterpret_cast<uintptr_t>(state) % 8) {
+    set_error("fbm_wire_stream_begin: null or misaligned state");
+    return FBM_E_ARG;
+  }
+  if (n_items == 0) {
+    set_error("fbm_wire_stream_begin: an array without items has nothing to stream");
+    return FBM_E_ARG;
+  }
+  if (n_items > 0xffffffffull) {
+    set_error("fbm_wire_stream_begin: %llu items exceed a msgpack array", (unsigned long long)n_items);
+    return FBM_E_UNSUPPORTED;
+  }
+  return FBM_OK;
+}
+
+static int wire_stream_feed_checks(int scheme, const uint8_t* span, uint64_t avail_len, const uint64_t* ckpt, uint64_t n_ckpt,
+                                   const uint64_t* state, const void* workspace, const uint64_t* rec) {
+  if (scheme != FBM_WIRE_JL && scheme != FBM_WIRE_LOM) {
+    set_error("fbm_wire_stream_feed: scheme=%d must be FBM_WIRE_JL or FBM_WIRE_LOM", scheme);
+    return FBM_E_ARG;
+  }
+  if (!span || !ckpt || !state || !workspace) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(ckpt) % 8) || (reinterpret_cast<uintptr_t>(state) % 8) || (reinterpret_cast<uintptr_t>(workspace) % 8)) {
+    set_error("fbm_wire_stream_feed: ckpt / state / workspace not aligned to 8 bytes");
+    return FBM_E_ARG;
+  }
+  if (!rec) {
+    set_error("fbm_wire_stream_feed: no stream begun on this state");
+    return FBM_E_ARG;
+  }
+  if (rec[FBM_WIRE_SEG_SCHEME] == (uint64_t)scheme + 1) {  // (any other: wire_seg_plan_of's refusal)
+    const uint64_t n = rec[FBM_WIRE_SEG_ITEMS], group = scheme == FBM_WIRE_JL ? 1 : FBM_WIRE_LOM_GROUP;
+    if (n_ckpt != (n + group - 1) / group) {
+      set_error("fbm_wire_stream_feed: %llu checkpoints for %llu items (one per %llu items)", (unsigned long long)n_ckpt,
+                (unsigned long long)n, (unsigned long long)group);
+      return FBM_E_ARG;
+    }
+  }
+  if (avail_len > (1ull << 62) || !wire_tokenize_fits(avail_len)) {
+    set_error("fbm_wire_stream_feed: a span of %llu bytes exceeds one launch's grid", (unsigned long long)avail_len);
+    return FBM_E_UNSUPPORTED;
+  }
+  return FBM_OK;
+}
+
+extern "C" {
+
+uint64_t fbm_wire_stream_workspace(int scheme, uint64_t cap_len) {
+  return scheme == FBM_WIRE_JL ? wire_tokenize_jl_workspace(cap_len) : wire_tokenize_workspace(cap_len);
+}
+
+int fbm_wire_stream_begin(int scheme, uint64_t first, uint64_t n_items, uint64_t* state, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc = wire_stream_begin_checks(scheme, n_items, state);
+  if (rc) return rc;
+  rc = timed("wire_stream_begin", s, [&] { return launch_wire_stream_begin(scheme, first, n_items, state, s); });
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(g_wire_streams_mu);
+  wire_stream_rec* r = wire_stream_find(state);
+  if (!r) r = wire_stream_find(nullptr);  // a free one
+  if (!r) {  // the one begun longest ago
+    r = &g_wire_streams[0];
+    for (auto& q : g_wire_streams)
+      if (q.begun < r->begun) r = &q;
+  }
+  r->state = state, r->begun = ++g_wire_streams_begun;
+  wire_seg_begin(scheme, first, n_items, r->rec);
+  return FBM_OK;
+}
+
+int fbm_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last, uint64_t* ckpt,
+                         uint64_t n_ckpt, uint64_t* state, void* workspace, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  uint64_t rec[FBM_WIRE_STREAM_STATE_WORDS];
+  bool have = false;
+  {
+    std::lock_guard<std::mutex> lock(g_wire_streams_mu);
+    if (wire_stream_rec* r = state ? wire_stream_find(state) : nullptr) memcpy(rec, r->rec, sizeof rec), have = true;
+  }
+  int rc = wire_stream_feed_checks(scheme, span, avail_len, ckpt, n_ckpt, state, workspace, have ? rec : nullptr);
+  if (rc) return rc;
+  wire_seg_plan p;
+  if (const char* err = wire_seg_plan_of(rec, scheme, span, span_base, avail_len, last, &p)) {
+    set_error("fbm_wire_stream_feed: %s", err);
+    return FBM_E_ARG;
+  }
+  if (p.hi > p.lo) {
+    rc = timed("wire_stream_feed", s, [&] {
+      return launch_wire_stream_feed(scheme, span, span_base, avail_len, last, ckpt, n_ckpt, state, workspace, rec, p, s);
+    });
+    if (rc) return rc;
+  }
+  wire_seg_fed(rec, p, span, span_base, avail_len, last);
+  std::lock_guard<std::mutex> lock(g_wire_streams_mu);
+  if (wire_stream_rec* r = wire_stream_find(state)) {
+    if (last)
+      r->state = nullptr;  // the stream is over: a further feed finds no record
+    else
+      memcpy(r->rec, rec, sizeof rec);
+  }
+  return FBM_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------
@@ -1680,6 +1833,23 @@ int fbm_test_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t 
   int rc = wire_tokenize_checks(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace);
   if (rc == FBM_OK) host_wire_tokenize_lom(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace);
   return rc;
+}
+
+int fbm_test_wire_stream_begin(int scheme, uint64_t first, uint64_t n_items, uint64_t* state) {
+  int rc = wire_stream_begin_checks(scheme, n_items, state);
+  if (rc == FBM_OK) wire_seg_begin(scheme, first, n_items, state);
+  return rc;
+}
+
+int fbm_test_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last,
+                              uint64_t* ckpt, uint64_t n_ckpt, uint64_t* state, void* workspace) {
+  int rc = wire_stream_feed_checks(scheme, span, avail_len, ckpt, n_ckpt, state, workspace, state);
+  if (rc) return rc;
+  if (const char* err = wire_seg_host_feed(scheme, span, span_base, avail_len, last, ckpt, n_ckpt, state, workspace)) {
+    set_error("fbm_wire_stream_feed: %s", err);
+    return FBM_E_ARG;
+  }
+  return FBM_OK;
 }
 
 int fbm_jl_window(void) { return FBM_WIN; }

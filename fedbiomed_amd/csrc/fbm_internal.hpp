@@ -374,6 +374,13 @@ int launch_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t ba
                              uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s);
 void host_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
                             uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
+// fbm_wire_stream_begin / fbm_wire_stream_feed: the record's reset and one feed's launches over the tiles of its plan
+// (fbm_wire.hpp: wire_seg_plan_of over the host's record `rec`)
+struct wire_seg_plan;
+int launch_wire_stream_begin(int scheme, uint64_t first, uint64_t n, uint64_t* state, hipStream_t s);
+int launch_wire_stream_feed(int scheme, const uint8_t* span, uint64_t base, uint64_t avail, int last, uint64_t* ckpt,
+                            uint64_t n_ckpt, uint64_t* state, void* workspace, const uint64_t* rec, const wire_seg_plan& p,
+                            hipStream_t s);
 
 // table slots the encrypt/aggregate kernels need for a given grid
 uint64_t jl_table_slots();

@@ -339,10 +339,12 @@ __global__ void __launch_bounds__(FBM_WIRE_BLOCK, 4) wire_tok_maps_kernel(const 
   maps[tile * FBM_WIRE_TOK_MAP + lane] = (uint32_t)st;  // <= 4096 items << 4
 }
 
-__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tok_scan_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
-                                                                              uint32_t head, uint64_t n,
-                                                                              uint64_t* __restrict__ entry,
-                                                                              uint64_t* __restrict__ result) {
+// The scan of `tiles` maps by one workgroup: in() is the state in front of the first tile (thread 0 asks), out(st) takes
+// the state behind the last (thread 0); every tile's entry state -> entry[].  wire_tok_scan_kernel and the resumable
+// wire_seg_scan_lom_kernel differ in those two alone.
+template <class In, class Out>
+__device__ __forceinline__ void wire_tok_scan_body(const uint32_t* __restrict__ maps, uint64_t tiles, uint64_t* __restrict__ entry,
+                                                   In in, Out out) {
   __shared__ uint64_t comp[FBM_WIRE_SCAN_THREADS][FBM_WIRE_TOK_MAP];
   __shared__ uint64_t ent[FBM_WIRE_SCAN_THREADS];
   const int t = threadIdx.x;
@@ -360,13 +362,12 @@ __global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tok_scan_kernel(co
   comp[t][9] = FBM_WIRE_TOK_BAD;
   __syncthreads();
   if (t == 0) {
-    uint64_t st = head;
+    uint64_t st = in();
     for (int u = 0; u < FBM_WIRE_SCAN_THREADS; ++u) {
       ent[u] = st;
       st = wire_tok_step(st, comp[u]);
     }
-    result[0] = wire_tok_whole_items(st, n);
-    result[1] = 0;  // wire_tok_emit_kernel writes the end where item n - 1 lies wholly inside the span
+    out(st);
   }
   __syncthreads();
   uint64_t st = ent[t];
@@ -374,6 +375,16 @@ __global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tok_scan_kernel(co
     entry[b] = st;
     st = wire_tok_step(st, maps + b * FBM_WIRE_TOK_MAP);
   }
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tok_scan_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
+                                                                              uint32_t head, uint64_t n,
+                                                                              uint64_t* __restrict__ entry,
+                                                                              uint64_t* __restrict__ result) {
+  wire_tok_scan_body(maps, tiles, entry, [&] { return (uint64_t)head; }, [&](uint64_t st) {
+    result[0] = wire_tok_whole_items(st, n);
+    result[1] = 0;  // wire_tok_emit_kernel writes the end where item n - 1 lies wholly inside the span
+  });
 }
 
 __global__ void __launch_bounds__(FBM_WIRE_BLOCK, 4) wire_tok_emit_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
@@ -472,10 +483,10 @@ __global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_tokj_maps_kernel(const ui
   if (lane < FBM_WIRE_TOKJ_SLOTS && (uint32_t)lane >= used) maps[tile * FBM_WIRE_TOKJ_SLOTS + lane] = ~0u;
 }
 
-__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tokj_scan_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
-                                                                               uint32_t head, uint64_t n,
-                                                                               uint64_t* __restrict__ entry,
-                                                                               uint64_t* __restrict__ result) {
+// (wire_tokj_scan_body: in() and out(st) as wire_tok_scan_body's; wire_tokj_scan_kernel and wire_seg_scan_jl_kernel)
+template <class In, class Out>
+__device__ __forceinline__ void wire_tokj_scan_body(const uint32_t* __restrict__ maps, uint64_t tiles, uint64_t* __restrict__ entry,
+                                                    In in, Out out) {
   __shared__ uint64_t comp[FBM_WIRE_TOKJ_SLOTS][FBM_WIRE_SCAN_THREADS];  // [slot][thread]: consecutive threads, consecutive banks
   __shared__ uint64_t ent[FBM_WIRE_SCAN_THREADS];
   const int t = threadIdx.x;
@@ -495,15 +506,14 @@ __global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tokj_scan_kernel(c
   }
   __syncthreads();
   if (t == 0) {
-    uint64_t st = head;
+    uint64_t st = in();
     for (int u = 0; u < FBM_WIRE_SCAN_THREADS; ++u) {
       ent[u] = st;
       uint64_t c0, c1;
       wire_tok_run(tiles, u, &c0, &c1);
       if (c0 < c1) st = wire_tokj_apply_run(st, maps + c0 * FBM_WIRE_TOKJ_SLOTS, &comp[0][u], FBM_WIRE_SCAN_THREADS);
     }
-    result[0] = (st >> 16) < n ? (st >> 16) : n;
-    result[1] = 0;  // wire_tokj_emit_kernel writes the end where item n - 1 is one of the chain's
+    out(st);
   }
   __syncthreads();
   uint64_t st = ent[t];
@@ -511,6 +521,16 @@ __global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tokj_scan_kernel(c
     entry[b] = st;
     st = wire_tokj_apply(st, maps + b * FBM_WIRE_TOKJ_SLOTS);
   }
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_tokj_scan_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
+                                                                               uint32_t head, uint64_t n,
+                                                                               uint64_t* __restrict__ entry,
+                                                                               uint64_t* __restrict__ result) {
+  wire_tokj_scan_body(maps, tiles, entry, [&] { return (uint64_t)head; }, [&](uint64_t st) {
+    result[0] = (st >> 16) < n ? (st >> 16) : n;
+    result[1] = 0;  // wire_tokj_emit_kernel writes the end where item n - 1 is one of the chain's
+  });
 }
 
 __global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_tokj_emit_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
@@ -538,6 +558,48 @@ __global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_tokj_emit_kernel(const ui
   for (uint32_t j = lane; j < cnt; j += 64)
     if (k0 + j < n_ckpt) ckpt[k0 + j] = sh_out[wave][j];
   if (lane == 0 && end >= 0) result[1] = (uint64_t)((int64_t)base + tbase + end);
+}
+
+// ---- the tokenizers as resumable scans (fbm_wire_stream_feed) --------------------------------------------------
+// fbm_wire.hpp has the stream's record and which tiles a feed runs.  A feed is the one-shot call's three launches over
+// its tiles [lo, hi): the maps and emit kernels above, given tile lo's span offset as their origin, and between them a
+// scan whose entry state is not the stream's `head` but the carry the last feed left in the record:
+//   wire_seg_scan_lom_kernel / wire_seg_scan_jl_kernel   wire_tok_scan_kernel's / wire_tokj_scan_kernel's body with thread 0
+//       reading its entry state from state[CARRY] (fresh: the stream's first tiles, `head`) and writing the state behind
+//       the segment back there, result[0] beside it -- and leaving result[1] alone: wire_seg_begin_kernel zeroed it and
+//       the one emit launch whose tiles hold item n - 1's start writes it
+// LDS: the one-shot scans' (LOM 22528 bytes, JL 34816 bytes).  Bound: their runs' dependent loads, as the one-shot's.
+__global__ void wire_seg_begin_kernel(uint64_t* __restrict__ state, uint64_t first, uint64_t n, uint64_t scheme) {
+  const int t = threadIdx.x;
+  if (t >= FBM_WIRE_STREAM_STATE_WORDS) return;
+  state[t] = t == FBM_WIRE_SEG_FIRST ? first : t == FBM_WIRE_SEG_ITEMS ? n : t == FBM_WIRE_SEG_SCHEME ? scheme + 1 : 0ull;
+}
+
+// thread 0's bookkeeping behind a segment's scan
+__device__ __forceinline__ void wire_seg_note(uint64_t* __restrict__ state, uint64_t st, uint64_t count, uint64_t fed,
+                                              uint64_t tiles_done, int last) {
+  state[FBM_WIRE_SEG_CARRY] = st;
+  state[FBM_WIRE_SEG_RESULT] = count;
+  state[FBM_WIRE_SEG_FED] = fed, state[FBM_WIRE_SEG_TILES] = tiles_done;
+  if (last) state[FBM_WIRE_SEG_SCHEME] |= FBM_WIRE_SEG_DONE;
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_seg_scan_lom_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
+                                                                                  uint32_t head, int fresh, uint64_t n,
+                                                                                  uint64_t* __restrict__ entry,
+                                                                                  uint64_t* __restrict__ state, uint64_t fed,
+                                                                                  uint64_t tiles_done, int last) {
+  wire_tok_scan_body(maps, tiles, entry, [&] { return fresh ? (uint64_t)head : state[FBM_WIRE_SEG_CARRY]; },
+                     [&](uint64_t st) { wire_seg_note(state, st, wire_tok_whole_items(st, n), fed, tiles_done, last); });
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_seg_scan_jl_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
+                                                                                 uint32_t head, int fresh, uint64_t n,
+                                                                                 uint64_t* __restrict__ entry,
+                                                                                 uint64_t* __restrict__ state, uint64_t fed,
+                                                                                 uint64_t tiles_done, int last) {
+  wire_tokj_scan_body(maps, tiles, entry, [&] { return fresh ? (uint64_t)head : state[FBM_WIRE_SEG_CARRY]; },
+                      [&](uint64_t st) { wire_seg_note(state, st, (st >> 16) < n ? (st >> 16) : n, fed, tiles_done, last); });
 }
 
 static int wire_grid(uint64_t blocks, const char* what, unsigned& g) {
@@ -662,6 +724,43 @@ int launch_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t bas
   hipLaunchKernelGGL(wire_tokj_emit_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, c.origin, c.tiles, entry, base,
                      n, ckpt, n_ckpt, result);
   return check_launch("wire_tokj_emit_kernel");
+}
+
+int launch_wire_stream_begin(int scheme, uint64_t first, uint64_t n, uint64_t* state, hipStream_t s) {
+  hipLaunchKernelGGL(wire_seg_begin_kernel, dim3(1), dim3(64), 0, s, state, first, n, (uint64_t)scheme);
+  return check_launch("wire_seg_begin_kernel");
+}
+
+// one feed's launches: `rec` is the host's record of the stream, `p` its plan (wire_seg_plan_of) with p.hi > p.lo
+int launch_wire_stream_feed(int scheme, const uint8_t* span, uint64_t base, uint64_t avail, int last, uint64_t* ckpt,
+                            uint64_t n_ckpt, uint64_t* state, void* workspace, const uint64_t* rec, const wire_seg_plan& p,
+                            hipStream_t s) {
+  const uint64_t tiles = p.hi - p.lo, n = rec[FBM_WIRE_SEG_ITEMS];
+  unsigned g = 0;
+  int rc = wire_grid((tiles + FBM_WIRE_TOK_WAVES - 1) / FBM_WIRE_TOK_WAVES, "fbm_wire_stream_feed", g);
+  if (rc) return rc;
+  uint64_t* entry = reinterpret_cast<uint64_t*>(workspace);
+  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(tiles));
+  uint64_t* result = state + FBM_WIRE_SEG_RESULT;
+  const int fresh = p.lo == 0;
+  if (scheme == FBM_WIRE_JL) {
+    hipLaunchKernelGGL(wire_tokj_maps_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, avail, p.origin, tiles, maps);
+    if ((rc = check_launch("wire_tokj_maps_kernel"))) return rc;
+    hipLaunchKernelGGL(wire_seg_scan_jl_kernel, dim3(1), dim3(FBM_WIRE_SCAN_THREADS), 0, s, maps, tiles, p.head, fresh, n, entry,
+                       state, avail, p.hi, last);
+    if ((rc = check_launch("wire_seg_scan_jl_kernel"))) return rc;
+    hipLaunchKernelGGL(wire_tokj_emit_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, avail, p.origin, tiles, entry, base, n,
+                       ckpt, n_ckpt, result);
+    return check_launch("wire_tokj_emit_kernel");
+  }
+  hipLaunchKernelGGL(wire_tok_maps_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, avail, p.origin, tiles, maps);
+  if ((rc = check_launch("wire_tok_maps_kernel"))) return rc;
+  hipLaunchKernelGGL(wire_seg_scan_lom_kernel, dim3(1), dim3(FBM_WIRE_SCAN_THREADS), 0, s, maps, tiles, p.head, fresh, n, entry,
+                     state, avail, p.hi, last);
+  if ((rc = check_launch("wire_seg_scan_lom_kernel"))) return rc;
+  hipLaunchKernelGGL(wire_tok_emit_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, avail, p.origin, tiles, entry, base, n, ckpt,
+                     n_ckpt, result);
+  return check_launch("wire_tok_emit_kernel");
 }
 
 // ---- the same per-item routines on the host (the test build's hooks) ------------------------------

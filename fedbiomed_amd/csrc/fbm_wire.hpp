@@ -274,16 +274,19 @@ inline void wire_tok_host_sub(const uint8_t* span, uint64_t span_len, int64_t su
   map[9] = (uint16_t)FBM_WIRE_TOK_BAD;
 }
 
-inline void wire_tokenize_host(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
-                            uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
-  const wire_tok_cut c = wire_tok_cut_of(span, span_len, first - base);
+// The three passes over the `tiles` tiles that begin at span offset `origin`, entered in the running state `carry`
+// (the whole stream: wire_tok_cut_of's origin, tiles and head); returns the state behind them.  result[0] is written,
+// result[1] only where item n - 1 ends in these tiles: the caller zeroes it first.
+inline uint64_t wire_seg_host_lom(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t n, int64_t origin,
+                                  uint64_t tiles, uint64_t carry, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result,
+                                  void* workspace) {
   uint64_t* entry = reinterpret_cast<uint64_t*>(workspace);
-  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(c.tiles));
+  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(tiles));
   uint32_t w[16];
   uint16_t map[FBM_WIRE_TOK_SUBS][FBM_WIRE_TOK_MAP];
   int valid = 0;
-  for (uint64_t tile = 0; tile < c.tiles; ++tile) {  // wire_tok_maps_kernel
-    const int64_t tbase = c.origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+  for (uint64_t tile = 0; tile < tiles; ++tile) {  // wire_tok_maps_kernel
+    const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
     for (int j = 0; j < FBM_WIRE_TOK_SUBS; ++j) wire_tok_host_sub(span, span_len, tbase + FBM_WIRE_TOK_SUB * j, w, &valid, map[j]);
     for (int p = 0; p < FBM_WIRE_TOK_MAP; ++p) {
       uint64_t st = (uint64_t)p;
@@ -291,10 +294,10 @@ inline void wire_tokenize_host(const uint8_t* span, uint64_t span_len, uint64_t 
       maps[tile * FBM_WIRE_TOK_MAP + p] = (uint32_t)st;
     }
   }
-  uint64_t st = c.head;  // wire_tok_scan_kernel
+  uint64_t st = carry;  // wire_tok_scan_kernel
   for (int t = 0; t < FBM_WIRE_TOK_SCAN_THREADS; ++t) {
     uint64_t b0, b1, comp[FBM_WIRE_TOK_MAP];
-    wire_tok_run(c.tiles, t, &b0, &b1);
+    wire_tok_run(tiles, t, &b0, &b1);
     for (int p = 0; p < FBM_WIRE_TOK_MAP; ++p) {
       comp[p] = (uint64_t)p;
       for (uint64_t b = b0; b < b1; ++b) comp[p] = wire_tok_step(comp[p], maps + b * FBM_WIRE_TOK_MAP);
@@ -307,9 +310,8 @@ inline void wire_tokenize_host(const uint8_t* span, uint64_t span_len, uint64_t 
     st = wire_tok_step(st, comp);  // (= in: the run's composite and its tiles one by one agree)
   }
   result[0] = wire_tok_whole_items(st, n);
-  result[1] = 0;
-  for (uint64_t tile = 0; tile < c.tiles; ++tile) {  // wire_tok_emit_kernel
-    const int64_t tbase = c.origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+  for (uint64_t tile = 0; tile < tiles; ++tile) {  // wire_tok_emit_kernel
+    const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
     uint64_t in = entry[tile];
     for (int j = 0; j < FBM_WIRE_TOK_SUBS; ++j) {
       const int64_t sub = tbase + FBM_WIRE_TOK_SUB * j;
@@ -326,6 +328,14 @@ inline void wire_tokenize_host(const uint8_t* span, uint64_t span_len, uint64_t 
       if (end >= 0 && (uint64_t)(sub + end) <= span_len) result[1] = base + (uint64_t)(sub + end);
     }
   }
+  return st;
+}
+
+inline void wire_tokenize_host(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                               uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  const wire_tok_cut c = wire_tok_cut_of(span, span_len, first - base);
+  result[1] = 0;
+  wire_seg_host_lom(span, span_len, base, n, c.origin, c.tiles, c.head, ckpt, n_ckpt, result, workspace);
 }
 
 // ---- tokenize (JL): where the values of an array of big-int maps start ------------------------------
@@ -465,21 +475,23 @@ inline void wire_tokj_host_map(const uint32_t* w, int64_t left, uint32_t* map) {
 // fbm_wire_tokenize_jl's three kernels (fbm_wire.hip) over host buffers, tile by tile and run by run as the kernels
 // cut them, through the same routines (host_wire_tokenize_jl; tools/wire_tokenize_jl_check.cpp runs it under the host
 // sanitizers).  Reads span[0, span_len) and no more; writes ckpt[0, n_ckpt), result[0, 2) and the workspace.
-inline void wire_tokenize_jl_host(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
-                                  uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
-  const wire_tok_cut c = wire_tok_cut_of(span, span_len, first - base);
+// (wire_seg_host_jl: the passes over the `tiles` tiles from span offset `origin` on, entered in the state `carry`, as
+// wire_seg_host_lom)
+inline uint64_t wire_seg_host_jl(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t n, int64_t origin,
+                                 uint64_t tiles, uint64_t carry, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result,
+                                 void* workspace) {
   uint64_t* entry = reinterpret_cast<uint64_t*>(workspace);
-  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(c.tiles));
+  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(tiles));
   uint32_t w[FBM_WIRE_TOKJ_WORDS];
-  for (uint64_t tile = 0; tile < c.tiles; ++tile) {  // wire_tokj_maps_kernel
-    const int64_t tbase = c.origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+  for (uint64_t tile = 0; tile < tiles; ++tile) {  // wire_tokj_maps_kernel
+    const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
     wire_tokj_host_stage(span, span_len, tbase, w);
     wire_tokj_host_map(w, (int64_t)span_len - tbase, maps + tile * FBM_WIRE_TOKJ_SLOTS);
   }
-  uint64_t st = c.head;  // wire_tokj_scan_kernel
+  uint64_t st = carry;  // wire_tokj_scan_kernel
   for (int t = 0; t < FBM_WIRE_TOK_SCAN_THREADS; ++t) {
     uint64_t b0, b1, comp[FBM_WIRE_TOKJ_SLOTS];
-    wire_tok_run(c.tiles, t, &b0, &b1);
+    wire_tok_run(tiles, t, &b0, &b1);
     if (b0 == b1) continue;
     for (int k = 0; k < FBM_WIRE_TOKJ_SLOTS; ++k) {
       const uint32_t m = maps[b0 * FBM_WIRE_TOKJ_SLOTS + k];
@@ -495,10 +507,9 @@ inline void wire_tokenize_jl_host(const uint8_t* span, uint64_t span_len, uint64
     st = wire_tokj_apply_run(st, maps + b0 * FBM_WIRE_TOKJ_SLOTS, comp, 1);  // (= in)
   }
   result[0] = (st >> 16) < n ? (st >> 16) : n;
-  result[1] = 0;
   uint64_t out[FBM_WIRE_TOKJ_ITEMS];
-  for (uint64_t tile = 0; tile < c.tiles; ++tile) {  // wire_tokj_emit_kernel
-    const int64_t tbase = c.origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+  for (uint64_t tile = 0; tile < tiles; ++tile) {  // wire_tokj_emit_kernel
+    const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
     wire_tokj_host_stage(span, span_len, tbase, w);
     int end = -1;
     const uint32_t cnt = wire_tokj_emit_walk(w, entry[tile], (int64_t)span_len - tbase, (int64_t)base + tbase, n, out, &end);
@@ -506,6 +517,98 @@ inline void wire_tokenize_jl_host(const uint8_t* span, uint64_t span_len, uint64
       if ((entry[tile] >> 16) + j < n_ckpt) ckpt[(entry[tile] >> 16) + j] = out[j];
     if (end >= 0) result[1] = (uint64_t)((int64_t)base + tbase + end);
   }
+  return st;
+}
+
+inline void wire_tokenize_jl_host(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                                  uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  const wire_tok_cut c = wire_tok_cut_of(span, span_len, first - base);
+  result[1] = 0;
+  wire_seg_host_jl(span, span_len, base, n, c.origin, c.tiles, c.head, ckpt, n_ckpt, result, workspace);
+}
+
+// ---- the tokenizers as resumable scans (fbm_wire_stream_begin / fbm_wire_stream_feed) ---------------------------
+// Both tokenizers are a scan over tiles, and a tile's place depends on the span's address, its base and `first` alone,
+// not on the span's length: a span that grows keeps its tiles.  A feed runs the three passes over the tiles that have
+// become final since the last one, the scan entered in the running state the last feed left in the stream's record and
+// leaving its own there.  A tile is final once every item that starts in it lies wholly below avail_len -- the tile's
+// end plus the longest item's reach, FBM_WIRE_NATIVE_MAX - 1 or FBM_WIRE_ITEM_MAX bytes --: then its map, its items'
+// table words and whether item n - 1 ends inside the span are what the whole span's one call finds.  The last feed
+// takes every tile left, the partial one included, under the span's final length.  The passes write a segment's entry
+// states and maps at the front of the workspace, each feed over the last one's (the stream orders them).
+//
+// The record, FBM_WIRE_STREAM_STATE_WORDS u64 words.  The device's copy holds what the kernels read and write (carry,
+// the two result words; FED and TILES as of the last feed that ran a tile); the library keeps the host's copy of a
+// device stream, which plans the launches, beside it (fbm_capi.hip), and the host run uses its record for both.
+#define FBM_WIRE_SEG_FED 0     // bytes fed: the largest avail_len so far
+#define FBM_WIRE_SEG_TILES 1   // tiles done
+#define FBM_WIRE_SEG_CARRY 2   // the running state behind them (LOM: items << 4 | phase; JL: items << 16 | offset)
+#define FBM_WIRE_SEG_RESULT 3  // the one-shot calls' result[0], result[1]
+#define FBM_WIRE_SEG_FIRST 5
+#define FBM_WIRE_SEG_ITEMS 6
+#define FBM_WIRE_SEG_SCHEME 7  // scheme + 1; | FBM_WIRE_SEG_DONE behind the last feed; 0: no stream begun
+#define FBM_WIRE_SEG_SPAN 8    // the first feed's span address (0: none yet) and base: every feed's
+#define FBM_WIRE_SEG_BASE 9
+#define FBM_WIRE_SEG_DONE 0x100ull
+static_assert(FBM_WIRE_STREAM_STATE_WORDS >= 10, "the record's words");
+
+inline void wire_seg_begin(int scheme, uint64_t first, uint64_t n, uint64_t* rec) {
+  for (int k = 0; k < FBM_WIRE_STREAM_STATE_WORDS; ++k) rec[k] = 0;
+  rec[FBM_WIRE_SEG_FIRST] = first, rec[FBM_WIRE_SEG_ITEMS] = n, rec[FBM_WIRE_SEG_SCHEME] = (uint64_t)scheme + 1;
+}
+
+struct wire_seg_plan {
+  int64_t origin;   // the span offset of tile `lo`
+  uint64_t lo, hi;  // the tiles this feed runs: [lo, hi)
+  uint32_t head;    // the stream's entry state (tile 0's)
+};
+// What a feed of avail_len bytes runs, from the host's record; a message where the arguments do not continue the
+// record's stream (FBM_E_ARG), else nullptr.
+inline const char* wire_seg_plan_of(const uint64_t* rec, int scheme, const uint8_t* span, uint64_t base, uint64_t avail,
+                                    int last, wire_seg_plan* p) {
+  if (rec[FBM_WIRE_SEG_SCHEME] != (uint64_t)scheme + 1)
+    return rec[FBM_WIRE_SEG_SCHEME] & FBM_WIRE_SEG_DONE ? "the stream has had its last feed" : "no stream of this scheme begun on this state";
+  if (rec[FBM_WIRE_SEG_SPAN] && (rec[FBM_WIRE_SEG_SPAN] != (uint64_t)reinterpret_cast<uintptr_t>(span) || rec[FBM_WIRE_SEG_BASE] != base))
+    return "span / span_base differ from the stream's first feed";
+  if (avail < rec[FBM_WIRE_SEG_FED]) return "avail_len below what was already fed";
+  const uint64_t first = rec[FBM_WIRE_SEG_FIRST];
+  if (first < base || (last && first - base >= avail)) return "first outside the span";
+  const wire_tok_cut c = wire_tok_cut_of(span, avail, first - base);
+  p->head = c.head, p->lo = rec[FBM_WIRE_SEG_TILES];
+  if (last) {
+    p->hi = c.tiles;
+  } else {
+    const int64_t reach = scheme == FBM_WIRE_JL ? FBM_WIRE_ITEM_MAX : FBM_WIRE_NATIVE_MAX - 1;
+    const int64_t room = (int64_t)avail - reach - c.origin;
+    p->hi = room > 0 ? (uint64_t)room / FBM_WIRE_TOK_TILE : 0;
+  }
+  if (p->hi < p->lo) p->hi = p->lo;  // (never: avail_len only grows)
+  p->origin = c.origin + (int64_t)(p->lo * FBM_WIRE_TOK_TILE);
+  return nullptr;
+}
+// the record behind a planned feed
+inline void wire_seg_fed(uint64_t* rec, const wire_seg_plan& p, const uint8_t* span, uint64_t base, uint64_t avail, int last) {
+  rec[FBM_WIRE_SEG_FED] = avail, rec[FBM_WIRE_SEG_TILES] = p.hi;
+  rec[FBM_WIRE_SEG_SPAN] = (uint64_t)reinterpret_cast<uintptr_t>(span), rec[FBM_WIRE_SEG_BASE] = base;
+  if (last) rec[FBM_WIRE_SEG_SCHEME] |= FBM_WIRE_SEG_DONE;
+}
+
+// fbm_wire_stream_feed over host buffers (the record is the state): the kernels' passes through the same routines
+inline const char* wire_seg_host_feed(int scheme, const uint8_t* span, uint64_t base, uint64_t avail, int last, uint64_t* ckpt,
+                                      uint64_t n_ckpt, uint64_t* state, void* workspace) {
+  wire_seg_plan p;
+  const char* err = wire_seg_plan_of(state, scheme, span, base, avail, last, &p);
+  if (err) return err;
+  if (p.hi > p.lo) {
+    const uint64_t carry = p.lo == 0 ? (uint64_t)p.head : state[FBM_WIRE_SEG_CARRY];
+    const uint64_t n = state[FBM_WIRE_SEG_ITEMS];
+    state[FBM_WIRE_SEG_CARRY] =
+        scheme == FBM_WIRE_JL
+            ? wire_seg_host_jl(span, avail, base, n, p.origin, p.hi - p.lo, carry, ckpt, n_ckpt, state + FBM_WIRE_SEG_RESULT, workspace)
+            : wire_seg_host_lom(span, avail, base, n, p.origin, p.hi - p.lo, carry, ckpt, n_ckpt, state + FBM_WIRE_SEG_RESULT, workspace);
+  }
+  wire_seg_fed(state, p, span, base, avail, last);
+  return nullptr;
 }
 
 }  // namespace fbm

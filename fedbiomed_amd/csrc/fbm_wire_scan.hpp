@@ -288,6 +288,155 @@ gave_up:
   return FBM_WIRE_SCAN_GAVE_UP;
 }
 
+// ---- the same pass over a message's PREFIX (fbm_wire_scan_prefix) ------------------------------------------------
+// What fbm_wire_scan_deferred2 with n_resolved = 0 answers for the whole message, as far as its first len bytes decide it:
+// FBM_WIRE_SCAN_PENDING with the first deferral candidate once its header and the bytes that make it a candidate are in
+// (1 byte behind the header for a native first item, 21 for a map), FBM_OK where the prefix is a whole message without
+// one, FBM_WIRE_SCAN_GAVE_UP for what no further byte mends (c1, the nesting bound, bytes behind the message's end),
+// and FBM_WIRE_SCAN_MORE wherever the pass would read at or past len.  The candidate test "the items at their
+// smallest fit the bytes left" needs the message's length and is not made.  An array of at least min_items items that
+// is no candidate is walked item by item as fbm_wire_candidate walks it -- accepted whole, the pass goes on behind it
+// without the nesting depth its items would take --, nothing being recorded.
+#define FBM_WIRE_SCAN_MORE 5
+
+// fbm_wire_item over a prefix: the item's byte count, 0 where no further byte makes it an accepted form, -1 where
+// that takes bytes at or past len
+static inline int64_t fbm_wire_item_prefix(const uint8_t* d, uint64_t pos, uint64_t len) {
+  if (pos >= len) return -1;
+  const uint64_t left = len - pos;
+  const uint8_t b = d[pos];
+  if (b <= 0x7f) return 1;
+  if (b >= 0xcc && b <= 0xcf) {
+    const uint32_t w = 1u << (b - 0xcc);
+    return left < 1ull + w ? -1 : (int64_t)(1ull + w);
+  }
+  const uint64_t have = left < FBM_WIRE_PREFIX_LEN ? left : FBM_WIRE_PREFIX_LEN;
+  if (memcmp(d + pos, FBM_WIRE_PREFIX, have) != 0) return 0;
+  if (left < FBM_WIRE_PREFIX_LEN + 1) return -1;
+  const uint64_t p = pos + FBM_WIRE_PREFIX_LEN;
+  uint64_t v;
+  uint32_t L;
+  if (d[p] == 0xc4) {
+    if (len - p < 2) return -1;
+    L = d[p + 1], v = p + 2;
+  } else if (d[p] == 0xc5) {
+    if (len - p < 3) return -1;
+    L = ((uint32_t)d[p + 1] << 8) | d[p + 2], v = p + 3;
+  } else {
+    return 0;
+  }
+  if (L < 1 || L > 257) return 0;
+  if (v >= len) return -1;
+  if (d[v] >= 0x80 || (L == 257 && d[v] != 0)) return 0;
+  if (len - v < L) return -1;
+  return (int64_t)(v + L - pos);
+}
+
+static inline int fbm_wire_scan_prefix_run(const uint8_t* d, uint64_t len, uint64_t min_items, uint64_t defer_items,
+                                           uint64_t defer_items_jl, fbm_wire_pending2* pending) {
+  uint64_t stack[FBM_WIRE_MAX_DEPTH];
+  int depth = 1;
+  uint64_t pos = 0;
+  stack[0] = 1;
+  if (min_items < 1) min_items = 1;
+  while (depth > 0) {
+    if (stack[depth - 1] == 0) {
+      --depth;
+      continue;
+    }
+    --stack[depth - 1];
+    if (pos >= len) return FBM_WIRE_SCAN_MORE;
+    const uint8_t b = d[pos];
+    const uint64_t left = len - pos;
+    uint64_t skip = 0, children = 0;
+    int container = 0, is_array = 0;
+    if (b <= 0x7f || b >= 0xe0 || b == 0xc0 || b == 0xc2 || b == 0xc3) {
+      skip = 1;
+    } else if (b <= 0x8f) {
+      container = 1, skip = 1, children = 2ull * (b & 0x0f);
+    } else if (b <= 0x9f) {
+      container = 1, is_array = 1, skip = 1, children = b & 0x0f;
+    } else if (b <= 0xbf) {
+      skip = 1ull + (b & 0x1f);
+    } else {
+      int lb = 0;
+      uint64_t extra = 0;
+      switch (b) {
+        case 0xc4: case 0xd9: lb = 1; break;
+        case 0xc5: case 0xda: lb = 2; break;
+        case 0xc6: case 0xdb: lb = 4; break;
+        case 0xc7: lb = 1, extra = 1; break;
+        case 0xc8: lb = 2, extra = 1; break;
+        case 0xc9: lb = 4, extra = 1; break;
+        case 0xca: case 0xce: case 0xd2: skip = 5; break;
+        case 0xcb: case 0xcf: case 0xd3: skip = 9; break;
+        case 0xcc: case 0xd0: skip = 2; break;
+        case 0xcd: case 0xd1: skip = 3; break;
+        case 0xd4: skip = 3; break;
+        case 0xd5: skip = 4; break;
+        case 0xd6: skip = 6; break;
+        case 0xd7: skip = 10; break;
+        case 0xd8: skip = 18; break;
+        case 0xdc: container = 1, is_array = 1, lb = 2; break;
+        case 0xdd: container = 1, is_array = 1, lb = 4; break;
+        case 0xde: container = 1, lb = 2; break;
+        case 0xdf: container = 1, lb = 4; break;
+        default: return FBM_WIRE_SCAN_GAVE_UP;  // 0xc1
+      }
+      if (lb) {
+        if (left < 1ull + lb) return FBM_WIRE_SCAN_MORE;
+        const uint64_t v = fbm_wire_be(d + pos + 1, lb);
+        if (container)
+          skip = 1ull + lb, children = is_array ? v : 2 * v;
+        else
+          skip = 1ull + lb + extra + v;
+      }
+    }
+    if (left < skip) return FBM_WIRE_SCAN_MORE;
+    if (!container) {
+      pos += skip;
+      continue;
+    }
+    if (is_array && children >= min_items) {
+      const uint64_t first = pos + skip;
+      int cand = -1;
+      if (first >= len) return FBM_WIRE_SCAN_MORE;  // (the array's first byte decides)
+      const uint8_t f = d[first];
+      if (defer_items && children >= defer_items && (f <= 0x7f || (f >= 0xcc && f <= 0xcf))) {
+        cand = FBM_WIRE_LOM;
+      } else if (defer_items_jl && children >= defer_items_jl) {
+        const uint64_t have = len - first < FBM_WIRE_PREFIX_LEN ? len - first : FBM_WIRE_PREFIX_LEN;
+        if (memcmp(d + first, FBM_WIRE_PREFIX, have) == 0) {
+          if (len - first < FBM_WIRE_PREFIX_LEN + 1) return FBM_WIRE_SCAN_MORE;
+          if (d[first + FBM_WIRE_PREFIX_LEN] == 0xc4 || d[first + FBM_WIRE_PREFIX_LEN] == 0xc5) cand = FBM_WIRE_JL;
+        }
+      }
+      if (cand >= 0) {
+        pending->begin = pos, pending->first = first, pending->n_items = children;
+        pending->scheme = cand, pending->pad = 0;
+        return FBM_WIRE_SCAN_PENDING;
+      }
+      uint64_t p = first, i = 0;  // fbm_wire_candidate's walk
+      for (; i < children; ++i) {
+        const int64_t c = fbm_wire_item_prefix(d, p, len);
+        if (c < 0) return FBM_WIRE_SCAN_MORE;
+        if (c == 0) break;
+        p += (uint64_t)c;
+      }
+      if (i == children) {
+        pos = p;
+        continue;
+      }
+    }
+    pos += skip;
+    if (children) {
+      if (depth >= FBM_WIRE_MAX_DEPTH) return FBM_WIRE_SCAN_GAVE_UP;
+      stack[depth++] = children;
+    }
+  }
+  return pos == len ? FBM_OK : FBM_WIRE_SCAN_GAVE_UP;  // trailing bytes: msgpack raises ExtraData
+}
+
 static inline int fbm_wire_scan_impl(const uint8_t* d, uint64_t len, uint64_t min_items, fbm_wire_scan_out* o) {
   return fbm_wire_scan_run(d, len, min_items, o, nullptr);
 }

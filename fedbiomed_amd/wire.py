@@ -37,14 +37,21 @@ chunks of `MAX_MESSAGE_BYTES_LENGTH` (4 MB) and the receiver rebuilds it with ``
 (`fedbiomed/transport/server.py:236-239`, `client.py:599-602` in `_call_researcher`), which copies the growing message at
 every chunk -- quadratic in the chunk count (a 10M-parameter JL update is 22-24 chunks).  The
 assembler keeps the chunks and joins them once.
+
+`StreamAssembler` is `ChunkAssembler` for the resident path: the same ``add`` in the transport's loop, but the reply's
+large integer array goes up to the device and is tokenized there chunk by chunk while the transport delivers the
+message, so that behind the last chunk neither the join nor the upload is left; `loads_reference` takes the
+`StreamedMessage` it returns where it takes ``bytes``.
 """
 
 from __future__ import annotations
 
+import logging
 from typing import Any, Dict, Iterable, Optional
 
 import numpy as np
 
+_log = logging.getLogger(__name__)  # the causes of `StreamAssembler`'s fallbacks (a counter alone would hide a device error)
 WIRE_TYPE = "fedbiomed_amd.EncryptedParams"
 _ENABLED = False
 
@@ -205,7 +212,7 @@ class ChunkAssembler:
 # consume exactly those bytes from the packed device form (the C ABI's fbm_wire_encode / fbm_wire_scan /
 # fbm_wire_decode), so only this side needs its two Serializer lines ("One patched side").
 _STATS = {"fast": 0, "fallback": 0, "resident": 0, "device_scan": 0, "device_scan_refused": 0, "device_scan_jl": 0,
-          "device_scan_jl_refused": 0}
+          "device_scan_jl_refused": 0, "streamed": 0, "stream_fallback": 0}
 # `loads_reference(resident=True)` leaves an all-native array of at least this many items to the device tokenizer
 # (fbm_wire_tokenize_lom) instead of the host scanner's walk: the smallest power of two from which on the device
 # route's take was the faster one on an MI355X (tools/wire_ref_ab.py --devscan, profiles/wire_devscan_ab.jsonl,
@@ -225,12 +232,14 @@ def reference_stats(reset: bool = False) -> Dict[str, Any]:
     ``resident=True``: "resident") and updates or messages that took msgpack's ("fallback") since the last
     reset, the arrays whose table the device made ("device_scan") and those its tokenizer refused, which the host
     scanner then walked ("device_scan_refused") -- both count all-native arrays; "device_scan_jl" and
-    "device_scan_jl_refused" count the arrays of big-int maps in the same way --, and the last call's phase times
+    "device_scan_jl_refused" count the arrays of big-int maps in the same way --, the arrays whose bytes and table
+    were on the device when their message's last chunk came (`StreamAssembler`: "streamed") and the messages that
+    began to go up that way and were then read from their joined bytes ("stream_fallback"), and the last call's phase times
     ("last": scan / h2d / devscan / kernel / d2h seconds; devscan covers both tokenizers)."""
     out = dict(_STATS, last=dict(_LAST))
     if reset:
         _STATS.update(fast=0, fallback=0, resident=0, device_scan=0, device_scan_refused=0, device_scan_jl=0,
-                      device_scan_jl_refused=0)
+                      device_scan_jl_refused=0, streamed=0, stream_fallback=0)
         _LAST.clear()
     return out
 
@@ -428,7 +437,215 @@ def _scan_resident(data: bytes, min_items: int, defer_items: int, defer_jl_items
     return out
 
 
-def loads_reference(data: bytes, object_hook=None, min_items: int = 1024, resident: bool = False,
+# ---- a stock peer's reply taken onto the device chunk by chunk as it arrives -------------------------------------
+def _scan_prefix(data: bytes, min_items: int, defer_items: int, defer_jl_items: int):
+    """The host's prefix scan of `StreamAssembler` (a seam like the others): `_device.wire_scan_prefix`."""
+    from . import _device as D
+
+    return D.wire_scan_prefix(data, min_items, defer_items, defer_jl_items)
+
+
+def _open_stream(scheme: str, begin: int, first: int, n_items: int, cap: int, ctx: dict):
+    """The device side of `StreamAssembler` (the same seam): a `_device.WireStream` -- ``push(chunk, offset, last)``,
+    ``result()``, ``handle(end)``, ``abort()``, ``failed``."""
+    from . import _device as D
+
+    return D.WireStream(scheme, begin, first, n_items, cap, ctx)
+
+
+def _part_slices(parts: list, lo: int, hi: int) -> list:
+    """The bytes [lo, hi) of the chunks `parts` as slices of them, nothing joined."""
+    out, pos = [], 0
+    for p in parts:
+        a, b = max(lo - pos, 0), min(hi - pos, len(p))
+        if a < b:
+            out.append(memoryview(p)[a:b])
+        pos += len(p)
+    return out
+
+
+class StreamedMessage:
+    """What `StreamAssembler.add` returns on a message's last chunk: the chunks as they came, and, where an array of
+    the message went up while they arrived (`streamed`), the device block, table and tokenizer state of that array.
+    ``bytes(msg)`` joins the chunks, once (`joins` counts it); `loads_reference` takes the message itself and, for a
+    streamed one read with ``resident=True`` and the assembler's arguments, never joins."""
+
+    __slots__ = ("_parts", "_len", "_joined", "joins", "_rx", "_cand", "_params", "_began", "_counted")
+
+    def __init__(self, parts: list, rx=None, cand=None, params=None, began: bool = False):
+        self._parts, self._len, self._joined, self.joins = parts, sum(len(p) for p in parts), None, 0
+        self._rx, self._cand, self._params, self._began, self._counted = rx, cand, params, began, False
+
+    def __len__(self) -> int:
+        return self._len
+
+    def __bytes__(self) -> bytes:
+        if self._joined is None:
+            self._joined = b"".join(self._parts)
+            self.joins += 1
+        return self._joined
+
+    @property
+    def streamed(self) -> bool:
+        """Whether the device holds the message's array and the table the tokenizer made while the chunks came."""
+        return self._rx is not None and not self._rx.failed
+
+    def _fell_back(self) -> None:
+        if self._began and not self._counted:
+            _STATS["stream_fallback"] += 1
+            self._counted = True
+        if self._rx is not None:
+            self._rx.abort()
+            self._rx = None
+
+
+class StreamAssembler:
+    """`ChunkAssembler` for a researcher that reads the reply with ``loads_reference(msg, resident=True)``: the same
+    ``add(chunk, size, iteration)`` in the transport's loop, chunks in arrival order, ``iteration == size`` the
+    completion test, None before the last chunk -- and on it a `StreamedMessage`, not ``bytes``.
+
+    While the chunks arrive the message's first large integer array goes up and is tokenized behind the wait for the
+    next chunk.  The chunks are kept as they come.  After each of the first four the host's prefix scanner
+    (fbm_wire_scan_prefix) looks for the array `loads_reference` would leave to a device tokenizer first: at least
+    ``max(min_items, device_scan_min_items)`` native items, or, under an `object_hook` that reads the reference's int
+    map, ``max(min_items, device_scan_jl_min_items)`` of those maps (the arguments and defaults are
+    `loads_reference`'s; they are needed when the first chunk arrives, and a `loads_reference` call with other
+    values reads ``bytes(msg)``).  Until one is found no device call is made; a message of one chunk, one without such
+    an array in its first four chunks and a malformed one are kept as `ChunkAssembler` keeps them.  Once it is known
+    a device block takes the message from the array's header on -- ``size * len(first chunk)`` bytes bound it: the
+    reference's sender cuts every chunk but the last to ``MAX_MESSAGE_BYTES_LENGTH`` --, the kept chunks and then
+    every further one go up through a pinned staging ring on a stream the assembler owns, and after each upload the
+    tokenizer is fed the tiles that have become final (fbm_wire_stream_feed).  `add` never synchronises the device.
+    A chunk that does not fit the block ends streaming for the message, and so does anything the device side raises;
+    a message whose announced ``size`` asks for a block of more than `max_block_bytes` (1 GiB: ten times the largest
+    reply of a 10M-parameter model) or for more device memory than there is is not streamed at all -- `add` keeps
+    the chunks as `ChunkAssembler` does, whatever the peer announces.  (Where the first chunk does not
+    decide, the scan runs over a growing copy of the chunks so far, each of the first four copied into it once; the
+    message itself is never joined here.  What ends streaming is logged under this module's logger.)"""
+
+    def __init__(self, object_hook=None, min_items: int = 1024, device_scan_min_items: Optional[int] = None,
+                 device_scan_jl_min_items: Optional[int] = None, max_block_bytes: int = 1 << 30) -> None:
+        self._max_block = int(max_block_bytes)
+        dmin = DEVICE_SCAN_MIN_ITEMS if device_scan_min_items is None else int(device_scan_min_items)
+        jmin = DEVICE_SCAN_JL_MIN_ITEMS if device_scan_jl_min_items is None else int(device_scan_jl_min_items)
+        self._params = (object_hook, int(min_items), dmin, jmin)
+        self._jl = _hook_reads_ints(object_hook)
+        self._ctx: dict = {}  # the device side's stream and staging ring, kept from message to message
+        self._reset()
+
+    def _reset(self) -> None:
+        self._parts: list = []
+        self._got, self._rx, self._cand, self._looking, self._began = 0, None, None, True, False
+        self._prefix: Optional[bytearray] = None  # the chunks so far, while the prefix scan still asks for more
+
+    def _look(self, size: int) -> None:
+        """After one of the first four chunks: the prefix scan, and where it finds the array, the device block."""
+        _, min_items, dmin, jmin = self._params
+        if len(self._parts) == 1:
+            prefix = self._parts[0]
+        else:  # (rare: the array begins behind the first chunk.  Each chunk is copied once into the growing prefix)
+            if self._prefix is None:
+                self._prefix = bytearray(self._parts[0])
+            self._prefix += self._parts[-1]
+            prefix = self._prefix
+        kind, cand = _scan_prefix(prefix, min_items, max(dmin, 1), max(jmin, 1) if self._jl else 0)
+        if kind != "more" or len(self._parts) >= 4:
+            self._prefix = None
+        if kind == "more":
+            return
+        self._looking = False
+        if kind != "pending":
+            return
+        begin, first, n_items, scheme = cand
+        cap = size * len(self._parts[0])
+        # (deferred2's bound, which the prefix cannot see: the items at their smallest fit what is still to come)
+        if n_items * (23 if scheme == "jl" else 1) > cap - first:
+            return
+        if cap - begin > self._max_block:
+            return
+        try:
+            rx = _open_stream(scheme, begin, first, n_items, cap, self._ctx)
+        except Exception as err:  # (no device memory for a block of the announced size, ...): the plain assembler's message
+            _log.warning("StreamAssembler: the device side did not open (%s: %s); the message is kept on the host",
+                         type(err).__name__, err)
+            return
+        self._began, self._cand, self._rx = True, cand, rx
+        pos = 0
+        for p in self._parts[:-1]:
+            self._push(p, pos, False)
+            pos += len(p)
+
+    def _push(self, chunk, offset: int, last: bool) -> None:
+        """One chunk to the device side; whatever it raises ends streaming for this message, never `add`."""
+        try:
+            self._rx.push(chunk, offset, last)
+        except Exception as err:
+            _log.warning("StreamAssembler: streaming ended for this message (%s: %s); it will be read from its joined bytes",
+                         type(err).__name__, err)
+            self._rx.abort()
+
+    def add(self, chunk: bytes, size: int, iteration: int):
+        self._parts.append(chunk)
+        last = size == iteration
+        if self._looking and size > 1:
+            self._looking = len(self._parts) < 4  # (set before the look: an exception there does not bring it back)
+            self._look(size)
+        elif size == 1:
+            self._looking = False
+        if self._rx is not None and not self._rx.failed:
+            self._push(chunk, self._got, last)
+        self._got += len(chunk)
+        if not last:
+            return None
+        msg = StreamedMessage(self._parts, self._rx, self._cand, self._params, self._began)
+        self._reset()
+        return msg
+
+
+_NOT_STREAMED = object()
+
+
+def _loads_streamed(msg: StreamedMessage, object_hook, min_items: int, resident: bool, dmin: int, jmin: int):
+    """`loads_reference` of a streamed message without joining it, or _NOT_STREAMED where the call is the one on
+    ``bytes(msg)``: read without ``resident``, with other arguments than the assembler's, refused by the tokenizer, or
+    with a reduced message that does not unpack."""
+    import os
+
+    import msgpack
+
+    if not msg._began:
+        return _NOT_STREAMED
+    if not resident or not msg.streamed or msg._params != (object_hook, int(min_items), dmin, jmin):
+        msg._fell_back()
+        return _NOT_STREAMED
+    begin, first, n_items, scheme = msg._cand
+    got, end = msg._rx.result()
+    if got != n_items or not first < end <= len(msg):
+        msg._fell_back()
+        return _NOT_STREAMED
+    token = "fedbiomed_amd.stream." + os.urandom(12).hex()
+    reduced = b"".join(_part_slices(msg._parts, 0, begin) + [msgpack.packb({"__type__": token, "value": 0})] +
+                       _part_slices(msg._parts, end, len(msg)))
+    handle = msg._rx.handle(end)
+
+    def hook(o):
+        if o.get("__type__") == token:
+            _STATS["resident"] += 1
+            _STATS["streamed"] += 1
+            return ResidentUpdate(scheme, n_items, handle)
+        return o if object_hook is None else object_hook(o)
+
+    before = dict(_STATS)
+    try:
+        return _loads_reference(reduced, hook, min_items, True, dmin, jmin, count_plain=False)
+    except Exception as err:  # what msgpack raises for the reduced message it raises for the whole one: that call decides
+        _log.info("loads_reference: the streamed message did not unpack (%s: %s); reading its joined bytes", type(err).__name__, err)
+        _STATS.update(before)
+        msg._fell_back()
+        return _NOT_STREAMED
+
+
+def loads_reference(data, object_hook=None, min_items: int = 1024, resident: bool = False,
                     device_scan_min_items: Optional[int] = None, device_scan_jl_min_items: Optional[int] = None) -> Any:
     """``msgpack.unpackb(data, object_hook=object_hook, strict_map_key=False)`` with every integer array of at
     least `min_items` items the host scanner records read on the device: it comes back as an `EncryptedParams`
@@ -446,7 +663,29 @@ def loads_reference(data: bytes, object_hook=None, min_items: int = 1024, reside
     before ("device_scan_refused").  An array of at least `device_scan_jl_min_items` big-int maps (None:
     `DEVICE_SCAN_JL_MIN_ITEMS`) goes the same way through the tokenizer for that form ("device_scan_jl"; a mixed
     array is refused and walked on the host: "device_scan_jl_refused") -- only where `object_hook` reads the map as
-    the reference's does.  ``resident=False`` keeps the host scan: its cost is the Python ints."""
+    the reference's does.  ``resident=False`` keeps the host scan: its cost is the Python ints.
+
+    `data` may be a `StreamedMessage` (`StreamAssembler`): the result is that of the same call on ``bytes(data)``.
+    Where an array of it went up while its chunks arrived and the call has ``resident=True`` and the assembler's
+    arguments, the chunks are not joined and that array is not uploaded again: the tokenizer's two result words come
+    back (the one synchronising copy), the message without the array -- its head, a token and its tail, from the
+    chunks' slices -- is read as above (a further large array in the tail goes the usual way), and the array comes
+    back as a `ResidentUpdate` on the streamed block and table (`reference_stats` counts "streamed").  An array the
+    tokenizer refuses (mixed, a negative int, cut off by the message's end) and a reduced message that does not
+    unpack make this the call on ``bytes(data)``, with that call's result or error ("stream_fallback")."""
+    dmin = DEVICE_SCAN_MIN_ITEMS if device_scan_min_items is None else int(device_scan_min_items)
+    jmin = DEVICE_SCAN_JL_MIN_ITEMS if device_scan_jl_min_items is None else int(device_scan_jl_min_items)
+    if isinstance(data, StreamedMessage):
+        out = _loads_streamed(data, object_hook, min_items, resident, dmin, jmin)
+        if out is not _NOT_STREAMED:
+            return out
+        data = bytes(data)
+    return _loads_reference(data, object_hook, min_items, resident, dmin, jmin)
+
+
+def _loads_reference(data: bytes, object_hook, min_items: int, resident: bool, dmin: int, jmin: int,
+                     count_plain: bool = True) -> Any:
+    """`loads_reference` for ``bytes``; count_plain: whether a message without arrays counts as "fallback"."""
     import os
     import time
 
@@ -457,8 +696,6 @@ def loads_reference(data: bytes, object_hook=None, min_items: int = 1024, reside
     _LAST.clear()
     held: Dict[int, Any] = {}  # the arrays the device tokenized: index -> handle
     if resident:
-        dmin = DEVICE_SCAN_MIN_ITEMS if device_scan_min_items is None else int(device_scan_min_items)
-        jmin = DEVICE_SCAN_JL_MIN_ITEMS if device_scan_jl_min_items is None else int(device_scan_jl_min_items)
         # (an array of maps is this library's only under a hook that reads them: otherwise it never goes up)
         arrays, held = _scan_resident(data, min_items, max(dmin, 1), max(jmin, 1) if _hook_reads_ints(object_hook) else 0)
     else:
@@ -469,7 +706,7 @@ def loads_reference(data: bytes, object_hook=None, min_items: int = 1024, reside
         keep = [i for i, a in enumerate(arrays) if a[3] != "jl"]  # (a tokenized "jl" array exists only under such a hook)
         arrays, held = [arrays[i] for i in keep], {k: held[i] for k, i in enumerate(keep) if i in held}
     if not arrays:
-        _STATS["fallback"] += 1
+        _STATS["fallback"] += 1 if count_plain else 0
         return msgpack.unpackb(data, object_hook=object_hook, strict_map_key=False)
     if resident:  # the arrays the scan recorded the old way go up with their host tables in a block of their own
         rest = [i for i in range(len(arrays)) if i not in held]

@@ -570,6 +570,47 @@ int fbm_wire_scan_deferred2(const uint8_t* data, uint64_t len, uint64_t min_item
                             fbm_wire_array* arrays, uint64_t arrays_cap, uint64_t* n_arrays, uint64_t* ckpt,
                             uint64_t ckpt_cap, uint64_t* n_ckpt, fbm_wire_pending2* pending);
 
+/* The two tokenizers as resumable scans, for a message that reaches the device chunk by chunk (additions under ABI 7).
+ * A tile's place depends on the span's address, span_base and `first`, not on the span's length, so a span that
+ * grows keeps its tiles: each feed runs the three passes over the tiles that have become final since the last one,
+ * the scan entered in the running state the last feed left in `state`.
+ *
+ * state (device, FBM_WIRE_STREAM_STATE_WORDS 8-byte words, 8-byte aligned) is the stream's record: the bytes fed and
+ * the tiles done (as of the last feed that ran a tile), the running entry state (FBM_WIRE_LOM: automaton phase and
+ * items so far; FBM_WIRE_JL: entry offset below 280 and items so far) and, in words 3 and 4, the one-shot calls'
+ * result[0] and result[1].  fbm_wire_stream_begin resets it on the stream for an array of n_items > 0 items whose
+ * item 0 is at the absolute offset first; the library keeps a host-side record under the state's address (at most
+ * 64 unfinished streams; the oldest is dropped), from which the feeds plan their launches: nothing is read back.
+ *
+ * fbm_wire_stream_feed: span (device; the same address and span_base at every feed) holds the message's bytes
+ * [span_base, span_base + avail_len), avail_len not below the last feed's; last != 0 says that avail_len is the
+ * span's final length.  A feed that is not the last runs the whole 4 KiB tiles whose end lies at least one item's
+ * reach (8 bytes; 280 for FBM_WIRE_JL) below avail_len; the last one runs every tile left.  ckpt (device, n_ckpt
+ * words as the one-shot call takes them, the same at every feed) and workspace (device,
+ * fbm_wire_stream_workspace(scheme, cap_len) bytes for a cap_len no feed's avail_len exceeds) are 8-byte aligned.
+ * For every way of cutting a span into feeds, state[3], state[4] and ckpt[0 .. n_ckpt) are behind the last feed word
+ * for word what fbm_wire_tokenize_lom / fbm_wire_tokenize_jl write as result[0], result[1] and ckpt for the whole
+ * span at the same address in one call.  No byte at or past avail_len is read and nothing outside ckpt, state and
+ * workspace is written, whatever the bytes are; everything runs on the stream.  Argument errors are the one-shot
+ * calls' (n_items == 0 is FBM_E_ARG at begin: there is nothing to stream); in addition a state without a begun
+ * stream of that scheme, a feed behind the last one, another span or span_base than the first feed's and an
+ * avail_len below what was already fed are FBM_E_ARG.  `first` must lie inside the span at the last feed. */
+#define FBM_WIRE_STREAM_STATE_WORDS 16
+uint64_t fbm_wire_stream_workspace(int scheme, uint64_t cap_len);
+int fbm_wire_stream_begin(int scheme, uint64_t first, uint64_t n_items, uint64_t* state, void* stream);
+int fbm_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last,
+                         uint64_t* ckpt, uint64_t n_ckpt, uint64_t* state, void* workspace, void* stream);
+
+/* fbm_wire_scan_deferred2's pass (n_resolved = 0) over a message's first len bytes, no device call, no byte at or
+ * past len read: FBM_WIRE_PENDING with *pending the message's first deferral candidate once the prefix holds its
+ * header and the bytes that make it one (its first byte; 21 bytes for an array of maps); FBM_OK where the prefix is
+ * a whole message without a candidate; FBM_E_UNSUPPORTED for what no further byte mends; FBM_WIRE_MORE where the
+ * pass needs bytes at or past len.  The candidate test "the items at their smallest fit the bytes left" needs the
+ * message's length and is not made: the caller bounds n_items by what it is about to receive. */
+#define FBM_WIRE_MORE 2
+int fbm_wire_scan_prefix(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
+                         uint64_t defer_items_jl, fbm_wire_pending2* pending);
+
 /* Drops the library's host-side caches: the short path's constant C per (N, |key|) -- kept under a
  * SHA-256 digest of (N, |key|), never the key itself, and zeroed here and on eviction -- and the
  * per-biprime public parameters.  The reference keeps nothing between calls (a fresh

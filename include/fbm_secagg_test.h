@@ -144,6 +144,11 @@ int fbm_test_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t s
                               uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
 int fbm_test_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
                                uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
+/* fbm_wire_stream_begin / fbm_wire_stream_feed over HOST buffers: state is a host record, the feeds cut the span into
+ * the same segments and run them through the same per-tile routines (wire_seg_host_feed), same argument errors. */
+int fbm_test_wire_stream_begin(int scheme, uint64_t first, uint64_t n_items, uint64_t* state);
+int fbm_test_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last,
+                              uint64_t* ckpt, uint64_t n_ckpt, uint64_t* state, void* workspace);
 
 /* The LOM aggregate kernel fbm_lom_aggregate launches for n_parties rows of n elements at y (device
  * pointer; its alignment picks the form), as rocprofv3 names it without the "fbm::" namespace, e.g.

@@ -46,6 +46,18 @@ wire_decode_lom_kernel + lom_fold_kernel on the same bytes, then four reads of t
 forced on (wire_tok_maps_kernel, wire_tok_scan_kernel, wire_tok_emit_kernel; the printed line has the stream's bytes),
 then four reads of a JL update of ceil(elements / 30) ciphertexts with the JL device scan forced on
 (wire_tokj_maps_kernel, wire_tokj_scan_kernel, wire_tokj_emit_kernel; a second line).
+
+--stream: the receive path behind the last chunk (profiles/wire_stream_ab.jsonl).  One node's LOM reply of --elements
+words and one JL reply of ceil(elements / 30) ciphertexts, cut into 4 MB chunks as the reference's sender cuts them,
+handed to `add` one by one; timed from handing over the last chunk until `loads_reference` returns:
+
+  streamed     wire.StreamAssembler.add ..., loads_reference(msg, hook, resident=True)
+  parent       wire.ChunkAssembler.add ..., loads_reference(bytes, hook, resident=True)    (the parent commit's path)
+
+Alternating, --runs fresh processes of each (one warm-up message per scheme, then one timed message per scheme and
+pacing), one session.  Chunks are paced 1.3 ms apart (4 MB at 25 Gb/s, faster than any link a hospital node has); an
+unpaced leg (gap 0) is recorded beside it without a condition, and so is the host time spent inside all `add` calls.
+The condition: on both schemes the slowest paced streamed run is below the fastest paced parent run.
 """
 import argparse
 import gc
@@ -316,6 +328,95 @@ def resident(a):
     return 0 if summary["holds"] else 1
 
 
+CHUNK = 4 * 1024 * 1024  # the reference's MAX_MESSAGE_BYTES_LENGTH
+STREAM_GAPS_MS = (1.3, 0.0)
+
+
+def stream_one(a):
+    """One process of --stream: `a.stream_one` = "streamed" or "parent"; one JSON line per scheme and pacing."""
+    import torch
+
+    from fedbiomed_amd import _device as D
+
+    dev = D.device()
+    rng = np.random.default_rng(2026)
+    n_ct = -(-a.elements // 30)
+    updates = {"lom": wire.EncryptedParams.from_packed("lom", _lom_words(rng, a.elements)),
+               "jl": wire.EncryptedParams.from_packed("jl", _jl_rows(rng, n_ct))}
+    streamed = a.stream_one == "streamed"
+    for scheme, upd in updates.items():
+        data = wire.dumps_reference({"node_id": "node-00", "params": upd, "n": len(upd)}, default=ref_default)
+        chunks = [data[i:i + CHUNK] for i in range(0, len(data), CHUNK)]
+        asm = wire.StreamAssembler(object_hook=ref_hook) if streamed else wire.ChunkAssembler()
+
+        def receive(gap):
+            t_add, start, msg = 0.0, time.perf_counter(), None
+            for i, c in enumerate(chunks, 1):
+                # chunk i arrives at start + (i - 1) * gap whatever `add` cost: both sides see the same link, and the
+                # host time of `add` counts against the side that spends it
+                while time.perf_counter() < start + (i - 1) * gap:
+                    pass
+                t0 = time.perf_counter()
+                msg = asm.add(c, len(chunks), i)
+                t_add += time.perf_counter() - t0
+            got = wire.loads_reference(msg, object_hook=ref_hook, resident=True)
+            t1 = time.perf_counter()
+            return t1 - t0, t_add, got, msg
+
+        _, _, got, msg = receive(0.0)  # warm-up: allocations, the pinned ring, the library's first launches
+        assert type(got["params"]) is wire.ResidentUpdate and got["params"].n_items == len(upd)
+        if a.elements <= 100_000:  # (a small run also checks the values)
+            assert got["params"].tolist() == list(upd)
+        del got, msg
+        for gap_ms in STREAM_GAPS_MS:
+            wire.reference_stats(reset=True)
+            gc.collect()
+            torch.cuda.synchronize(dev)
+            dt, t_add, got, msg = receive(gap_ms * 1e-3)
+            st = wire.reference_stats()
+            rec = {"leg": f"{scheme}_last_chunk", "impl": a.stream_one, "gap_ms": gap_ms, "ms": round(dt * 1e3, 3),
+                   "add_total_ms": round(t_add * 1e3, 3), "chunks": len(chunks), "chunk_bytes": CHUNK, "message_bytes": len(data),
+                   "items": len(upd), "streamed": st["streamed"], "stream_fallback": st["stream_fallback"],
+                   "joined": bool(getattr(msg, "joins", 1))}
+            print(json.dumps(rec), flush=True)
+            del got, msg
+    return 0
+
+
+def stream(a):
+    """--stream: alternating fresh processes of both implementations (see the module's docstring)."""
+    import subprocess
+
+    lines = []
+    for run in range(a.runs):
+        for impl in ("streamed", "parent"):
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--stream-one", impl, "--elements", str(a.elements)],
+                                 check=True, capture_output=True, text=True, timeout=600).stdout
+            for ln in out.splitlines():
+                rec = dict(json.loads(ln), run=run)
+                lines.append(rec)
+                print(json.dumps(rec), flush=True)
+    legs = {}
+    for leg in sorted({r["leg"] for r in lines}):
+        for gap in STREAM_GAPS_MS:
+            t = {impl: [r["ms"] for r in lines if (r["leg"], r["gap_ms"], r["impl"]) == (leg, gap, impl)] for impl in ("streamed", "parent")}
+            adds = {impl: [r["add_total_ms"] for r in lines if (r["leg"], r["gap_ms"], r["impl"]) == (leg, gap, impl)]
+                    for impl in ("streamed", "parent")}
+            legs[f"{leg}@{gap}ms"] = {"streamed_ms": t["streamed"], "parent_ms": t["parent"], "slowest_streamed_ms": max(t["streamed"]),
+                                      "fastest_parent_ms": min(t["parent"]), "holds": max(t["streamed"]) < min(t["parent"]),
+                                      "add_total_ms": adds, "conditioned": gap > 0}
+    paced = [v for v in legs.values() if v["conditioned"]]
+    summary = {"summary": legs, "condition": "paced legs, both schemes: slowest streamed run < fastest parent run",
+               "holds": all(v["holds"] for v in paced), "pacing_ms": STREAM_GAPS_MS[0], "chunk_bytes": CHUNK, "elements": a.elements,
+               "processes_each": a.runs, "all_streamed": all(r["streamed"] == 1 and not r["joined"] for r in lines if r["impl"] == "streamed")}
+    lines.append(summary)
+    print(json.dumps(summary), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.writelines(json.dumps(ln) + "\n" for ln in lines)
+    return 0 if summary["holds"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--elements", type=int, default=10_000_000)
@@ -326,11 +427,17 @@ def main():
     ap.add_argument("--devscan-jl", action="store_true")
     ap.add_argument("--device-scan-min-items", type=int, default=None)
     ap.add_argument("--device-scan-jl-min-items", type=int, default=None)
+    ap.add_argument("--stream", action="store_true")
+    ap.add_argument("--stream-one", choices=("streamed", "parent"), default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "wire_devscan_jl_ab.jsonl" if a.devscan_jl else
+    if a.stream_one:
+        return stream_one(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "wire_stream_ab.jsonl" if a.stream else "wire_devscan_jl_ab.jsonl" if a.devscan_jl else
                                   "wire_devscan_ab.jsonl" if a.devscan else
                                   "wire_resident_ab.jsonl" if a.resident else "wire_reference_ab.jsonl")
+    if a.stream:
+        return stream(a)
     if a.kernels:
         return kernels(a)
     if a.devscan or a.devscan_jl:
