@@ -859,7 +859,7 @@ def _key_limbs(key: int) -> Tuple[np.ndarray, int]:
 
 JL_MAX_CT = 14_000_000  # include/fbm_secagg.h FBM_JL_MAX_CT: ciphertexts per library call
 
-_ENGINES = {"auto": 0, "single": 1, "generic": 2, "triple": 3, "quad": 4}
+_ENGINES = {"auto": 0, "single": 1, "generic": 2, "triple": 3, "quad": 4, "wave": 5}
 
 
 class jl_engine:
@@ -993,7 +993,7 @@ def list_encrypt_stripes(n_ct: int, dev=None) -> List[Tuple[int, int]]:
 
 def jl_engine_for(n_ct: int) -> str:
     """The engine a launch of n_ct ciphertexts takes under this thread's policy (test build)."""
-    return {1: "single", 2: "generic", 3: "triple", 4: "quad"}[N.load_test().fbm_jl_engine_for(int(n_ct))]
+    return {1: "single", 2: "generic", 3: "triple", 4: "quad", 5: "wave"}[N.load_test().fbm_jl_engine_for(int(n_ct))]
 
 
 def lom_aggregate_kernel(n_parties: int, y: torch.Tensor) -> str:

@@ -1865,9 +1865,9 @@ int fbm_jl_triple_mads(int square) {
 
 int fbm_jl_set_engine(int mode) {
   if (mode != FBM_ENGINE_AUTO && mode != FBM_ENGINE_SINGLE && mode != FBM_ENGINE_GENERIC && mode != FBM_ENGINE_QUAD &&
-      mode != FBM_ENGINE_TRIPLE) {
+      mode != FBM_ENGINE_TRIPLE && mode != FBM_ENGINE_WAVE) {
     set_error("fbm_jl_set_engine: mode must be 0 (auto), 1 (one lane per ciphertext), 2 (generic: any modulus), "
-              "3 (three lanes) or 4 (four)");
+              "3 (three lanes), 4 (four) or 5 (a wave per ciphertext)");
     return FBM_E_ARG;
   }
   return jl_engine_set(mode);

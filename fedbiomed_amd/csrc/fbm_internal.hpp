@@ -390,12 +390,18 @@ uint64_t jl_table_slots();
 #define FBM_ENGINE_GENERIC 2  // every modulus on the generic engine (fbm_gen.hip; odd N: a cross-check)
 #define FBM_ENGINE_TRIPLE 3
 #define FBM_ENGINE_QUAD 4
+#define FBM_ENGINE_WAVE 5  // one ciphertext per wave64 (fbm_jl_wave.hip): the latency of a small launch
 int jl_engine_policy();
 int jl_engine_set(int mode);
 int jl_chain_set(int percall);
 int jl_split_set(int on);
 int jl_engine_for(uint64_t n_ct);
 uint64_t jl_table_bytes(uint64_t n_ct);
+// the wave engine (fbm_jl_wave.hip): launch_jl_exp's inputs and outputs; the ciphertexts of one resident round
+int launch_jl_expw(const uint32_t* H, uint64_t n_ct, const JlSched& sc, int mode, int key_is_zero,
+                   const uint32_t* nude, const uint32_t* ops, const uint32_t* cst, uint32_t* out, hipStream_t s,
+                   const uint32_t* Hc);
+uint64_t wave_resident_ct();
 // compute units of the calling thread's current device (cached per device)
 int device_num_cu();
 

@@ -2362,8 +2362,22 @@ static int group_ct_per_wg(int engine) { return engine == FBM_ENGINE_TRIPLE ? 84
 // w = 1 … 5, quad 9.4 / 17.1 / 24.8 / 32.5 / 46.6 at w = 1 / 2 / 3 / 4 / 6; the one-lane engine with its
 // unrolled square (profiles/r3_unroll_ab.jsonl) 27.2 (lone waves), 49 (one round of two), then ~45.5 per
 // round (a tail of at most half a round: ~23)
+// The wave engine (fbm_jl_wave.hip), measured on MI355X with tools/exp_probe.py (the whole decryption-factor
+// call, 2043-bit negative key, BIPRIME0; profiles/wave_engine_sweep.jsonl): 4.45 - 4.64 ms at 1 ... 768
+// ciphertexts and 4.54 - 4.74 at 1 024 (one wave per SIMD), 6.35 - 6.48 at 2 048 (one resident round of two
+// waves per SIMD), 12.2 at 4 096, 21.5 at 8 192: A = 1.3, B = 5.05 per round, 4.5 up to half a round.  The quad
+// engine takes 9.33 - 9.59 ms at every one of these sizes, so the wave engine wins up to one resident round
+// (FBM_WAVE_AUTO_CT) and loses from two; FBM_ENGINE_AUTO's bound is that, capped at three ciphertexts per CU.
+#define FBM_WAVE_MS_A 1.3
+#define FBM_WAVE_MS_B 5.05
+#define FBM_WAVE_AUTO_CT 2048u
 static double engine_model_ms(int engine, uint64_t n_ct) {
   const uint64_t ncu = (uint64_t)device_num_cu();
+  if (engine == FBM_ENGINE_WAVE) {  // rounds of one resident launch (wave_resident_ct ciphertexts)
+    const uint64_t res = wave_resident_ct();
+    if (n_ct <= res / 2) return 4.5;
+    return FBM_WAVE_MS_A + FBM_WAVE_MS_B * (double)((n_ct + res - 1) / res);
+  }
   if (engine == FBM_ENGINE_SINGLE) {
     const uint64_t lanes = ncu * 2 * FBM_BLOCK;
     if (n_ct <= lanes / 2) return 27.2;
@@ -2389,6 +2403,10 @@ int jl_engine_for(uint64_t n_ct) {
       best = g;
     }
   }
+  // the wave engine: launches up to its measured bound only, itself capped at three ciphertexts per CU
+  const uint64_t cap = 3 * (uint64_t)device_num_cu();
+  if (n_ct <= (FBM_WAVE_AUTO_CT < cap ? FBM_WAVE_AUTO_CT : cap) && engine_model_ms(FBM_ENGINE_WAVE, n_ct) < tb)
+    best = FBM_ENGINE_WAVE;
   return best;
 }
 
@@ -2517,6 +2535,7 @@ int launch_jl_exp(const uint32_t* H, uint64_t n_ct, const JlParams& jp, const Jl
   if (t_chain_percall) mode |= FBM_EXP_PERCALL;
   if (g_batch.active && g_batch.accept) return jl_batch_record(H, n_ct, jp, sc, mode, nude, ops, cst, out, Hc);
   const int eng = jl_engine_for(n_ct);
+  if (eng == FBM_ENGINE_WAVE) return launch_jl_expw(H, n_ct, sc, mode, jp.key_is_zero, nude, ops, cst, out, s, Hc);
   if (eng == FBM_ENGINE_QUAD || eng == FBM_ENGINE_TRIPLE) {
     uint64_t g = (n_ct + group_ct_per_wg(eng) - 1) / group_ct_per_wg(eng);
     // Workgroups launched per CU (each pulls chunks until none are left).  Up to four chunks per CU, two
