@@ -30,7 +30,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "_lib", "libfbm_secagg.so")
 TEST_OUT = os.path.join(HERE, "_lib", "libfbm_secagg_test.so")
-KERNEL_SOURCES = ["fbm_lom.hip", "fbm_jl.hip", "fbm_jl_wave.hip", "fbm_gen.hip", "fbm_ass.hip", "fbm_wire.hip"]
+KERNEL_SOURCES = ["fbm_lom.hip", "fbm_jl.hip", "fbm_jl_wave.hip", "fbm_jl_wide.hip", "fbm_gen.hip", "fbm_ass.hip",
+                  "fbm_wire.hip"]
 SETUP_SOURCE = "fbm_setup.hip"  # host only, no test hooks: compiled once, like the kernels
 CAPI_SOURCE = "fbm_capi.hip"
 SOURCES = KERNEL_SOURCES + [SETUP_SOURCE, CAPI_SOURCE]

@@ -1328,6 +1328,159 @@ def jl_aggregate(cts: torch.Tensor, biprime: int, key: int, tau: int, n_expected
 
 
 # ------------------------------------------------------------------------------------------
+# Joye-Libert for an odd biprime of 1025 to 2048 bits: the wide engine (csrc/fbm_jl_wide.hip)
+# ------------------------------------------------------------------------------------------
+JLW_LIMBS = 128  # a ciphertext's 32-bit limbs (< N^2 < 2^4096)
+
+
+def jl_wide(biprime) -> bool:
+    """Whether SecaggCrypter's one-shot calls take the wide engine for this biprime: an odd integer of 1025 to
+    2048 bits.  Every other biprime takes the code it took before (an even one above 1024 bits its FB624)."""
+    return isinstance(biprime, int) and not isinstance(biprime, bool) and biprime & 1 == 1 \
+        and 1025 <= biprime.bit_length() <= 2048
+
+
+def _jlw_key_limbs(key: int) -> Tuple[np.ndarray, int]:
+    if abs(key).bit_length() > 4096:
+        raise FedbiomedSecaggCrypterError(f"{ErrorNumbers.FB624.value}: key larger than 4096 bits")
+    return int_limbs(abs(key), JLW_LIMBS), 1 if key < 0 else 0
+
+
+def _jlw_rows(t: torch.Tensor, shape, what: str, dev) -> torch.Tensor:
+    if t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int32 {tuple(shape)} tensor on {dev}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+    return t
+
+
+def jlw_encrypt(x: torch.Tensor, biprime: int, key: int, tau: int, n_users: int, clip=None, target=None,
+                weight: int = 1, ct_offset: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """jl_encrypt for a wide biprime: one party's ciphertexts as int32 [n_ct, 128] limbs."""
+    dev = x.device
+    lib = N.load()
+    target = target or SAParameters.TARGET_RANGE
+    es, cr = jl_slot(target, n_users)
+    raw = x.dtype == torch.int64
+    c, c2, tf, tm1 = (1.0, 2.0, 1.0, 0) if raw else quant_params(clip, target)
+    tl = _check_round(tau)
+    x = x.contiguous()
+    xdt, n = _x_dtype(x), x.numel()
+    n_ct = (n + cr - 1) // cr
+    ct = torch.empty((n_ct, JLW_LIMBS), dtype=torch.int32, device=dev) if out is None \
+        else _jlw_rows(out, (n_ct, JLW_LIMBS), "out", dev)
+    if n_ct == 0:
+        return ct
+    bp = int_limbs(biprime, 64)
+    kl, kneg = _jlw_key_limbs(key)
+    chunk = jl_chunk_ct()
+    ws = torch.empty(int(lib.fbm_jlw_workspace(min(n_ct, chunk))), dtype=torch.uint8, device=dev)
+    try:
+        for k0 in range(0, n_ct, chunk):
+            k1 = min(n_ct, k0 + chunk)
+            xs = x[k0 * cr:min(n, k1 * cr)]
+            st = _stats(dev)
+            _call(lib.fbm_jlw_encrypt, _ptr(xs), xdt, xs.numel(), c, c2, tf, tm1, int(weight) & U64_MAX, es, cr,
+                  _np_ptr(bp), _np_ptr(kl), kneg, _np_ptr(tl), int(ct_offset) + k0, _ptr(ct[k0:k1]), _ptr(ws),
+                  _ptr(st), _stream())
+            _check_stats_or_defer(st)
+    finally:
+        ws.zero_()  # it holds |key| beside the constants: zeroed, in stream order, before the allocator has it back
+    return ct
+
+
+def jlw_decrypt_factor(n_ct: int, biprime: int, key: int, tau: int, ct_offset: int = 0, dev=None) -> torch.Tensor:
+    """jl_decrypt_factor for a wide biprime: H(t_k)^key mod N^2 as int32 [n_ct, 128] limbs."""
+    dev = dev or device()
+    lib = N.load()
+    tl = _check_round(tau)
+    f = torch.empty((n_ct, JLW_LIMBS), dtype=torch.int32, device=dev)
+    if n_ct == 0:
+        return f
+    bp = int_limbs(biprime, 64)
+    kl, kneg = _jlw_key_limbs(key)
+    chunk = jl_chunk_ct()
+    ws = torch.empty(int(lib.fbm_jlw_workspace(min(n_ct, chunk))), dtype=torch.uint8, device=dev)
+    try:
+        for k0 in range(0, n_ct, chunk):
+            k1 = min(n_ct, k0 + chunk)
+            st = _stats(dev)
+            _call(lib.fbm_jlw_decrypt_factor, k1 - k0, _np_ptr(bp), _np_ptr(kl), kneg, _np_ptr(tl),
+                  int(ct_offset) + k0, _ptr(f[k0:k1]), _ptr(ws), _ptr(st), _stream())
+            _check_stats_or_defer(st)
+    finally:
+        ws.zero_()  # (|key|, as jlw_encrypt's)
+    return f
+
+
+def jlw_powmod(h: torch.Tensor, biprime: int, key: int, pt: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """jl_powmod for a wide biprime: (N pt + 1) h^key mod N^2 (pt int32 [n, 32] or None) of the bases h, int32
+    [n, 128] limbs below 2^4096; a negative key inverts the base first."""
+    dev = h.device
+    lib = N.load()
+    n_ct = h.shape[0]
+    h = _jlw_rows(h.contiguous(), (n_ct, JLW_LIMBS), "h", dev)
+    if pt is not None:
+        pt = _jlw_rows(pt.contiguous(), (n_ct, 32), "pt", dev)
+    out = torch.empty((n_ct, JLW_LIMBS), dtype=torch.int32, device=dev)
+    if n_ct == 0:
+        return out
+    bp = int_limbs(biprime, 64)
+    kl, kneg = _jlw_key_limbs(key)
+    ws = torch.empty(int(lib.fbm_jlw_workspace(n_ct)), dtype=torch.uint8, device=dev)
+    st = _stats(dev)
+    try:
+        _call(lib.fbm_jlw_powmod, _ptr(h), _ptr(pt), n_ct, _np_ptr(bp), _np_ptr(kl), kneg, _ptr(out), _ptr(ws),
+              _ptr(st), _stream())
+        _check_stats_or_defer(st)
+    finally:
+        ws.zero_()  # (|key|, as jlw_encrypt's)
+    return out
+
+
+def jlw_aggregate(cts: torch.Tensor, biprime: int, key: int, tau: int, n_expected: int, total_weight: int,
+                  clip=None, target=None, want_sums: bool = False, ct_offset: int = 0,
+                  factor: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+                  out: Optional[torch.Tensor] = None):
+    """jl_aggregate for a wide biprime: [P, n_ct, 128] int32 ciphertext limbs -> (out [n_out], sums or None);
+    `factor`: the round's jlw_decrypt_factor, or None to compute it here."""
+    dev = cts.device
+    lib = N.load()
+    target = target or SAParameters.TARGET_RANGE
+    P, n_ct, _ = cts.shape
+    es, cr = jl_slot(target, P)
+    n_out = max(0, min(int(n_expected), n_ct * cr))
+    negc, step = dequant_params(clip, target)
+    if total_weight == 0:
+        raise ZeroDivisionError("division by zero")
+    if total_weight < 0 or total_weight > U64_MAX:
+        raise FedbiomedSecaggCrypterError(
+            f"{ErrorNumbers.FB624.value}: total_sample_size must be in [1, 2^64) for the device path")
+    out, odt = _out_tensor(n_out, dev, out_dtype, out)
+    sums = torch.empty((n_out, 2), dtype=torch.int64, device=dev) if want_sums else None
+    if n_ct == 0:
+        return out, sums
+    cts = _jlw_rows(cts.contiguous(), (P, n_ct, JLW_LIMBS), "cts", dev)
+    if factor is None:
+        factor = jlw_decrypt_factor(n_ct, biprime, key, tau, ct_offset=ct_offset, dev=dev)
+    factor = _jlw_rows(factor.contiguous(), (n_ct, JLW_LIMBS), "factor", dev)
+    bp = int_limbs(biprime, 64)
+    chunk = jl_chunk_ct()
+    ws = torch.empty(int(lib.fbm_jlw_workspace(min(n_ct, chunk))), dtype=torch.uint8, device=dev)
+    for k0 in range(0, n_ct, chunk):
+        k1 = min(n_ct, k0 + chunk)
+        part = cts[:, k0:k1].contiguous() if (k0, k1) != (0, n_ct) else cts
+        e0, e1 = k0 * cr, min(n_out, k1 * cr)
+        if e1 <= e0:
+            break
+        st = _stats(dev)
+        _call(lib.fbm_jlw_aggregate_factor_as, _ptr(part), P, k1 - k0, es, cr, e1 - e0, _np_ptr(bp),
+              _ptr(factor[k0:k1]), int(total_weight), negc, step, _ptr(out[e0:e1]), odt,
+              _ptr(sums[e0:e1] if want_sums else None), _ptr(ws), _ptr(st), _stream())
+        _check_stats_or_defer(st)
+    return out, sums
+
+
+# ------------------------------------------------------------------------------------------
 # the JoyeLibert object API (secagg/_jls.py): VES, FDH, ciphertext products, raw decryption
 # ------------------------------------------------------------------------------------------
 def ints_to_u128(values: Sequence[int], dev=None) -> torch.Tensor:

@@ -956,6 +956,108 @@ int fbm_jl_aggregate_factor_as(const uint32_t* cts, int n_parties, uint64_t n_ct
                          out_dtype, sums, agg_ws(workspace, n_ct), stats, s);
 }
 
+// ---- the wide engine (fbm_jl_wide.hip): an odd biprime of 1025 to 2048 bits ----
+// workspace: the call's constants, then n_ct rows of 32 words (the packed plaintexts, or the decrypted ones)
+uint64_t fbm_jlw_workspace(uint64_t n_ct) { return FBM_JLW_CST_BYTES + n_ct * 32 * sizeof(uint32_t); }
+
+static int jlw_ves_checks(int es, int cr) {
+  if (es < 1 || cr < 1 || es > 100 || (int64_t)es * cr > 1024) {
+    set_error("invalid VES parameters es=%d cr=%d", es, cr);
+    return FBM_E_ARG;
+  }
+  return FBM_OK;
+}
+
+// the constants of (biprime, key, round) into the workspace, then the exponentiation kernel
+static int jlw_exp_impl(const uint32_t* Hin, const uint32_t* pt, int neg_pt, uint64_t n_ct, const uint32_t* biprime,
+                        const uint32_t* key, int key_negative, const uint32_t* tau, uint64_t ct_offset, uint32_t* out,
+                        void* workspace, uint32_t* stats, hipStream_t s) {
+  JlwConsts c;
+  int rc = build_jlw_consts(biprime, key, key_negative, tau, ct_offset, c);
+  if (!rc) rc = launch_jlw_setup(c, (uint32_t*)workspace, s);
+  wipe(&c, sizeof(c));
+  if (rc) return rc;
+  return timed(pt ? "jlw_encrypt" : "jlw_factor", s,
+               [&] { return launch_jlw_exp(Hin, pt, neg_pt, n_ct, (const uint32_t*)workspace, out, stats, s); });
+}
+
+int fbm_jlw_encrypt(const void* x, int x_dtype, uint64_t n, double clip, double two_clip, double target_f,
+                    uint64_t target_m1, uint64_t weight, int es, int cr, const uint32_t* biprime, const uint32_t* key,
+                    int key_negative, const uint32_t* tau, uint64_t ct_offset, uint32_t* ct_out, void* workspace,
+                    uint32_t* stats, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  QuantParams qp;
+  uint64_t n_ct;
+  int rc = jl_encrypt_checks(x, x_dtype, n, clip, two_clip, target_f, target_m1, weight, cr, biprime, key, tau, false,
+                             nullptr, ct_out, workspace, stats, s, true, qp, n_ct);
+  if (rc || !n_ct) return rc;
+  if ((rc = jlw_ves_checks(es, cr))) return rc;
+  uint32_t* pt = (uint32_t*)((char*)workspace + FBM_JLW_CST_BYTES);
+  if (x_dtype != FBM_PT &&
+      (rc = timed("jl_pack", s, [&] { return launch_jl_pack(x, x_dtype, n, qp, weight, es, cr, n_ct, pt, stats, s); })))
+    return rc;
+  return jlw_exp_impl(nullptr, x_dtype == FBM_PT ? (const uint32_t*)x : pt, (int64_t)weight < 0 ? 1 : 0, n_ct, biprime,
+                      key, key_negative, tau, ct_offset, ct_out, workspace, stats, s);
+}
+
+int fbm_jlw_decrypt_factor(uint64_t n_ct, const uint32_t* biprime, const uint32_t* key, int key_negative,
+                           const uint32_t* tau, uint64_t ct_offset, uint32_t* factor, void* workspace, uint32_t* stats,
+                           void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc = zero_stats(stats, s);
+  if (rc) return rc;
+  if ((rc = jl_agg_checks(1, n_ct, biprime, 1))) return rc;
+  if (n_ct == 0) return FBM_OK;
+  if (!key || !tau || !factor || !workspace) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  return jlw_exp_impl(nullptr, nullptr, 0, n_ct, biprime, key, key_negative, tau, ct_offset, factor, workspace, stats, s);
+}
+
+int fbm_jlw_powmod(const uint32_t* h, const uint32_t* pt, uint64_t n_ct, const uint32_t* biprime, const uint32_t* key,
+                   int key_negative, uint32_t* out, void* workspace, uint32_t* stats, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc = zero_stats(stats, s);
+  if (rc) return rc;
+  if ((rc = jl_agg_checks(1, n_ct, biprime, 1))) return rc;
+  if (n_ct == 0) return FBM_OK;
+  if (!h || !key || !out || !workspace) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  return jlw_exp_impl(h, pt, 0, n_ct, biprime, key, key_negative, nullptr, 0, out, workspace, stats, s);
+}
+
+int fbm_jlw_aggregate_factor_as(const uint32_t* cts, int n_parties, uint64_t n_ct, int es, int cr, uint64_t n_out,
+                                const uint32_t* biprime, const uint32_t* factor, uint64_t total_weight, double neg_clip,
+                                double step, void* out, int out_dtype, uint64_t* sums, void* workspace, uint32_t* stats,
+                                void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc = check_out_dtype(out_dtype);
+  if (rc) return rc;
+  if ((rc = zero_stats(stats, s))) return rc;
+  if ((rc = jl_agg_checks(n_parties, n_ct, biprime, total_weight))) return rc;
+  if (n_ct == 0) return FBM_OK;
+  if ((rc = jlw_ves_checks(es, cr))) return rc;
+  if (n_out > n_ct * (uint64_t)cr) n_out = n_ct * (uint64_t)cr;
+  if (!cts || !factor || !workspace) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  JlwConsts c;
+  if ((rc = build_jlw_consts(biprime, nullptr, 0, nullptr, 0, c)) || (rc = launch_jlw_setup(c, (uint32_t*)workspace, s)))
+    return rc;
+  uint32_t* xs = (uint32_t*)((char*)workspace + FBM_JLW_CST_BYTES);
+  if ((rc = timed("jlw_combine", s, [&] {
+         return launch_jlw_combine(cts, n_parties, n_ct, factor, (const uint32_t*)workspace, xs, s);
+       })))
+    return rc;
+  return timed("jl_decode", s, [&] {
+    return launch_jl_decode(xs, es, cr, n_out, total_weight, neg_clip, step, out, out_dtype, sums, stats, s);
+  });
+}
+
 // ---- the JoyeLibert object API (fedbiomed_amd/secagg/_jls.py) ----
 int fbm_jl_pack(const void* x, int x_dtype, uint64_t n, int es, int cr, uint32_t* pt, uint32_t* stats, void* stream) {
   hipStream_t s = (hipStream_t)stream;

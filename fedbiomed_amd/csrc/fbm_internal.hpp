@@ -405,6 +405,36 @@ uint64_t wave_resident_ct();
 // compute units of the calling thread's current device (cached per device)
 int device_num_cu();
 
+// ---- the wide engine (fbm_jl_wide.hip): an odd biprime of 1025 to 2048 bits, one ciphertext per wave ----
+// The call's constants, host-built (fbm_setup.hip build_jlw_consts) and copied to the workspace by
+// jlw_setup_kernel.  32-bit words, little-endian; M = N^2 < 2^4096, R = 2^4096.
+struct JlwConsts {
+  uint32_t M[128];
+  uint32_t one[128];   // R mod M
+  uint32_t R2[128];    // R^2 mod M
+  uint32_t NR[128];    // N R mod M: its product with pt is N pt
+  uint32_t N[64];
+  uint32_t Ninv[64];   // N^-1 mod 2^2048 (the exact division by N)
+  uint32_t key[128];   // |key|
+  uint32_t mid[8], tau14_w[16], tau_w[16];  // FDH's message, as JlParams'
+  uint32_t mp;         // -M^-1 mod 2^32
+  int key_bits, key_negative, pad;
+  uint64_t ct_offset;
+};
+static_assert(sizeof(JlwConsts) <= 4096, "passed to jlw_setup_kernel by value");
+#define FBM_JLW_CST_BYTES 4096  // the constants' share of a wide call's workspace
+// biprime: 64 words, odd, 1025..2048 bits (else FBM_E_UNSUPPORTED); key (128 words, |key|) and tau may be NULL
+int build_jlw_consts(const uint32_t* biprime, const uint32_t* key, int key_negative, const uint32_t* tau,
+                     uint64_t ct_offset, JlwConsts& c);
+int launch_jlw_setup(const JlwConsts& c, uint32_t* cst, hipStream_t s);
+// out[k] = h_k^key mod N^2, times N pt_k + 1 when pt != NULL (pt [ct][32]: |pt|, neg_pt its sign); Hin NULL: h_k =
+// FDH.H(((k + ct_offset) << 512) | tau), else the rows Hin [ct][128].  out [ct][128].
+int launch_jlw_exp(const uint32_t* Hin, const uint32_t* pt, int neg_pt, uint64_t n_ct, const uint32_t* cst,
+                   uint32_t* out, uint32_t* stats, hipStream_t s);
+// xout[k] = (prod_u cts[u][k] * factor[k] mod N^2 - 1) / N as the 32-word row jl_decode_kernel reads
+int launch_jlw_combine(const uint32_t* cts, int n_parties, uint64_t n_ct, const uint32_t* factor, const uint32_t* cst,
+                       uint32_t* xout, hipStream_t s);
+
 // ---- host setup (fbm_setup.hip): per-modulus and per-key constants, and their caches ----------
 void wipe(void* p, size_t n);  // a zeroing the optimiser keeps (key-derived temporaries)
 // FDH.H's parameters only (fbm_jl_fdh and the generic engine): the gcd modulus' odd part

@@ -1,7 +1,7 @@
 // fedbiomed_amd -- the C ABI's host setup: the per-modulus and per-key constants the kernels take
 // (Montgomery / N-adic / lane-group constants, the generic engine's GenCtx, FDH's message blocks and
-// midstate, the sliding-window schedules, the short path's and the split exponentiation's constants)
-// and the four bounded caches that keep them between calls.  Nothing here runs on the GPU or depends
+// midstate, the sliding-window schedules, the short path's and the split exponentiation's constants, the wide
+// engine's JlwConsts) and the five bounded caches that keep them between calls.  Nothing here runs on the GPU or depends
 // on FBM_TEST_HOOKS: compiled once and linked into both libraries, like the kernel objects.  The big
 // integers are fbm_bigint.hpp's.
 #include <string.h>
@@ -95,11 +95,19 @@ struct JlSplitCacheEntry {
 };
 static BoundedCache<JlSplitCacheEntry, 32, true> g_split_cache;
 
+// The wide engine's per-biprime constants (build_jlw_consts)
+struct JlwCacheEntry {
+  uint32_t key[64];  // N
+  JlwConsts c;       // (its key, round and offset fields unused)
+};
+static BoundedCache<JlwCacheEntry, 4, false> g_jlw_cache;
+
 void setup_clear_caches() {
   g_short_cache.clear();  // the only ones derived from a key (zeroed)
   g_split_cache.clear();
   g_jp_cache.clear();  // per-N public parameters
   g_rk_cache.clear();
+  g_jlw_cache.clear();
 }
 
 int short_cache_dump(uint32_t* out, int cap_words) {
@@ -389,6 +397,59 @@ void jl_rk_for(const uint32_t* n32, int n_parties, JlRk& r) {  // n32: an odd N 
   memcpy(e.key, key, sizeof(e.key));
   e.rk = r;
   g_rk_cache.insert(e);
+}
+
+// The wide engine's constants (fbm_jl_wide.hip): M = N^2 < 2^4096 and R = 2^4096.  pow2_mod stops at 2048 bits,
+// so R and R^2 are reduced by the long division; the per-biprime part is kept like JlParams'.
+static void put_words(const Big& a, uint32_t* o, int n) {
+  for (int i = 0; i < n; ++i) o[i] = i < (int)a.size() ? a[i] : 0u;
+}
+
+int build_jlw_consts(const uint32_t* biprime, const uint32_t* key, int key_negative, const uint32_t* tau,
+                     uint64_t ct_offset, JlwConsts& c) {
+  Big N(biprime, biprime + 64);
+  const int nb = big_bits(N);
+  if (nb < 1025 || (N[0] & 1u) == 0u) {
+    set_error("the wide engine takes an odd biprime of 1025 to 2048 bits; got %d bits, %s", nb,
+              (N[0] & 1u) ? "odd" : "even");
+    return FBM_E_UNSUPPORTED;
+  }
+  JlwCacheEntry e;
+  if (g_jlw_cache.find(biprime, e, true)) {
+    c = e.c;
+  } else {
+    memset(&c, 0, sizeof(c));
+    const Big M = big_mul(N, N);  // 128 words
+    Big R(129, 0u), q, one, r2, nr;
+    R[128] = 1u;
+    big_divmod(R, M, q, one);
+    big_divmod(big_mul(one, one), M, q, r2);
+    big_divmod(big_mul(N, one), M, q, nr);
+    put_words(M, c.M, 128);
+    put_words(one, c.one, 128);
+    put_words(r2, c.R2, 128);
+    put_words(nr, c.NR, 128);
+    put_words(N, c.N, 64);
+    put_words(inv_mod_pow2(N, 2048), c.Ninv, 64);
+    c.mp = neg_inv<uint32_t>(M[0]);
+    memcpy(e.key, biprime, sizeof(e.key));
+    e.c = c;
+    g_jlw_cache.insert(e);
+  }
+  if (key) {
+    Big K(key, key + 128);
+    c.key_bits = big_bits(K);
+    memcpy(c.key, key, sizeof(c.key));
+    c.key_negative = key_negative ? 1 : 0;
+    wipe(K.data(), K.size() * 4);
+  }
+  JlParams jp;  // (set_tau's fields only)
+  set_tau(jp, tau);
+  memcpy(c.mid, jp.mid, sizeof(c.mid));
+  memcpy(c.tau14_w, jp.tau14_w, sizeof(c.tau14_w));
+  memcpy(c.tau_w, jp.tau_w, sizeof(c.tau_w));
+  c.ct_offset = ct_offset;
+  return FBM_OK;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -259,7 +259,7 @@ class JlStreamAggregation:
                 side = torch.cuda.Stream(device=dev)
                 side.wait_stream(main)
                 with torch.cuda.stream(side), D.capture_checks() as checks:
-                    factor = c.decrypt_factor_tensor(self._round, n_ct, self._key, self._biprime)
+                    factor = c._factor_tensor(self._round, n_ct, self._key, self._biprime)
                 ev = torch.cuda.Event()
                 ev.record(side)
                 self._own = {"factor": factor, "event": ev}
@@ -574,6 +574,14 @@ class SecaggCrypter:
         target_range = target_range or SAParameters.TARGET_RANGE
         _check_weight(weight, jl=True)
         try:
+            if D.jl_wide(biprime):  # an odd biprime of 1025 to 2048 bits: [n_ct, 128] limbs, one launch
+                if defer_exp or factor is not None:
+                    raise FedbiomedSecaggCrypterError(
+                        f"{ErrorNumbers.FB624.value}: a biprime above 1024 bits takes neither `defer_exp` nor "
+                        f"`factor` (the wide engine has no phases)")
+                return D.jlw_encrypt(params, biprime, key, current_round, num_nodes, clip=clipping_range,
+                                     target=target_range, weight=1 if weight is None else weight,
+                                     ct_offset=ct_offset, out=out)
             return D.jl_encrypt(params, biprime, key, current_round, num_nodes, clip=clipping_range,
                                 target=target_range, weight=1 if weight is None else weight, ct_offset=ct_offset,
                                 defer_exp=defer_exp, out=out, factor=factor)
@@ -598,9 +606,10 @@ class SecaggCrypter:
         if not isinstance(key, int):
             raise TypeError("The key should be type of integer")
         target_range = target_range or SAParameters.TARGET_RANGE
-        out, sums = D.jl_aggregate(cts, biprime, key, current_round, num_expected_params, total_sample_size,
-                                   clip=clipping_range, target=target_range, want_sums=want_sums,
-                                   ct_offset=ct_offset, factor=decrypt_factor, out_dtype=out_dtype, out=out)
+        agg = D.jlw_aggregate if D.jl_wide(biprime) else D.jl_aggregate  # wide: [P, n_ct, 128] limbs
+        out, sums = agg(cts, biprime, key, current_round, num_expected_params, total_sample_size,
+                        clip=clipping_range, target=target_range, want_sums=want_sums,
+                        ct_offset=ct_offset, factor=decrypt_factor, out_dtype=out_dtype, out=out)
         return (out, sums) if want_sums else out
 
     def decrypt_factor_tensor(self, current_round: int, num_ciphertexts: int, key: int, biprime: int,
@@ -610,6 +619,19 @@ class SecaggCrypter:
         so the researcher can compute it before they arrive and pass it to aggregate_tensor.
         `phased`: issue constants + FDH only and return a PendingFactor (exponentiate(),
         finish() -> tensor) so a caller can order its kernels against other work."""
+        if D.jl_wide(biprime) and isinstance(key, int):  # [num_ciphertexts, 128] limbs
+            if phased:
+                raise FedbiomedSecaggCrypterError(
+                    f"{ErrorNumbers.FB624.value}: a biprime above 1024 bits takes no `phased` factor")
+            return D.jlw_decrypt_factor(num_ciphertexts, biprime, key, current_round, ct_offset=ct_offset)
+        return self._factor_tensor(current_round, num_ciphertexts, key, biprime, ct_offset, phased)
+
+    @staticmethod
+    def _factor_tensor(current_round, num_ciphertexts, key, biprime, ct_offset=0, phased=False):
+        """decrypt_factor_tensor on the engines for N < 2^1024 only, [num_ciphertexts, 64] limbs: what
+        prepare_encrypt, prepare_aggregate and the streaming aggregation call, whose factors feed 64-limb
+        products.  A biprime above 1024 bits is FB624 here, so those three refuse it (the two prepare_* by
+        returning False) before any exponentiation is issued."""
         if not isinstance(key, int):
             raise TypeError("The key should be type of integer")
         return D.jl_decrypt_factor(num_ciphertexts, biprime, key, current_round, ct_offset=ct_offset,
@@ -646,6 +668,12 @@ class SecaggCrypter:
         dev = D.device()
         x = host.to(dev, non_blocking=True)  # stream-ordered before the encrypt's kernels
         n_ct = (x.numel() + cr - 1) // cr
+        if D.jl_wide(biprime):  # no preparation, no stripes: one call, ints below N^2 < 2^4096
+            with D.deferred_checks():
+                ct = self.encrypt_tensor(num_nodes, current_round, x, key, biprime, clipping_range, weight,
+                                         target_range)
+                out = D.limbs_to_ints_w(ct, D.JLW_LIMBS)
+            return out
         prep = self._take_prepared_encrypt(current_round, num_nodes, key, biprime, target_range, n_ct, dev)
         if prep is not None:  # prepare_encrypt's factor: one product per ciphertext, no exponentiation
             factor, pool = prep
@@ -738,7 +766,7 @@ class SecaggCrypter:
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side), D.capture_checks() as checks:
-                factor = self.decrypt_factor_tensor(current_round, n_ct, key, biprime)
+                factor = self._factor_tensor(current_round, n_ct, key, biprime)
             ev = torch.cuda.Event()
             ev.record(side)
             warm = [D.host_empty((num_params,), torch.float64), D.host_empty((n_ct, 64), torch.int32)]
@@ -820,7 +848,7 @@ class SecaggCrypter:
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side), D.capture_checks() as checks:
-                factors = [self.decrypt_factor_tensor(current_round, c1 - c0, key, biprime, ct_offset=c0)
+                factors = [self._factor_tensor(current_round, c1 - c0, key, biprime, ct_offset=c0)
                            for c0, c1 in stripes]
             ev = torch.cuda.Event()
             ev.record(side)
@@ -877,6 +905,9 @@ class SecaggCrypter:
                 agg.add(p)
             return agg.finish()
         start = time.process_time()
+        if D.jl_wide(biprime) and isinstance(key, int):
+            return self._aggregate_wide(current_round, num_nodes, params, key, biprime, total_sample_size,
+                                        clipping_range, num_expected_params, target_range)
         if len(params) != num_nodes:
             raise FedbiomedSecaggCrypterError(
                 f"{ErrorNumbers.FB624.value}: Num of parameters that are received from nodes "
@@ -928,6 +959,35 @@ class SecaggCrypter:
                                           num_expected_params, target_range, n2, n_ct, stripes, factors, dev, pool)
         logger.info(f"Aggregating {len(params)} parameters from {num_nodes} nodes.")
         logger.debug(f"Aggregation is completed in {round(time.process_time() - start, ndigits=2)} seconds.")
+        return res
+
+    def _aggregate_wide(self, current_round, num_nodes, params, key, biprime, total_sample_size, clipping_range,
+                        num_expected_params, target_range) -> List[float]:
+        """`aggregate` for an odd biprime of 1025 to 2048 bits: the reference's checks in its order, then one
+        factor launch and one combine on [P, n_ct, 128] limbs (no preparation, no stripes)."""
+        if len(params) != num_nodes:
+            raise FedbiomedSecaggCrypterError(
+                f"{ErrorNumbers.FB624.value}: Num of parameters that are received from nodes "
+                f"does not match the number of nodes has been set for the encrypter. There might "
+                f"be some nodes did not answered to training request or num of clients of "
+                "`ParameterEncrypter` has not been set properly before train request.")
+        _check_int_lists(params)
+        if not params:
+            raise FedbiomedSecaggCrypterError(
+                f"{ErrorNumbers.FB624.value}: The aggregation of encrypted parameters "
+                f"is not successful: list_y_u_tau should be a non-empty list.")
+        n_ct = min(len(p) for p in params)  # zip(*list_y_u_tau) truncates (_jls.py:691-693)
+        if n_ct == 0:
+            return []
+        n2 = biprime * biprime
+        nb = 4 * D.JLW_LIMBS
+        rows = np.frombuffer(b"".join((int(c) % n2).to_bytes(nb, "little") for p in params for c in p[:n_ct]),
+                             dtype=np.int32).reshape(len(params), n_ct, D.JLW_LIMBS)
+        with D.deferred_checks():
+            cts = torch.from_numpy(rows.copy()).to(D.device())
+            out = self.aggregate_tensor(current_round, cts, key, biprime, total_sample_size, clipping_range,
+                                        num_expected_params, target_range)
+            res = D.to_host(out).numpy().tolist()
         return res
 
     def _aggregate_stripes(self, current_round, params, key, biprime, total_sample_size, clipping_range,

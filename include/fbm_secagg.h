@@ -163,7 +163,7 @@ int fbm_lom_aggregate_host(const uint64_t* y_host, int n_parties, uint64_t n, ui
  * biprime: HOST, 32 limbs (N, 1 <= N < 2^1024; an odd N >= 3 runs on the Montgomery engines, an
  *          even one and N = 1 on the generic engine, fedbiomed_amd/csrc/fbm_gen.hip -- same results;
  *          at N = 1 every ciphertext is 0 and every decryption is FBM_E_INVERSE, the reference's
- *          invert(delta^2, N^2) modulo 1)
+ *          invert(delta^2, N^2) modulo 1; an odd N of 1025 to 2048 bits: the fbm_jlw_* entry points below)
  * key:     HOST, 64 limbs |sk| (< 2^2048);  key_negative: sign of sk
  * es, cr:  VES slot bits / slots per ciphertext (JoyeLibert vector encoder, _jls.py:104-116)
  * tau:     HOST, FBM_TAU_LIMBS limbs: the round, < 2^8192 (t_k = (k << 512) | tau, FDH.H's input, _jls.py:451-467);
@@ -253,6 +253,37 @@ int fbm_jl_aggregate_factor_as(const uint32_t* cts, int n_parties, uint64_t n_ct
                                const uint32_t* biprime, const uint32_t* factor, uint64_t total_weight, double neg_clip,
                                double step, void* out, int out_dtype, uint64_t* sums, void* workspace, uint32_t* stats,
                                void* stream);
+
+/* ---- Joye-Libert for a biprime of 1025 to 2048 bits: the wide engine (additions, ABI still 7) -------
+ * The entry points above take N < 2^1024 and keep refusing a wider one.  These take an ODD N of 1025 to 2048
+ * bits (anything else is FBM_E_UNSUPPORTED) with the same semantics, status words and reference lines as their
+ * namesakes; only the shapes differ:
+ *   biprime  HOST, 64 limbs          key  HOST, 128 limbs |sk| (< 2^4096), key_negative its sign
+ *   ciphertext and factor rows: 128 uint32 limbs (< N^2 < 2^4096)
+ * The plaintext stays 1024 bits whatever N is (the reference's bits = KEY_SIZE // 2, _secagg_crypter.py:28-43),
+ * so es, cr, the packing and the decode are fbm_jl_encrypt's and fbm_jl_aggregate's.  One ciphertext runs on one
+ * wave64 (fedbiomed_amd/csrc/fbm_jl_wide.hip); a launch is one kernel, there are no phases and no batches.
+ *   workspace: fbm_jlw_workspace(n_ct) bytes, device, 8-byte aligned.  The calls that take a key leave |sk|
+ *   in it beside the modulus' constants (the host copy is wiped): the caller zeroes it before releasing it.
+ * fbm_jlw_encrypt: fbm_jl_encrypt.  fbm_jlw_decrypt_factor: fbm_jl_decrypt_factor.
+ * fbm_jlw_powmod: fbm_jl_powmod -- h: n_ct x 128 limbs (< 2^4096), pt: n_ct x 32 limbs or NULL.
+ * fbm_jlw_aggregate_factor_as: fbm_jl_aggregate_factor_as; x = (v - 1) / N is formed as an exact division, which
+ *   it is for ciphertexts of the scheme (v = 1 mod N); the aggregate with the key is fbm_jlw_decrypt_factor, then
+ *   this.  All rows are 8-byte aligned. */
+uint64_t fbm_jlw_workspace(uint64_t n_ct);
+int fbm_jlw_encrypt(const void* x, int x_dtype, uint64_t n, double clip, double two_clip, double target_f,
+                    uint64_t target_m1, uint64_t weight, int es, int cr, const uint32_t* biprime, const uint32_t* key,
+                    int key_negative, const uint32_t* tau, uint64_t ct_offset, uint32_t* ct_out, void* workspace,
+                    uint32_t* stats, void* stream);
+int fbm_jlw_decrypt_factor(uint64_t n_ct, const uint32_t* biprime, const uint32_t* key, int key_negative,
+                           const uint32_t* tau, uint64_t ct_offset, uint32_t* factor, void* workspace, uint32_t* stats,
+                           void* stream);
+int fbm_jlw_powmod(const uint32_t* h, const uint32_t* pt, uint64_t n_ct, const uint32_t* biprime, const uint32_t* key,
+                   int key_negative, uint32_t* out, void* workspace, uint32_t* stats, void* stream);
+int fbm_jlw_aggregate_factor_as(const uint32_t* cts, int n_parties, uint64_t n_ct, int es, int cr, uint64_t n_out,
+                                const uint32_t* biprime, const uint32_t* factor, uint64_t total_weight, double neg_clip,
+                                double step, void* out, int out_dtype, uint64_t* sums, void* workspace, uint32_t* stats,
+                                void* stream);
 
 /* ---- the JoyeLibert object API (reference _jls.py classes, fedbiomed_amd/secagg/_jls.py) ----
  * fbm_jl_encrypt takes the floating-point x_dtypes FBM_F16 / FBM_BF16 / FBM_F32 / FBM_F64 (quantised), FBM_U64

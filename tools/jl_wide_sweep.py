@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Times of the wide Joye-Libert engine, one JSON line per run: a factor launch at several
+ciphertext counts with a 4090-bit key in both signs (the difference is the negative key's inversion), the
+encrypt rate at --elements, and host Python `pow` per exponentiation as the comparison.  2048-bit
+N = (2^1024 - 105)^2; host clock around the call and a synchronise; one warm-up, then --reps runs.
+
+    python tools/jl_wide_sweep.py [--out profiles/jl_wide_sweep.jsonl] [--reps 3] [--elements 1000000]
+"""
+import argparse
+import json
+import math
+import os
+import random
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jl_wide_sweep.jsonl"))
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--elements", type=int, default=1000000)
+    ap.add_argument("--counts", type=int, nargs="+", default=[1, 256, 2048, 4096])
+    args = ap.parse_args()
+    import torch
+
+    from fedbiomed_amd import _device as D
+    from fedbiomed_amd.secagg import SecaggCrypter
+
+    n = ((1 << 1024) - 105) ** 2
+    key = random.Random(41).getrandbits(4090) | (1 << 4089)
+    dev, sc = D.device(), SecaggCrypter()
+    props = torch.cuda.get_device_properties(dev)
+    rows = [{"what": "device", "name": props.name, "cus": props.multi_processor_count}]
+
+    def timed(fn):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize(dev)
+        return (time.perf_counter() - t0) * 1e3
+
+    for n_ct in args.counts:
+        for k in (-key, key):
+            def run():
+                sc.decrypt_factor_tensor(5, n_ct, k, n)
+            run()
+            for rep in range(args.reps):
+                rows.append({"what": "factor_launch", "n_ct": n_ct, "key_bits": 4090, "key_negative": k < 0,
+                             "n_bits": n.bit_length(), "rep": rep, "ms": timed(run)})
+    x = torch.rand(args.elements, dtype=torch.float64, device=dev) * 4 - 2
+    for rep in range(args.reps + 1):
+        ms = timed(lambda: sc.encrypt_tensor(3, 5, x, key, n))
+        rows.append({"what": "encrypt_tensor", "elements": args.elements, "num_nodes": 3, "rep": rep,
+                     "warmup": rep == 0, "ms": ms, "params_per_s": args.elements / ms * 1e3})
+    h = random.Random(7).getrandbits(4090) % (n * n)
+    while math.gcd(h, n) != 1:
+        h += 1
+    for rep in range(args.reps):
+        t0 = time.perf_counter()
+        pow(h, -key, n * n)
+        rows.append({"what": "host_python_pow", "key_bits": 4090, "key_negative": True, "n_bits": n.bit_length(),
+                     "rep": rep, "ms": (time.perf_counter() - t0) * 1e3})
+    with open(args.out, "w") as f:
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+            print(json.dumps(r))
+
+
+if __name__ == "__main__":
+    main()
