@@ -1340,6 +1340,35 @@ def jl_wide(biprime) -> bool:
         and 1025 <= biprime.bit_length() <= 2048
 
 
+_JLW_ENGINES = {"auto": 0, "wave": 1, "group": 2}
+
+
+class jlw_engine(jl_engine):
+    """jl_engine for the wide family (the test build's fbm_jlw_set_engine): "auto" (the product library's only
+    policy: by launch size), "wave" (csrc/fbm_jl_wide.hip's one ciphertext per wave64: the latency of a small
+    launch) or "group" (four lanes per ciphertext: the throughput of a large one) for the wide
+    calls this thread issues inside.  Results are bit-identical under either."""
+
+    def __init__(self, mode: str):
+        if mode not in _JLW_ENGINES:
+            raise ValueError(f"engine must be one of {sorted(_JLW_ENGINES)}")
+        self._mode, self._prev, self._hooks = _JLW_ENGINES[mode], None, N.test_hooks()
+
+    def __enter__(self):
+        self._hooks.__enter__()
+        self._prev = N.load_test().fbm_jlw_set_engine(self._mode)
+        return self
+
+    def __exit__(self, *exc):
+        N.load_test().fbm_jlw_set_engine(self._prev)
+        return self._hooks.__exit__(*exc)
+
+
+def jlw_engine_for(n_ct: int) -> str:
+    """The engine a wide launch of n_ct ciphertexts takes under this thread's policy (test build)."""
+    return {1: "wave", 2: "group"}[N.load_test().fbm_jlw_engine_for(int(n_ct))]
+
+
 def _jlw_key_limbs(key: int) -> Tuple[np.ndarray, int]:
     if abs(key).bit_length() > 4096:
         raise FedbiomedSecaggCrypterError(f"{ErrorNumbers.FB624.value}: key larger than 4096 bits")

@@ -957,8 +957,11 @@ int fbm_jl_aggregate_factor_as(const uint32_t* cts, int n_parties, uint64_t n_ct
 }
 
 // ---- the wide engine (fbm_jl_wide.hip): an odd biprime of 1025 to 2048 bits ----
-// workspace: the call's constants, then n_ct rows of 32 words (the packed plaintexts, or the decrypted ones)
-uint64_t fbm_jlw_workspace(uint64_t n_ct) { return FBM_JLW_CST_BYTES + n_ct * 32 * sizeof(uint32_t); }
+// workspace: the call's constants, then n_ct rows of 32 words (the packed plaintexts, or the decrypted ones), then the
+// group engine's table of powers where a launch of n_ct takes that engine
+uint64_t fbm_jlw_workspace(uint64_t n_ct) {
+  return FBM_JLW_CST_BYTES + n_ct * 32 * sizeof(uint32_t) + jlw_table_bytes(n_ct);
+}
 
 static int jlw_ves_checks(int es, int cr) {
   if (es < 1 || cr < 1 || es > 100 || (int64_t)es * cr > 1024) {
@@ -1976,6 +1979,16 @@ int fbm_jl_set_engine(int mode) {
 }
 
 int fbm_jl_engine_for(uint64_t n_ct) { return jl_engine_for(n_ct); }
+
+int fbm_jlw_set_engine(int mode) {
+  if (mode != FBM_JLW_ENGINE_AUTO && mode != FBM_JLW_ENGINE_WAVE && mode != FBM_JLW_ENGINE_GROUP) {
+    set_error("fbm_jlw_set_engine: mode must be 0 (auto), 1 (a wave per ciphertext) or 2 (four lanes per ciphertext)");
+    return FBM_E_ARG;
+  }
+  return jlw_engine_set(mode);
+}
+
+int fbm_jlw_engine_for(uint64_t n_ct) { return jlw_engine_for(n_ct); }
 
 int fbm_jl_set_chain(int percall) { return jl_chain_set(percall); }
 

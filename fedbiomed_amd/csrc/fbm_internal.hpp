@@ -420,6 +420,7 @@ struct JlwConsts {
   uint32_t mp;         // -M^-1 mod 2^32
   int key_bits, key_negative, pad;
   uint64_t ct_offset;
+  uint32_t R2g[128];   // the group engine's R'^2 mod M, R' = 2^4104
 };
 static_assert(sizeof(JlwConsts) <= 4096, "passed to jlw_setup_kernel by value");
 #define FBM_JLW_CST_BYTES 4096  // the constants' share of a wide call's workspace
@@ -431,6 +432,15 @@ int launch_jlw_setup(const JlwConsts& c, uint32_t* cst, hipStream_t s);
 // FDH.H(((k + ct_offset) << 512) | tau), else the rows Hin [ct][128].  out [ct][128].
 int launch_jlw_exp(const uint32_t* Hin, const uint32_t* pt, int neg_pt, uint64_t n_ct, const uint32_t* cst,
                    uint32_t* out, uint32_t* stats, hipStream_t s);
+// launch_jlw_exp's engine: the wave engine, or the group engine (four lanes per ciphertext) for large launches; the
+// calling thread's policy (the test build's fbm_jlw_set_engine) and the bytes of the group engine's table, which
+// lies in the call's workspace behind the constants and n_ct rows of 32 words
+#define FBM_JLW_ENGINE_AUTO 0
+#define FBM_JLW_ENGINE_WAVE 1
+#define FBM_JLW_ENGINE_GROUP 2
+int jlw_engine_set(int mode);
+int jlw_engine_for(uint64_t n_ct);
+uint64_t jlw_table_bytes(uint64_t n_ct);
 // xout[k] = (prod_u cts[u][k] * factor[k] mod N^2 - 1) / N as the 32-word row jl_decode_kernel reads
 int launch_jlw_combine(const uint32_t* cts, int n_parties, uint64_t n_ct, const uint32_t* factor, const uint32_t* cst,
                        uint32_t* xout, hipStream_t s);

@@ -397,6 +397,310 @@ __global__ void __launch_bounds__(FBM_JW_BLOCK)
   }
 }
 
+// ---- the group engine: four lanes per ciphertext, 16 ciphertexts per wave64, for large launches ----
+// A residue is 152 limbs of 27 bits, R' = 2^4104 >= 2^8 M: a Montgomery product of two values below 2 M (+ 1) is
+// below 2 M again, so nothing is subtracted between products; one compare-and-subtract ends a ciphertext.
+//   * lane l of a group (l = lane & 3) owns limbs 38 l .. 38 l + 37 of the running value a, of M, and of the
+//     window of 38 accumulator slots; one 64-bit accumulator per slot takes a_j b_i and m_j q_i alike;
+//   * b lives in the group's LDS block (b_i is one word for the group's four lanes); q_i is formed in the
+//     group's lane 0 and broadcast by DPP quad_perm:[0,0,0,0];
+//   * a row retires slot 0 of every lane: its low 27 bits become the top slot of the lane below
+//     (quad_perm:[1,2,3,3], the top lane takes 0), the rest is added into the lane's own next slot.  The window
+//     shift is register renaming: 38 rows are unrolled (slot r of row i is acc[(r + i) % 38]), run four times;
+//   * limbs are lazy between products: below 2^27 + 2^11 (jg_mul's closing carry pass), so a product is below
+//     2^54.001 and a slot, 2 products a row over its 38 rows in a lane plus one carry below 2^35, below 2^61.
+// Bases (FDH, the gcd, a negative key's inverse) stay on the wave layout: jlw_base_kernel writes the canonical base
+// into the output row, jlw_group_kernel raises it to |key| in place.  Exponent: fixed windows of FBM_JG_WIN bits;
+// the powers 1 .. 2^WIN - 1 (and the encrypt's last factor) in the call's workspace, one block per resident wave,
+// [entry][limb][lane] so that a wave's loads coalesce.
+#define FBM_JG_BITS 27
+#define FBM_JG_MASK ((1u << FBM_JG_BITS) - 1u)
+#define FBM_JG_NL 152   // limbs of a residue
+#define FBM_JG_PER 38   // limbs (and accumulator slots) per lane
+#define FBM_JG_STRIDE 153  // LDS words per ciphertext: odd, so the 16 groups' b_i fall into distinct banks
+#define FBM_JG_CT_PER_WAVE 16
+#define FBM_JG_CT_PER_WG (FBM_JG_CT_PER_WAVE * FBM_JW_WAVES)
+#ifndef FBM_JG_WIN
+#define FBM_JG_WIN 4
+#endif
+#define FBM_JG_TABLE ((1 << FBM_JG_WIN) - 1)
+#define FBM_JG_ENTRY_WORDS (FBM_JG_PER * 64)  // one table entry of a wave's 16 ciphertexts
+#define FBM_JG_WAVE_WORDS ((FBM_JG_TABLE + 1) * FBM_JG_ENTRY_WORDS)  // + the row that keeps the last factor
+
+__device__ __forceinline__ uint32_t jg_lane0(uint32_t v) {  // the group's lane 0 to all four
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x00 /* quad_perm:[0,0,0,0] */, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t jg_above(uint32_t v) {  // lane l <- lane l + 1 (the top lane: its own, masked by the caller)
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xF9 /* quad_perm:[1,2,3,3] */, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t jg_below(uint32_t v) {  // lane l <- lane l - 1 (lane 0: its own, masked by the caller)
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x90 /* quad_perm:[0,0,1,2] */, 0xF, 0xF, false);
+}
+// what one lane wrote to the group's LDS block is read by the other three (one wave: program order on the LDS)
+__device__ __forceinline__ void jg_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// limb k (27 bits) of the little-endian words w[0 .. nw)
+__device__ __forceinline__ uint32_t jg_limb(const uint32_t* w, int k, int nw) {
+  const int bit = FBM_JG_BITS * k, wi = bit >> 5;
+  uint64_t v = wi < nw ? w[wi] : 0u;
+  if (wi + 1 < nw) v |= (uint64_t)w[wi + 1] << 32;
+  return (uint32_t)(v >> (bit & 31)) & FBM_JG_MASK;
+}
+
+struct JgLane {
+  uint32_t m[FBM_JG_PER];  // this lane's limbs of M
+  uint32_t mp;             // -M^-1 mod 2^27
+  uint32_t keep_above, keep_below;  // all ones, or zero in the group's top / bottom lane
+};
+
+// rows R .. 37 of a block of 38: slot s of row R is acc[(s + R) % 38], every index a constant (a template recursion
+// rather than a loop: the unroller's size bound refuses 38 rows)
+template <int R>
+__device__ __forceinline__ void jg_rows(uint64_t (&acc)[FBM_JG_PER], const uint32_t (&a)[FBM_JG_PER], const uint32_t* bo,
+                                        const JgLane& k) {
+  if constexpr (R < FBM_JG_PER) {
+    const uint32_t b = bo[R];
+    acc[R] += (uint64_t)a[0] * b;
+    const uint32_t q = jg_lane0(((uint32_t)acc[R] * k.mp) & FBM_JG_MASK);
+#pragma unroll
+    for (int s = 1; s < FBM_JG_PER; ++s) acc[(s + R) % FBM_JG_PER] += (uint64_t)a[s] * b;
+#pragma unroll
+    for (int s = 0; s < FBM_JG_PER; ++s) acc[(s + R) % FBM_JG_PER] += (uint64_t)k.m[s] * q;
+    const uint64_t t = acc[R];  // slot 0 retires (lane 0: its low 27 bits are zero)
+    acc[(R + 1) % FBM_JG_PER] += t >> FBM_JG_BITS;
+    acc[R] = jg_above((uint32_t)t & FBM_JG_MASK) & k.keep_above;
+    jg_rows<R + 1>(acc, a, bo, k);
+  }
+}
+
+// a <- a b 2^-4104 mod M (any representative below 2 M for a b < 2 M (2 M + 1)); b: the group's LDS block
+__device__ __forceinline__ void jg_mul(uint32_t (&a)[FBM_JG_PER], const uint32_t* bl, const JgLane& k) {
+  uint64_t acc[FBM_JG_PER];
+#pragma unroll
+  for (int s = 0; s < FBM_JG_PER; ++s) acc[s] = 0;
+#pragma unroll 1
+  for (int o = 0; o < FBM_JG_NL / FBM_JG_PER; ++o) {
+    // the limbs pass through an empty asm in every block (fbm_mont.hpp's laundering): hoisted out of the loop, their
+    // zero-extensions to 64 bits would each hold a register pair across the product, and spill
+    JgLane kl = k;
+#pragma unroll
+    for (int s = 0; s < FBM_JG_PER; ++s) {
+      asm volatile("" : "+v"(a[s]));
+      asm volatile("" : "+v"(kl.m[s]));
+    }
+    jg_rows<0>(acc, a, bl + o * FBM_JG_PER, kl);
+  }
+  // back to limbs: the lane's own carries, then the carry out of the lane below into limbs 0 and 1 (the top
+  // lane's own carry out is zero: the value is below 2^4104)
+  uint64_t c = 0;
+#pragma unroll
+  for (int s = 0; s < FBM_JG_PER; ++s) {
+    const uint64_t t = acc[s] + c;
+    a[s] = (uint32_t)t & FBM_JG_MASK;
+    c = t >> FBM_JG_BITS;
+  }
+  const uint64_t cin = ((uint64_t)(jg_below((uint32_t)(c >> 32)) & k.keep_below) << 32) |
+                       (jg_below((uint32_t)c) & k.keep_below);
+  const uint64_t t = a[0] + cin;
+  a[0] = (uint32_t)t & FBM_JG_MASK;
+  a[1] += (uint32_t)(t >> FBM_JG_BITS);
+}
+
+__device__ __forceinline__ void jg_put(uint32_t* bl, int l, const uint32_t (&a)[FBM_JG_PER]) {
+#pragma unroll
+  for (int s = 0; s < FBM_JG_PER; ++s) bl[FBM_JG_PER * l + s] = a[s];
+}
+__device__ __forceinline__ void jg_words(uint32_t (&a)[FBM_JG_PER], const uint32_t* w, int nw, int l) {
+#pragma unroll
+  for (int s = 0; s < FBM_JG_PER; ++s) a[s] = w ? jg_limb(w, FBM_JG_PER * l + s, nw) : 0u;
+}
+
+// one lane, on a group's LDS block of lazy limbs: the value (below 2 M) to the canonical limbs of its residue
+__device__ __forceinline__ void jg_canonical(uint32_t* bl, const uint32_t* M) {
+  uint32_t c = 0;
+  for (int i = 0; i < FBM_JG_NL; ++i) {
+    const uint32_t t = bl[i] + c;
+    bl[i] = t & FBM_JG_MASK;
+    c = t >> FBM_JG_BITS;
+  }
+  bool ge = true;
+  for (int i = FBM_JG_NL - 1; i >= 0; --i) {
+    const uint32_t mi = jg_limb(M, i, 128);
+    if (bl[i] != mi) {
+      ge = bl[i] > mi;
+      break;
+    }
+  }
+  if (!ge) return;
+  uint32_t bw = 0;
+  for (int i = 0; i < FBM_JG_NL; ++i) {
+    const uint32_t t = bl[i] - jg_limb(M, i, 128) - bw;
+    bl[i] = t & FBM_JG_MASK;
+    bw = t >> 31;
+  }
+}
+// one lane: x (lazy limbs, below 2 M) to the limbs of 2 M - x + 1 (a negative plaintext's 1 - N |pt|)
+__device__ __forceinline__ void jg_negate_plus1(uint32_t* bl, const uint32_t* M) {
+  int64_t c = 1;
+  for (int i = 0; i < FBM_JG_NL; ++i) {
+    const int64_t t = 2 * (int64_t)jg_limb(M, i, 128) - (int64_t)bl[i] + c;
+    bl[i] = (uint32_t)t & FBM_JG_MASK;
+    c = t >> FBM_JG_BITS;
+  }
+}
+
+__device__ __forceinline__ uint32_t jg_window(const uint32_t* kw, int w) {
+  const int bit = FBM_JG_WIN * w, wi = bit >> 5;
+  uint64_t v = kw[wi];
+  if (wi + 1 < 128) v |= (uint64_t)kw[wi + 1] << 32;
+  return (uint32_t)(v >> (bit & 31)) & ((1u << FBM_JG_WIN) - 1u);
+}
+
+// the canonical base of every ciphertext into its output row, on the wave layout: H(t_k), or the row of Hin reduced
+// mod M; its inverse for a negative non-zero key (none: flagged, a zero row)
+__global__ void __launch_bounds__(FBM_JW_BLOCK, FBM_JW_WGS_PER_CU)
+    jlw_base_kernel(const uint32_t* __restrict__ Hin, uint64_t n_ct, const JlwConsts* __restrict__ c,
+                    uint32_t* __restrict__ out, uint32_t* __restrict__ stats) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const JwMod k = jw_mod(c, lane);
+  const uint64_t unit = lane == 0 ? 1u : 0u;
+  uint32_t err = 0;
+#pragma unroll 1
+  for (uint64_t ct = (uint64_t)blockIdx.x * FBM_JW_WAVES + wv; ct < n_ct; ct += (uint64_t)gridDim.x * FBM_JW_WAVES) {
+    const uint64_t h = Hin ? jw_digit(Hin + ct * 128, lane) : jw_fdh(c, ct + c->ct_offset, lane, err);
+    uint64_t v = jw_mm(jw_mm(h, k.r2, k, lane), unit, k, lane);  // h mod M
+    if (c->key_negative && c->key_bits) {
+      uint64_t gi;
+      if (jw_inverse(v, k, lane, gi, err)) {
+        v = jw_mm(gi, unit, k, lane);
+      } else {
+        err |= FBM_ERR_NOT_INVERTIBLE;
+        v = 0;
+      }
+    }
+    reinterpret_cast<uint64_t*>(out + ct * 128)[lane] = v;
+  }
+  if (err && lane == 0) atomicOr(stats + FBM_STAT_ERRFLAGS, err);
+}
+
+// out[k] <- out[k]^|key| (N pt_k + 1, or 1) mod M over the base rows jlw_base_kernel left.  tbl: FBM_JG_WAVE_WORDS
+// words per wave of the grid.
+__global__ void __launch_bounds__(FBM_JW_BLOCK, FBM_JW_WGS_PER_CU)
+    jlw_group_kernel(const uint32_t* __restrict__ pt, int neg_pt, uint64_t n_ct, const JlwConsts* __restrict__ c,
+                     uint32_t* __restrict__ out, uint32_t* __restrict__ tbl_g) {
+  __shared__ uint32_t b_s[FBM_JW_WAVES * FBM_JG_CT_PER_WAVE * FBM_JG_STRIDE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l = lane & 3;
+  uint32_t* bl = b_s + (wv * FBM_JG_CT_PER_WAVE + (lane >> 2)) * FBM_JG_STRIDE;
+  uint32_t* tbl = tbl_g + ((uint64_t)blockIdx.x * FBM_JW_WAVES + wv) * FBM_JG_WAVE_WORDS + lane;
+  JgLane k;
+  jg_words(k.m, c->M, 128, l);
+  k.mp = c->mp & FBM_JG_MASK;
+  k.keep_above = l == 3 ? 0u : ~0u;
+  k.keep_below = l == 0 ? 0u : ~0u;
+  const int kbits = c->key_bits;
+  uint32_t a[FBM_JG_PER];
+#pragma unroll 1
+  for (uint64_t ct0 = ((uint64_t)blockIdx.x * FBM_JW_WAVES + wv) * FBM_JG_CT_PER_WAVE; ct0 < n_ct;
+       ct0 += (uint64_t)gridDim.x * FBM_JG_CT_PER_WG) {
+    const uint64_t ct = ct0 + (lane >> 2);
+    const bool live = ct < n_ct;
+    if (pt) {  // the last factor N |pt| + 1 (negative: 2 M - N |pt| + 1) into the table block's spare row
+      jg_words(a, c->R2g, 128, l);
+      jg_put(bl, l, a);
+      jg_sync();
+      jg_words(a, c->N, 64, l);
+#pragma unroll 1
+      for (int e = 0; e < 2; ++e) {  // N R' = N R'^2 / R', then N |pt| = |pt| (N R') / R'
+        if (e) {
+          jg_put(bl, l, a);
+          jg_sync();
+          jg_words(a, live ? pt + ct * 32 : nullptr, 32, l);
+        }
+        jg_mul(a, bl, k);
+      }
+      if (neg_pt) {
+        jg_put(bl, l, a);
+        jg_sync();
+        if (l == 0) jg_negate_plus1(bl, c->M);
+        jg_sync();
+#pragma unroll
+        for (int s = 0; s < FBM_JG_PER; ++s) a[s] = bl[FBM_JG_PER * l + s];
+      } else if (l == 0) {
+        a[0] += 1u;
+      }
+#pragma unroll
+      for (int s = 0; s < FBM_JG_PER; ++s) tbl[FBM_JG_TABLE * FBM_JG_ENTRY_WORDS + s * 64] = a[s];
+    }
+    // g R' and its powers: the table's entry t is g^(t + 1) R'.  A zero key: the base is 1, the power its entry 0.
+    jg_words(a, c->R2g, 128, l);
+    jg_put(bl, l, a);
+    jg_sync();
+    jg_words(a, live && kbits ? out + ct * 128 : nullptr, 128, l);
+    if (!kbits && l == 0) a[0] = 1u;
+    const int nt = kbits ? FBM_JG_TABLE : 1;
+#pragma unroll 1
+    for (int t = 0; t < nt; ++t) {
+      jg_mul(a, bl, k);
+#pragma unroll
+      for (int s = 0; s < FBM_JG_PER; ++s) tbl[t * FBM_JG_ENTRY_WORDS + s * 64] = a[s];
+      if (t == 0) {
+        jg_sync();
+        jg_put(bl, l, a);
+        jg_sync();
+      }
+    }
+    int w = kbits ? (kbits - 1) / FBM_JG_WIN : 0;
+    const uint32_t top = kbits ? jw_first(jg_window(c->key, w)) : 1u;  // (it holds the key's top bit)
+#pragma unroll
+    for (int s = 0; s < FBM_JG_PER; ++s) a[s] = tbl[(top - 1u) * FBM_JG_ENTRY_WORDS + s * 64];
+#pragma unroll 1
+    for (--w; w >= 0; --w) {
+      const uint32_t d = jw_first(jg_window(c->key, w));
+      const int np = FBM_JG_WIN + (d ? 1 : 0);
+#pragma unroll 1
+      for (int p = 0; p < np; ++p) {  // WIN squares, then the window's product: a is the table entry, b the value
+        jg_sync();
+        jg_put(bl, l, a);
+        jg_sync();
+        if (p == FBM_JG_WIN) {
+#pragma unroll
+          for (int s = 0; s < FBM_JG_PER; ++s) a[s] = tbl[(d - 1u) * FBM_JG_ENTRY_WORDS + s * 64];
+        }
+        jg_mul(a, bl, k);
+      }
+    }
+    // times the last factor (out of Montgomery form), to the residue, to 32-bit words
+    jg_sync();
+    if (pt) {
+#pragma unroll
+      for (int s = 0; s < FBM_JG_PER; ++s) bl[FBM_JG_PER * l + s] = tbl[FBM_JG_TABLE * FBM_JG_ENTRY_WORDS + s * 64];
+    } else {
+#pragma unroll
+      for (int s = 0; s < FBM_JG_PER; ++s) bl[FBM_JG_PER * l + s] = (l == 0 && s == 0) ? 1u : 0u;
+    }
+    jg_sync();
+    jg_mul(a, bl, k);
+    jg_sync();
+    jg_put(bl, l, a);
+    jg_sync();
+    if (l == 0) jg_canonical(bl, c->M);
+    jg_sync();
+    if (live) {
+#pragma unroll 4
+      for (int j = 0; j < 32; ++j) {
+        const int wd = 4 * j + l, bit = 32 * wd, k0 = bit / FBM_JG_BITS;
+        uint64_t v = bl[k0] | ((uint64_t)bl[k0 + 1] << FBM_JG_BITS);
+        if (k0 + 2 < FBM_JG_NL) v |= (uint64_t)bl[k0 + 2] << (2 * FBM_JG_BITS);
+        out[ct * 128 + wd] = (uint32_t)(v >> (bit - FBM_JG_BITS * k0));
+      }
+    }
+    jg_sync();
+  }
+}
+
 __global__ void jlw_setup_kernel(JlwConsts c, uint32_t* __restrict__ dst) {
   const uint32_t* src = reinterpret_cast<const uint32_t*>(&c);
   for (int i = threadIdx.x; i < (int)(sizeof(JlwConsts) / 4); i += blockDim.x) dst[i] = src[i];
@@ -413,9 +717,47 @@ int launch_jlw_setup(const JlwConsts& c, uint32_t* cst, hipStream_t s) {
   return check_launch("jlw_setup_kernel");
 }
 
+// Engine choice: the wave engine is the latency of a small launch, the group engine the throughput of
+// a large one.  FBM_JLW_GROUP_MIN_CT is the measured crossover (profiles/jl_wide_group_sweep.jsonl).  The policy is per
+// thread, as the narrow engines'; the product library never sets it.
+#define FBM_JLW_GROUP_MIN_CT 8192u
+static thread_local int t_jlw_engine = FBM_JLW_ENGINE_AUTO;
+
+int jlw_engine_set(int mode) {
+  const int prev = t_jlw_engine;
+  t_jlw_engine = mode;
+  return prev;
+}
+
+int jlw_engine_for(uint64_t n_ct) {
+  if (t_jlw_engine != FBM_JLW_ENGINE_AUTO) return t_jlw_engine;
+  return n_ct >= FBM_JLW_GROUP_MIN_CT ? FBM_JLW_ENGINE_GROUP : FBM_JLW_ENGINE_WAVE;
+}
+
+static unsigned jlw_group_grid(uint64_t n_ct) {
+  uint64_t g = (n_ct + FBM_JG_CT_PER_WG - 1) / FBM_JG_CT_PER_WG;
+  const uint64_t gmax = (uint64_t)device_num_cu() * FBM_JW_WGS_PER_CU;
+  return (unsigned)(g > gmax ? gmax : g);
+}
+
+// the group engine's table of powers: one block per wave of the grid, so by min(n_ct, the resident slots)
+uint64_t jlw_table_bytes(uint64_t n_ct) {
+  if (n_ct == 0 || jlw_engine_for(n_ct) != FBM_JLW_ENGINE_GROUP) return 0;
+  return (uint64_t)jlw_group_grid(n_ct) * FBM_JW_WAVES * FBM_JG_WAVE_WORDS * sizeof(uint32_t);
+}
+
 int launch_jlw_exp(const uint32_t* Hin, const uint32_t* pt, int neg_pt, uint64_t n_ct, const uint32_t* cst,
                    uint32_t* out, uint32_t* stats, hipStream_t s) {
   const dim3 grid(jlw_grid(n_ct, FBM_JW_WGS_PER_CU)), block(FBM_JW_BLOCK);
+  if (jlw_engine_for(n_ct) == FBM_JLW_ENGINE_GROUP) {  // the table lies behind the constants and the n_ct plaintext rows
+    uint32_t* tbl = (uint32_t*)((char*)cst + FBM_JLW_CST_BYTES) + n_ct * 32;
+    hipLaunchKernelGGL(jlw_base_kernel, grid, block, 0, s, Hin, n_ct, (const JlwConsts*)cst, out, stats);
+    const int rc = check_launch("jlw_base_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(jlw_group_kernel, dim3(jlw_group_grid(n_ct)), block, 0, s, pt, neg_pt, n_ct, (const JlwConsts*)cst,
+                       out, tbl);
+    return check_launch("jlw_group_kernel");
+  }
   if (pt) {
     hipLaunchKernelGGL(jlw_encrypt_kernel, grid, block, 0, s, Hin, pt, neg_pt, n_ct, (const JlwConsts*)cst, out, stats);
     return check_launch("jlw_encrypt_kernel");

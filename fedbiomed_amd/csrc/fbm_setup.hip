@@ -429,6 +429,11 @@ int build_jlw_consts(const uint32_t* biprime, const uint32_t* key, int key_negat
     put_words(one, c.one, 128);
     put_words(r2, c.R2, 128);
     put_words(nr, c.NR, 128);
+    Big Rg(129, 0u), oneg, r2g;  // the group engine's R' = 2^4104
+    Rg[128] = 1u << 8;
+    big_divmod(Rg, M, q, oneg);
+    big_divmod(big_mul(oneg, oneg), M, q, r2g);
+    put_words(r2g, c.R2g, 128);
     put_words(N, c.N, 64);
     put_words(inv_mod_pow2(N, 2048), c.Ninv, 64);
     c.mp = neg_inv<uint32_t>(M[0]);

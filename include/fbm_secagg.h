@@ -262,8 +262,10 @@ int fbm_jl_aggregate_factor_as(const uint32_t* cts, int n_parties, uint64_t n_ct
  *   ciphertext and factor rows: 128 uint32 limbs (< N^2 < 2^4096)
  * The plaintext stays 1024 bits whatever N is (the reference's bits = KEY_SIZE // 2, _secagg_crypter.py:28-43),
  * so es, cr, the packing and the decode are fbm_jl_encrypt's and fbm_jl_aggregate's.  One ciphertext runs on one
- * wave64 (fedbiomed_amd/csrc/fbm_jl_wide.hip); a launch is one kernel, there are no phases and no batches.
- *   workspace: fbm_jlw_workspace(n_ct) bytes, device, 8-byte aligned.  The calls that take a key leave |sk|
+ * wave64, or from 8192 ciphertexts a launch on four lanes (fedbiomed_amd/csrc/fbm_jl_wide.hip); there are no
+ * phases and no batches.
+ *   workspace: fbm_jlw_workspace(n_ct) bytes, device, 8-byte aligned (for a large launch it includes the table of
+ *   the bases' powers: up to 160 KB per 16 ciphertexts resident on the device).  The calls that take a key leave |sk|
  *   in it beside the modulus' constants (the host copy is wiped): the caller zeroes it before releasing it.
  * fbm_jlw_encrypt: fbm_jl_encrypt.  fbm_jlw_decrypt_factor: fbm_jl_decrypt_factor.
  * fbm_jlw_powmod: fbm_jl_powmod -- h: n_ct x 128 limbs (< 2^4096), pt: n_ct x 32 limbs or NULL.

@@ -60,6 +60,14 @@ int fbm_jl_triple_mads(int square);
  * FBM_E_ARG).  * fbm_jl_engine_for: the engine a launch of n_ct ciphertexts takes under the policy (1-4). */
 int fbm_jl_set_engine(int mode);
 int fbm_jl_engine_for(uint64_t n_ct);
+/* The wide family's exponentiation engine (fbm_jlw_encrypt, fbm_jlw_decrypt_factor, fbm_jlw_powmod) for the CALLING
+ * THREAD: 0 = auto (the default: the wave engine, one ciphertext per wave64, below the measured crossover and the
+ * group engine, four lanes per ciphertext, from it on), 1 = wave, 2 = group.  Results are
+ * bit-identical either way; fbm_jlw_workspace follows the policy (the group engine keeps its table of powers in the
+ * workspace).  Returns the previous policy (or FBM_E_ARG).  fbm_jlw_engine_for: the engine (1 or 2) a launch of n_ct
+ * ciphertexts takes under the policy. */
+int fbm_jlw_set_engine(int mode);
+int fbm_jlw_engine_for(uint64_t n_ct);
 /* The exponentiation's short path (a binary chain with the 9-row short-base product, taken for a
  * one-digest FDH h and N > 2^262: DESIGN.md 5.3) on (1, the default) or off (0: every wave runs the
  * sliding-window table path -- an A/B and test switch; results are bit-identical).  Returns the

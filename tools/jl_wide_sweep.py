@@ -5,6 +5,12 @@ encrypt rate at --elements, and host Python `pow` per exponentiation as the comp
 N = (2^1024 - 105)^2; host clock around the call and a synchronise; one warm-up, then --reps runs.
 
     python tools/jl_wide_sweep.py [--out profiles/jl_wide_sweep.jsonl] [--reps 3] [--elements 1000000]
+
+--engine wave group: the factor launch (negative key) and encrypt_tensor under each forced engine of
+the test build instead, the engines alternating within a repetition, every row with its "engine":
+
+    python tools/jl_wide_sweep.py --engine wave group --out profiles/jl_wide_group_sweep.jsonl \
+        --counts 256 1024 2048 4096 8192 16384 31250 65536
 """
 import argparse
 import json
@@ -24,6 +30,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--elements", type=int, default=1000000)
     ap.add_argument("--counts", type=int, nargs="+", default=[1, 256, 2048, 4096])
+    ap.add_argument("--engine", nargs="+", choices=["auto", "wave", "group"], default=None)
     args = ap.parse_args()
     import torch
 
@@ -43,7 +50,18 @@ def main():
         torch.cuda.synchronize(dev)
         return (time.perf_counter() - t0) * 1e3
 
-    for n_ct in args.counts:
+    for n_ct in args.counts if args.engine else []:
+        def run_engine(eng):
+            with D.jlw_engine(eng):
+                sc.decrypt_factor_tensor(5, n_ct, -key, n)
+        for eng in args.engine:
+            run_engine(eng)
+        for rep in range(args.reps):
+            for eng in args.engine:
+                rows.append({"what": "factor_launch", "engine": eng, "n_ct": n_ct, "key_bits": 4090,
+                             "key_negative": True, "n_bits": n.bit_length(), "rep": rep,
+                             "ms": timed(lambda: run_engine(eng))})
+    for n_ct in [] if args.engine else args.counts:
         for k in (-key, key):
             def run():
                 sc.decrypt_factor_tensor(5, n_ct, k, n)
@@ -53,9 +71,11 @@ def main():
                              "n_bits": n.bit_length(), "rep": rep, "ms": timed(run)})
     x = torch.rand(args.elements, dtype=torch.float64, device=dev) * 4 - 2
     for rep in range(args.reps + 1):
-        ms = timed(lambda: sc.encrypt_tensor(3, 5, x, key, n))
-        rows.append({"what": "encrypt_tensor", "elements": args.elements, "num_nodes": 3, "rep": rep,
-                     "warmup": rep == 0, "ms": ms, "params_per_s": args.elements / ms * 1e3})
+        for eng in args.engine or ["auto"]:
+            with D.jlw_engine(eng):
+                ms = timed(lambda: sc.encrypt_tensor(3, 5, x, key, n))
+            rows.append({"what": "encrypt_tensor", "engine": eng, "elements": args.elements, "num_nodes": 3, "rep": rep,
+                         "warmup": rep == 0, "ms": ms, "params_per_s": args.elements / ms * 1e3})
     h = random.Random(7).getrandbits(4090) % (n * n)
     while math.gcd(h, n) != 1:
         h += 1
