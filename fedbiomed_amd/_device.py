@@ -1383,8 +1383,12 @@ def _jlw_rows(t: torch.Tensor, shape, what: str, dev) -> torch.Tensor:
 
 
 def jlw_encrypt(x: torch.Tensor, biprime: int, key: int, tau: int, n_users: int, clip=None, target=None,
-                weight: int = 1, ct_offset: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """jl_encrypt for a wide biprime: one party's ciphertexts as int32 [n_ct, 128] limbs."""
+                weight: int = 1, ct_offset: int = 0, out: Optional[torch.Tensor] = None,
+                factor: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """jl_encrypt for a wide biprime: one party's ciphertexts as int32 [n_ct, 128] limbs.  `factor`: this party's
+    jlw_decrypt_factor of these ciphertexts (its key, round and ct_offset) computed ahead: the encrypt is then
+    (N pt + 1) F mod N^2 (fbm_jlw_encrypt_with: two products a ciphertext), bit for bit the exponentiation's; key,
+    tau and ct_offset are not read."""
     dev = x.device
     lib = N.load()
     target = target or SAParameters.TARGET_RANGE
@@ -1400,8 +1404,22 @@ def jlw_encrypt(x: torch.Tensor, biprime: int, key: int, tau: int, n_users: int,
     if n_ct == 0:
         return ct
     bp = int_limbs(biprime, 64)
-    kl, kneg = _jlw_key_limbs(key)
     chunk = jl_chunk_ct()
+    if factor is not None:
+        if (factor.dtype != torch.int32 or tuple(factor.shape) != (n_ct, JLW_LIMBS) or not factor.is_contiguous()
+                or factor.device != dev):
+            raise ValueError(f"factor must be the contiguous int32 ({n_ct}, {JLW_LIMBS}) H(t_k)^key of these "
+                             f"ciphertexts on {dev}")
+        ws = torch.empty(int(lib.fbm_jlw_seal_workspace(min(n_ct, chunk))), dtype=torch.uint8, device=dev)
+        for k0 in range(0, n_ct, chunk):
+            k1 = min(n_ct, k0 + chunk)
+            xs = x[k0 * cr:min(n, k1 * cr)]
+            st = _stats(dev)
+            _call(lib.fbm_jlw_encrypt_with, _ptr(xs), xdt, xs.numel(), c, c2, tf, tm1, int(weight) & U64_MAX, es, cr,
+                  _np_ptr(bp), _ptr(factor[k0:k1]), _ptr(ct[k0:k1]), _ptr(ws), _ptr(st), _stream())
+            _check_stats_or_defer(st)
+        return ct
+    kl, kneg = _jlw_key_limbs(key)
     ws = torch.empty(int(lib.fbm_jlw_workspace(min(n_ct, chunk))), dtype=torch.uint8, device=dev)
     try:
         for k0 in range(0, n_ct, chunk):
@@ -1469,14 +1487,15 @@ def jlw_powmod(h: torch.Tensor, biprime: int, key: int, pt: Optional[torch.Tenso
 def jlw_aggregate(cts: torch.Tensor, biprime: int, key: int, tau: int, n_expected: int, total_weight: int,
                   clip=None, target=None, want_sums: bool = False, ct_offset: int = 0,
                   factor: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
-                  out: Optional[torch.Tensor] = None):
+                  out: Optional[torch.Tensor] = None, slot: Optional[Tuple[int, int]] = None):
     """jl_aggregate for a wide biprime: [P, n_ct, 128] int32 ciphertext limbs -> (out [n_out], sums or None);
-    `factor`: the round's jlw_decrypt_factor, or None to compute it here."""
+    `factor`: the round's jlw_decrypt_factor, or None to compute it here.  `slot`: the packing's (element_size,
+    comp_ratio) when P is not the party count (jlw_fold's accumulator: P = 1, the slot of the parties folded)."""
     dev = cts.device
     lib = N.load()
     target = target or SAParameters.TARGET_RANGE
     P, n_ct, _ = cts.shape
-    es, cr = jl_slot(target, P)
+    es, cr = slot if slot else jl_slot(target, P)
     n_out = max(0, min(int(n_expected), n_ct * cr))
     negc, step = dequant_params(clip, target)
     if total_weight == 0:
@@ -1770,6 +1789,33 @@ def jl_fold(acc: torch.Tensor, rows: torch.Tensor, biprime: int, seed_ops: int =
     rows = _on_current_stream(rows.contiguous())
     ws = torch.empty(int(lib.fbm_jl_aggregate_workspace(1)), dtype=torch.uint8, device=acc.device)
     _call(lib.fbm_jl_fold, _ptr(acc), _ptr(rows), k, n_ct, _np_ptr(bp), int(seed_ops), _ptr(ws), _stream())
+    return acc
+
+
+def jlw_fold(acc: torch.Tensor, rows: torch.Tensor, biprime: int, seed_ops: int = 0) -> torch.Tensor:
+    """jl_fold for a wide biprime (fbm_jlw_fold): acc[c] <- (1 if seed_ops > 0 else acc[c]) * prod_j rows[j][c]
+    mod N^2 in place, on the current stream.  acc: int32 [n_ct, 128], contiguous; rows: int32 [n_ct, 128] or
+    [k, n_ct, 128], any values below 2^4096.  acc is the canonical product of the rows folded so far after every
+    call (two products a row: no R-power bookkeeping); seed_ops > 0 starts it, 0 continues it."""
+    if rows.dim() == 2:
+        rows = rows[None]
+    k, n_ct, _ = rows.shape
+    if acc.dtype != torch.int32 or rows.dtype != torch.int32 or tuple(acc.shape) != (n_ct, JLW_LIMBS) or \
+            rows.shape[2] != JLW_LIMBS or not acc.is_contiguous() or acc.device != rows.device:
+        raise ValueError(f"jlw_fold takes a contiguous int32 [n_ct, {JLW_LIMBS}] accumulator and int32 "
+                         f"[k, n_ct, {JLW_LIMBS}] rows on its device")
+    bp = int_limbs(biprime, 64)
+    if n_ct == 0 and k >= 1:
+        return acc
+    lib = N.load()
+    rows = _on_current_stream(rows.contiguous())
+    ws = torch.empty(int(lib.fbm_jlw_seal_workspace(0)), dtype=torch.uint8, device=acc.device)
+    chunk = jl_chunk_ct()
+    for k0 in range(0, n_ct, chunk):  # (as jlw_aggregate loops: at most FBM_JL_MAX_CT per library call)
+        k1 = min(n_ct, k0 + chunk)
+        part = rows[:, k0:k1].contiguous() if (k0, k1) != (0, n_ct) else rows
+        _call(lib.fbm_jlw_fold, _ptr(acc[k0:k1]), _ptr(part), k, k1 - k0, _np_ptr(bp), int(seed_ops), _ptr(ws),
+              _stream())
     return acc
 
 

@@ -127,6 +127,10 @@ SIGNATURES = {
     "fbm_jlw_powmod": (c_int, [c_vp, c_vp, c_u64, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "fbm_jlw_aggregate_factor_as": (c_int, [c_vp, c_int, c_u64, c_int, c_int, c_u64, c_vp, c_vp, c_u64, c_dbl, c_dbl,
                                             c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "fbm_jlw_seal_workspace": (c_u64, [c_u64]),
+    "fbm_jlw_encrypt_with": (c_int, [c_vp, c_int, c_u64, c_dbl, c_dbl, c_dbl, c_u64, c_u64, c_int, c_int, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp]),
+    "fbm_jlw_fold": (c_int, [c_vp, c_vp, c_int, c_u64, c_vp, c_int, c_vp, c_vp]),
     "fbm_jl_pack": (c_int, [c_vp, c_int, c_u64, c_int, c_int, c_vp, c_vp, c_vp]),
     "fbm_jl_unpack": (c_int, [c_vp, c_u64, c_int, c_int, c_u64, c_vp, c_vp]),
     "fbm_jl_fdh": (c_int, [c_u64, c_vp, c_int, c_vp, c_u64, c_vp, c_vp, c_vp]),

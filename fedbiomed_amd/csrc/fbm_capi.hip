@@ -1032,6 +1032,61 @@ int fbm_jlw_powmod(const uint32_t* h, const uint32_t* pt, uint64_t n_ct, const u
   return jlw_exp_impl(h, pt, 0, n_ct, biprime, key, key_negative, nullptr, 0, out, workspace, stats, s);
 }
 
+// the encrypt from a factor computed ahead (jlw_seal_kernel) and the streaming product (jlw_fold_kernel): no key,
+// so the workspace holds the modulus' constants and the packed plaintext rows only, never the group engine's table
+uint64_t fbm_jlw_seal_workspace(uint64_t n_ct) { return FBM_JLW_CST_BYTES + n_ct * 32 * sizeof(uint32_t); }
+
+int fbm_jlw_encrypt_with(const void* x, int x_dtype, uint64_t n, double clip, double two_clip, double target_f,
+                         uint64_t target_m1, uint64_t weight, int es, int cr, const uint32_t* biprime,
+                         const uint32_t* factor, uint32_t* ct_out, void* workspace, uint32_t* stats, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  QuantParams qp;
+  uint64_t n_ct;
+  int rc = jl_encrypt_checks(x, x_dtype, n, clip, two_clip, target_f, target_m1, weight, cr, biprime, nullptr, nullptr,
+                             true, factor, ct_out, workspace, stats, s, true, qp, n_ct);
+  if (rc || !n_ct) return rc;
+  if ((rc = jlw_ves_checks(es, cr))) return rc;
+  {  // a wave reads its factor row and then writes its output row: the same rows may not lie at different places
+    const uintptr_t o0 = (uintptr_t)ct_out, o1 = o0 + n_ct * 512, f0 = (uintptr_t)factor, f1 = f0 + n_ct * 512;
+    if (o0 < f1 && f0 < o1) {
+      set_error("fbm_jlw_encrypt_with: ct_out must not overlap factor");
+      return FBM_E_ARG;
+    }
+  }
+  JlwConsts c;
+  if ((rc = build_jlw_consts(biprime, nullptr, 0, nullptr, 0, c)) || (rc = launch_jlw_setup(c, (uint32_t*)workspace, s)))
+    return rc;
+  uint32_t* pt = (uint32_t*)((char*)workspace + FBM_JLW_CST_BYTES);
+  if (x_dtype != FBM_PT &&
+      (rc = timed("jl_pack", s, [&] { return launch_jl_pack(x, x_dtype, n, qp, weight, es, cr, n_ct, pt, stats, s); })))
+    return rc;
+  return timed("jlw_seal", s, [&] {
+    return launch_jlw_seal(x_dtype == FBM_PT ? (const uint32_t*)x : pt, (int64_t)weight < 0 ? 1 : 0, n_ct, factor,
+                           (const uint32_t*)workspace, ct_out, s);
+  });
+}
+
+int fbm_jlw_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, const uint32_t* biprime, int seed_ops,
+                 void* workspace, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = jl_agg_checks(k, n_ct, biprime, 1))) return rc;
+  if (seed_ops < 0 || (seed_ops > 0 && k > seed_ops)) {
+    set_error("fbm_jlw_fold: %d rows into an accumulator seeded for %d", k, seed_ops);
+    return FBM_E_ARG;
+  }
+  if (n_ct == 0) return FBM_OK;
+  if (!acc || !rows || !workspace) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  JlwConsts c;
+  if ((rc = build_jlw_consts(biprime, nullptr, 0, nullptr, 0, c)) || (rc = launch_jlw_setup(c, (uint32_t*)workspace, s)))
+    return rc;
+  return timed("jlw_fold", s,
+               [&] { return launch_jlw_fold(acc, rows, k, n_ct, seed_ops > 0, (const uint32_t*)workspace, s); });
+}
+
 int fbm_jlw_aggregate_factor_as(const uint32_t* cts, int n_parties, uint64_t n_ct, int es, int cr, uint64_t n_out,
                                 const uint32_t* biprime, const uint32_t* factor, uint64_t total_weight, double neg_clip,
                                 double step, void* out, int out_dtype, uint64_t* sums, void* workspace, uint32_t* stats,

@@ -444,6 +444,12 @@ uint64_t jlw_table_bytes(uint64_t n_ct);
 // xout[k] = (prod_u cts[u][k] * factor[k] mod N^2 - 1) / N as the 32-word row jl_decode_kernel reads
 int launch_jlw_combine(const uint32_t* cts, int n_parties, uint64_t n_ct, const uint32_t* factor, const uint32_t* cst,
                        uint32_t* xout, hipStream_t s);
+// out[k] = (N pt_k + 1) factor[k] mod N^2: launch_jlw_exp's ciphertexts from the factor rows H(t_k)^key [ct][128]
+int launch_jlw_seal(const uint32_t* pt, int neg_pt, uint64_t n_ct, const uint32_t* factor, const uint32_t* cst,
+                    uint32_t* out, hipStream_t s);
+// acc[k] <- (seed ? 1 : acc[k]) prod_j rows[j][k] mod N^2 in place; rows [k][ct][128], acc [ct][128], canonical after
+int launch_jlw_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, bool seed, const uint32_t* cst,
+                    hipStream_t s);
 
 // ---- host setup (fbm_setup.hip): per-modulus and per-key constants, and their caches ----------
 void wipe(void* p, size_t n);  // a zeroing the optimiser keeps (key-derived temporaries)

@@ -397,6 +397,88 @@ __global__ void __launch_bounds__(FBM_JW_BLOCK)
   }
 }
 
+// ---- the encrypt from a factor computed ahead, and the streaming product ----
+// lane j <- lane j - 16 of a 64-bit value (lanes 0..15: lane j + 48's, dropped by the caller)
+__device__ __forceinline__ uint64_t jw_from16(uint64_t v, int lane) {
+  const int src = (lane - 16) & 63;
+  return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src);
+}
+
+// N p as an integer, for p < 2^1024 (its digits in lanes 0..15, zeros above) and N < 2^2048 (n: lanes 0..31, zeros
+// above): jw_mullo's scan by the 32 words of p, without a modulus, kept whole.  Row i retires word i of the product
+// (into lane i / 2); what the accumulators hold after the last row are the words 32 and up, so they move up by 16
+// lanes.  N p < 2^3072: nothing reaches digit 48.
+__device__ __forceinline__ uint64_t jw_npt(uint64_t n, uint64_t p, int lane) {
+  const uint32_t n0 = (uint32_t)n, n1 = (uint32_t)(n >> 32), p0 = (uint32_t)p, p1 = (uint32_t)(p >> 32);
+  uint64_t U0 = 0, U1 = 0, x = 0;
+#pragma unroll 2
+  for (int i = 0; i < 16; ++i) {
+#pragma unroll
+    for (int hw = 0; hw < 2; ++hw) {
+      const uint32_t bi = jw_lane(hw ? p1 : p0, i);
+      U0 += (uint64_t)n0 * bi;
+      U1 += (uint64_t)n1 * bi;
+      const uint32_t w = jw_first((uint32_t)U0), u0 = (uint32_t)U0;
+      if (lane == i) x |= (uint64_t)w << (32 * hw);
+      U0 = (U0 >> 32) + (uint32_t)U1;
+      U1 = (U1 >> 32) + jw_up32(u0);
+    }
+  }
+  const jw_u128 s = (jw_u128)U0 + ((jw_u128)U1 << 32);  // words 32 + 2 j and up, of lane j
+  const uint64_t L = jw_from16((uint64_t)s, lane), H = jw_from16((uint64_t)(s >> 64), lane);
+  uint32_t ov;
+  return jw_resolve(lane < 16 ? x : L, lane < 16 ? 0ull : H, lane, ov);
+}
+
+// out[k] = (1 + N pt_k) F_k mod M from the factor rows F (any value below 2^4096; jlw_factor_kernel's H(t_k)^key):
+// bit for bit jlw_encrypt_kernel's ciphertext, at two products.  N >= 2^1024 > |pt| gives 1 + N |pt| <= M - N + 1:
+// the last factor G needs no reduction, so it is formed by jw_npt's 32 plain rows; a negative plaintext takes
+// jw_exp_body's signed pass.  No key, no table.
+__global__ void __launch_bounds__(FBM_JW_BLOCK)
+    jlw_seal_kernel(const uint32_t* __restrict__ pt, int neg_pt, uint64_t n_ct, const uint32_t* __restrict__ factor,
+                    const JlwConsts* __restrict__ c, uint32_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const JwMod k = jw_mod(c, lane);
+  const uint64_t n = jw_digit_lo(c->N, lane);
+#pragma unroll 1
+  for (uint64_t ct = (uint64_t)blockIdx.x * FBM_JW_WAVES + wv; ct < n_ct; ct += (uint64_t)gridDim.x * FBM_JW_WAVES) {
+    const uint64_t f = jw_digit(factor + ct * 128, lane);  // (under way behind G's rows)
+    const uint64_t np = jw_npt(n, lane < 16 ? jw_digit(pt + ct * 32, lane) : 0ull, lane);
+    uint64_t g;
+    uint32_t ov;
+    if (neg_pt && __ballot(np != 0) != 0) {
+      const jw_u128 s = (jw_u128)k.m + ~np + (lane == 0 ? 2u : 0u);  // M - N |pt| + 1
+      g = jw_resolve((uint64_t)s, (uint64_t)(s >> 64), lane, ov);
+    } else {
+      const jw_u128 s = (jw_u128)np + (lane == 0 ? 1u : 0u);
+      g = jw_resolve((uint64_t)s, (uint64_t)(s >> 64), lane, ov);
+    }
+    reinterpret_cast<uint64_t*>(out + ct * 128)[lane] = jw_mm(jw_mm(f, k.r2, k, lane), g, k, lane);
+  }
+}
+
+// acc[k] <- (seed ? 1 : acc[k]) prod_j rows[j][k] mod M in place, rows [n_rows][n_ct][128] of any values below
+// 2^4096: two products a row (the row to Montgomery form, then into the accumulator), so acc is the plain canonical
+// product after every call.  A lane reads its digit of the next row before the current row's products run.
+__global__ void __launch_bounds__(FBM_JW_BLOCK)
+    jlw_fold_kernel(uint32_t* __restrict__ acc, const uint32_t* __restrict__ rows, int n_rows, uint64_t n_ct, int seed,
+                    const JlwConsts* __restrict__ c) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const JwMod k = jw_mod(c, lane);
+#pragma unroll 1
+  for (uint64_t ct = (uint64_t)blockIdx.x * FBM_JW_WAVES + wv; ct < n_ct; ct += (uint64_t)gridDim.x * FBM_JW_WAVES) {
+    uint64_t next = jw_digit(rows + ct * 128, lane);
+    uint64_t a = seed ? (lane == 0 ? 1ull : 0ull) : jw_digit(acc + ct * 128, lane);
+#pragma unroll 1
+    for (int j = 0; j < n_rows; ++j) {
+      const uint64_t row = next;
+      if (j + 1 < n_rows) next = jw_digit(rows + ((uint64_t)(j + 1) * n_ct + ct) * 128, lane);
+      a = jw_mm(a, jw_mm(row, k.r2, k, lane), k, lane);
+    }
+    reinterpret_cast<uint64_t*>(acc + ct * 128)[lane] = a;
+  }
+}
+
 // ---- the group engine: four lanes per ciphertext, 16 ciphertexts per wave64, for large launches ----
 // A residue is 152 limbs of 27 bits, R' = 2^4104 >= 2^8 M: a Montgomery product of two values below 2 M (+ 1) is
 // below 2 M again, so nothing is subtracted between products; one compare-and-subtract ends a ciphertext.
@@ -771,6 +853,20 @@ int launch_jlw_combine(const uint32_t* cts, int n_parties, uint64_t n_ct, const 
   hipLaunchKernelGGL(jlw_combine_kernel, dim3(jlw_grid(n_ct, 8)), dim3(FBM_JW_BLOCK), 0, s, cts, n_parties, n_ct, factor,
                      (const JlwConsts*)cst, xout);
   return check_launch("jlw_combine_kernel");
+}
+
+int launch_jlw_seal(const uint32_t* pt, int neg_pt, uint64_t n_ct, const uint32_t* factor, const uint32_t* cst,
+                    uint32_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(jlw_seal_kernel, dim3(jlw_grid(n_ct, 8)), dim3(FBM_JW_BLOCK), 0, s, pt, neg_pt, n_ct, factor,
+                     (const JlwConsts*)cst, out);
+  return check_launch("jlw_seal_kernel");
+}
+
+int launch_jlw_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, bool seed, const uint32_t* cst,
+                    hipStream_t s) {
+  hipLaunchKernelGGL(jlw_fold_kernel, dim3(jlw_grid(n_ct, 8)), dim3(FBM_JW_BLOCK), 0, s, acc, rows, k, n_ct, seed ? 1 : 0,
+                     (const JlwConsts*)cst);
+  return check_launch("jlw_fold_kernel");
 }
 
 }  // namespace fbm

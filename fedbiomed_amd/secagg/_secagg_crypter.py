@@ -562,7 +562,8 @@ class SecaggCrypter:
         tensor encrypts to the ciphertexts of `params.double()`, with no upcast copy made.
         `factor`: this party's H(t_k)^key of these ciphertexts computed ahead (`decrypt_factor_tensor` with
         the party's key, round and ct_offset; `prepare_encrypt` issues it for the list API): the encrypt is
-        then one product per ciphertext instead of an exponentiation, with the same ciphertexts.
+        then one product per ciphertext instead of an exponentiation, with the same ciphertexts (a biprime
+        above 1024 bits: int32 [n_ct, 128] rows, two products; `ct_offset` then belongs to the factor's call).
         `ct_offset`: global index of this shard's first ciphertext (element-range sharding).
         `out`: an int32 [n_ct, 64] destination (e.g. this party's row of the [P, n_ct, 64] block
         aggregate_tensor takes), as SecaggLomCrypter.encrypt_tensor's.
@@ -575,13 +576,13 @@ class SecaggCrypter:
         _check_weight(weight, jl=True)
         try:
             if D.jl_wide(biprime):  # an odd biprime of 1025 to 2048 bits: [n_ct, 128] limbs, one launch
-                if defer_exp or factor is not None:
+                if defer_exp:
                     raise FedbiomedSecaggCrypterError(
-                        f"{ErrorNumbers.FB624.value}: a biprime above 1024 bits takes neither `defer_exp` nor "
-                        f"`factor` (the wide engine has no phases)")
+                        f"{ErrorNumbers.FB624.value}: a biprime above 1024 bits takes no `defer_exp` (the wide "
+                        f"engine has no phases; pass the `factor` computed ahead instead)")
                 return D.jlw_encrypt(params, biprime, key, current_round, num_nodes, clip=clipping_range,
                                      target=target_range, weight=1 if weight is None else weight,
-                                     ct_offset=ct_offset, out=out)
+                                     ct_offset=ct_offset, out=out, factor=factor)
             return D.jl_encrypt(params, biprime, key, current_round, num_nodes, clip=clipping_range,
                                 target=target_range, weight=1 if weight is None else weight, ct_offset=ct_offset,
                                 defer_exp=defer_exp, out=out, factor=factor)

@@ -271,8 +271,30 @@ int fbm_jl_aggregate_factor_as(const uint32_t* cts, int n_parties, uint64_t n_ct
  * fbm_jlw_powmod: fbm_jl_powmod -- h: n_ct x 128 limbs (< 2^4096), pt: n_ct x 32 limbs or NULL.
  * fbm_jlw_aggregate_factor_as: fbm_jl_aggregate_factor_as; x = (v - 1) / N is formed as an exact division, which
  *   it is for ciphertexts of the scheme (v = 1 mod N); the aggregate with the key is fbm_jlw_decrypt_factor, then
- *   this.  All rows are 8-byte aligned. */
+ *   this.  All rows are 8-byte aligned.
+ * fbm_jlw_encrypt_with: fbm_jl_encrypt_factor -- fbm_jlw_encrypt without key, tau and ct_offset, from this party's
+ *   factor: device, n_ct x 128 limbs, fbm_jlw_decrypt_factor's H(t_k)^sk with the party's key, round and ct_offset
+ *   (computed ahead: it does not depend on x).  ct_out[k] = (N pt_k + 1) factor[k] mod N^2 at two products a
+ *   ciphertext, bit for bit fbm_jlw_encrypt's.  Any factor row below 2^4096 is taken (a zero row gives a zero
+ *   ciphertext); ct_out must not overlap factor (FBM_E_ARG).  workspace: fbm_jlw_seal_workspace(n_ct) bytes (the
+ *   constants and the packed plaintexts; fbm_jlw_workspace(n_ct) bytes suffice as well).  Nothing secret goes into
+ *   it, but A PARTY'S FACTOR TOGETHER WITH THE CIPHERTEXT IT SENT REVEALS ITS UPDATE (ct factor^-1 = N pt + 1): the
+ *   factor is as secret as the key, and the caller zeroes it after use.
+ * fbm_jlw_fold: fbm_jl_fold on 128-limb rows:
+ *     acc[c] <- (seed_ops > 0 ? 1 : acc[c]) * prod_j rows[j][c] mod N^2,  c < n_ct
+ *   acc device, n_ct x 128 limbs, in place; rows device, k x n_ct x 128 limbs (party-major), any values below
+ *   2^4096.  Two products a row, so -- unlike fbm_jl_fold -- acc IS the plain canonical product (< N^2) of the rows
+ *   folded so far after every call, whatever seed_ops announced; seed_ops > 0 only says that acc's contents are
+ *   ignored.  The checks are fbm_jl_fold's (k < 1, a null biprime, seed_ops < 0 or 0 < seed_ops < k: FBM_E_ARG;
+ *   n_ct == 0: FBM_OK; then a null acc / rows / workspace: FBM_E_ARG).  workspace: fbm_jlw_seal_workspace(0) bytes
+ *   (the constants alone).  No status words.  The finish is fbm_jlw_aggregate_factor_as with n_parties = 1. */
 uint64_t fbm_jlw_workspace(uint64_t n_ct);
+uint64_t fbm_jlw_seal_workspace(uint64_t n_ct);
+int fbm_jlw_encrypt_with(const void* x, int x_dtype, uint64_t n, double clip, double two_clip, double target_f,
+                         uint64_t target_m1, uint64_t weight, int es, int cr, const uint32_t* biprime,
+                         const uint32_t* factor, uint32_t* ct_out, void* workspace, uint32_t* stats, void* stream);
+int fbm_jlw_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, const uint32_t* biprime, int seed_ops,
+                 void* workspace, void* stream);
 int fbm_jlw_encrypt(const void* x, int x_dtype, uint64_t n, double clip, double two_clip, double target_f,
                     uint64_t target_m1, uint64_t weight, int es, int cr, const uint32_t* biprime, const uint32_t* key,
                     int key_negative, const uint32_t* tau, uint64_t ct_offset, uint32_t* ct_out, void* workspace,

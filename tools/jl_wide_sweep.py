@@ -11,6 +11,12 @@ the test build instead, the engines alternating within a repetition, every row w
 
     python tools/jl_wide_sweep.py --engine wave group --out profiles/jl_wide_group_sweep.jsonl \
         --counts 256 1024 2048 4096 8192 16384 31250 65536
+
+--seal: at --elements, the unprepared encrypt_tensor, decrypt_factor_tensor alone, encrypt_tensor(factor=)
+alone and a continuing D.jlw_fold of one row, alternating within a repetition, then the slowest prepared run over the
+fastest unprepared one:
+
+    python tools/jl_wide_sweep.py --seal --out profiles/jl_wide_seal.jsonl
 """
 import argparse
 import json
@@ -31,6 +37,7 @@ def main():
     ap.add_argument("--elements", type=int, default=1000000)
     ap.add_argument("--counts", type=int, nargs="+", default=[1, 256, 2048, 4096])
     ap.add_argument("--engine", nargs="+", choices=["auto", "wave", "group"], default=None)
+    ap.add_argument("--seal", action="store_true")
     args = ap.parse_args()
     import torch
 
@@ -50,6 +57,26 @@ def main():
         torch.cuda.synchronize(dev)
         return (time.perf_counter() - t0) * 1e3
 
+    if args.seal:  # the legs alternate within a repetition, after one warm-up of each
+        x = torch.rand(args.elements, dtype=torch.float64, device=dev) * 4 - 2
+        n_ct = -(-args.elements // D.jl_slot(None, 3)[1])
+        f = sc.decrypt_factor_tensor(5, n_ct, key, n)
+        acc = sc.encrypt_tensor(3, 5, x, key, n)
+        assert torch.equal(acc, sc.encrypt_tensor(3, 5, x, key, n, factor=f))
+        legs = [("encrypt_tensor", lambda: sc.encrypt_tensor(3, 5, x, key, n)),
+                ("decrypt_factor_tensor", lambda: sc.decrypt_factor_tensor(5, n_ct, key, n)),
+                ("encrypt_tensor_factor", lambda: sc.encrypt_tensor(3, 5, x, key, n, factor=f)),
+                ("jlw_fold_k1", lambda: D.jlw_fold(acc, f, n))]
+        timed(legs[3][1])
+        for rep in range(args.reps):
+            for what, fn in legs:
+                rows.append({"what": what, "elements": args.elements, "n_ct": n_ct, "num_nodes": 3, "rep": rep,
+                             "n_bits": n.bit_length(), "ms": timed(fn)})
+        ms = {w: [r["ms"] for r in rows if r["what"] == w] for w, _ in legs}
+        rows.append({"what": "seal_summary", "n_ct": n_ct,
+                     "slowest_prepared_over_fastest_unprepared": max(ms["encrypt_tensor_factor"]) / min(ms["encrypt_tensor"]),
+                     "fold_bytes": 512 * 3 * n_ct, "fold_gb_per_s": 512 * 3 * n_ct / min(ms["jlw_fold_k1"]) / 1e6})
+        return emit(rows, args.out)
     for n_ct in args.counts if args.engine else []:
         def run_engine(eng):
             with D.jlw_engine(eng):
@@ -84,7 +111,11 @@ def main():
         pow(h, -key, n * n)
         rows.append({"what": "host_python_pow", "key_bits": 4090, "key_negative": True, "n_bits": n.bit_length(),
                      "rep": rep, "ms": (time.perf_counter() - t0) * 1e3})
-    with open(args.out, "w") as f:
+    emit(rows, args.out)
+
+
+def emit(rows, out):
+    with open(out, "w") as f:
         for r in rows:
             f.write(json.dumps(r) + "\n")
             print(json.dumps(r))
