@@ -617,10 +617,14 @@ def limbs_to_ints(arr: np.ndarray) -> List[int]:
     return _pyconv().bytes_to_ints(np.ascontiguousarray(arr, dtype=np.uint32), 256)
 
 
+def limbs_to_ints_n(arr: np.ndarray, words: int) -> List[int]:
+    """limbs_to_ints for host rows of `words` 32-bit limbs."""
+    return _pyconv().bytes_to_ints(np.ascontiguousarray(arr.view(np.uint32).reshape(-1, words)), 4 * words)
+
+
 def limbs_to_ints_w(t: torch.Tensor, words: int) -> List[int]:
     """[n, words] 32-bit limbs (device or host tensor) -> list of Python ints."""
-    a = (to_host(t) if t.is_cuda else t).numpy().view(np.uint32)
-    return _pyconv().bytes_to_ints(np.ascontiguousarray(a.reshape(-1, words)), 4 * words)
+    return limbs_to_ints_n((to_host(t) if t.is_cuda else t).numpy(), words)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2037,15 +2041,20 @@ def int128_to_ints(arr: np.ndarray) -> List[int]:
 # ------------------------------------------------------------------------------------------
 # the reference Serializer's update bytes (fbm_wire_*; fedbiomed/common/serializer.py:96-110, 140-149)
 # ------------------------------------------------------------------------------------------
-_WIRE_SCHEME = {"jl": N.WIRE_JL, "lom": N.WIRE_LOM}
+_WIRE_SCHEME = {"jl": N.WIRE_JL, "lom": N.WIRE_LOM, "jlw": N.WIRE_JLW}
+_WIRE_LIMBS = {"jl": 64, "jlw": JLW_LIMBS}  # a row's 32-bit limbs
 _WIRE_NAME = {v: k for k, v in _WIRE_SCHEME.items()}
 
 
-def wire_scan(data, min_items: int) -> Optional[list]:
+def wire_scan(data, min_items: int, jl_limbs: int = 64) -> Optional[list]:
     """The host scanner (fbm_wire_scan) over a message: [(begin, end, n_items, scheme, checkpoints)] of the arrays
     it recorded -- scheme "jl" / "lom", checkpoints a uint64 array --, or None where it gives up (the message
-    stays msgpack's).  No device call."""
+    stays msgpack's).  No device call.  jl_limbs=128: fbm_wire_scan_jlw -- map items of up to 513 bytes (values
+    below 2^4096), an array that holds one recorded as "jlw"."""
+    if jl_limbs not in (64, JLW_LIMBS):
+        raise ValueError("jl_limbs must be 64 or 128")
     lib = N.load()
+    scan = lib.fbm_wire_scan if jl_limbs == 64 else lib.fbm_wire_scan_jlw
     buf = np.frombuffer(data, dtype=np.uint8)
     n = buf.size
     n_arr, n_ck = ctypes.c_uint64(0), ctypes.c_uint64(0)
@@ -2053,8 +2062,8 @@ def wire_scan(data, min_items: int) -> Optional[list]:
     for a_cap, c_cap in ((1024, n // 8 + 1024), (n // max(int(min_items), 1) + 1, n + 16)):
         arrays = (N.WireArray * a_cap)()
         ckpt = np.empty(c_cap, dtype=np.uint64)
-        rc = lib.fbm_wire_scan(_np_ptr(buf) if n else None, n, max(int(min_items), 1), ctypes.addressof(arrays), a_cap,
-                               ctypes.addressof(n_arr), _np_ptr(ckpt), c_cap, ctypes.addressof(n_ck))
+        rc = scan(_np_ptr(buf) if n else None, n, max(int(min_items), 1), ctypes.addressof(arrays), a_cap,
+                  ctypes.addressof(n_arr), _np_ptr(ckpt), c_cap, ctypes.addressof(n_ck))
         if rc == N.FBM_E_RANGE:
             continue
         if rc == N.FBM_E_UNSUPPORTED:
@@ -2067,19 +2076,19 @@ def wire_scan(data, min_items: int) -> Optional[list]:
 
 
 def _wire_rows(scheme: str, rows, dev) -> torch.Tensor:
-    """The scheme's rows as a contiguous device tensor: int32 [n, 64] (jl) or int64 [n] (lom)."""
+    """The scheme's rows as a contiguous device tensor: int32 [n, 64] (jl), int32 [n, 128] (jlw) or int64 [n] (lom)."""
     if scheme not in _WIRE_SCHEME:
-        raise ValueError("scheme must be 'jl' or 'lom'")
+        raise ValueError("scheme must be 'jl', 'jlw' or 'lom'")
+    w = _WIRE_LIMBS.get(scheme)
     if isinstance(rows, np.ndarray):
         a = np.ascontiguousarray(rows)
-        a = a.view(np.int32).reshape(-1, 64) if scheme == "jl" else a.view(np.int64).reshape(-1)
-        host = host_empty(a.shape, torch.int32 if scheme == "jl" else torch.int64)
+        a = a.view(np.int32).reshape(-1, w) if w else a.view(np.int64).reshape(-1)
+        host = host_empty(a.shape, torch.int32 if w else torch.int64)
         host.numpy()[...] = a
         return host.to(dev, non_blocking=host.is_pinned())
-    want = torch.int32 if scheme == "jl" else torch.int64
-    if rows.dtype != want or (scheme == "jl" and (rows.dim() != 2 or rows.shape[1] != 64)) or \
-            (scheme == "lom" and rows.dim() != 1):
-        raise ValueError("wire_encode takes int32 [n, 64] rows (jl) or int64 [n] words (lom)")
+    want = torch.int32 if w else torch.int64
+    if rows.dtype != want or (w and (rows.dim() != 2 or rows.shape[1] != w)) or (not w and rows.dim() != 1):
+        raise ValueError("wire_encode takes int32 [n, 64] rows (jl), int32 [n, 128] rows (jlw) or int64 [n] words (lom)")
     return rows.contiguous()
 
 
@@ -2097,11 +2106,16 @@ def wire_encode(scheme: str, rows, timing: Optional[dict] = None) -> bytes:
             torch.cuda.synchronize()
         t1 = time.perf_counter()
         n, sch = r.shape[0], _WIRE_SCHEME[scheme]
-        cap = int(lib.fbm_wire_encode_bound(sch, n))
+        wide = scheme == "jlw"  # (entry points of its own: fbm_wire_encode keeps its two schemes)
+        cap = int(lib.fbm_wire_encode_jlw_bound(n) if wide else lib.fbm_wire_encode_bound(sch, n))
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
-        ws = torch.empty(int(lib.fbm_wire_encode_workspace(sch, n)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(int(lib.fbm_wire_encode_jlw_workspace(n) if wide else lib.fbm_wire_encode_workspace(sch, n)),
+                         dtype=torch.uint8, device=dev)
         total = torch.empty(1, dtype=torch.int64, device=dev)
-        _call(lib.fbm_wire_encode, sch, _ptr(r), n, _ptr(out), cap, _ptr(ws), _ptr(total), _stream())
+        if wide:
+            _call(lib.fbm_wire_encode_jlw, _ptr(r), n, _ptr(out), cap, _ptr(ws), _ptr(total), _stream())
+        else:
+            _call(lib.fbm_wire_encode, sch, _ptr(r), n, _ptr(out), cap, _ptr(ws), _ptr(total), _stream())
         size = int(total.item())  # the one small copy; synchronises the stream
         t2 = time.perf_counter()
         data = to_host(out[:size]).numpy().tobytes()
@@ -2135,7 +2149,7 @@ class WireHandle:
         self._blk = self._tab = None
 
     def rows_host(self) -> np.ndarray:
-        """The decoded rows copied back: uint32 [n, 64] (jl) / uint64 [n] (lom)."""
+        """The decoded rows copied back: uint32 [n, 64] (jl) / uint32 [n, 128] (jlw) / uint64 [n] (lom)."""
         r = wire_rows_device(self)
         return to_host(r).numpy().view(np.uint32 if r.dtype == torch.int32 else np.uint64)
 
@@ -2424,19 +2438,50 @@ class WireStream:
 
 def wire_rows_device(handle: WireHandle, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The packed rows of an uploaded array (fbm_wire_decode) as a device tensor, on the current stream: int32
-    [n, 64] (jl) / int64 [n] (lom).  No host copy.  out: a contiguous tensor of that layout to decode into (the
-    caller orders its earlier uses)."""
+    [n, 64] (jl) / int32 [n, 128] (jlw: fbm_wire_decode_jlw) / int64 [n] (lom).  No host copy.  out: a contiguous
+    tensor of that layout to decode into (the caller orders its earlier uses)."""
     dev = handle.device
-    shape, dtype = ((handle.n, 64), torch.int32) if handle.scheme == "jl" else ((handle.n,), torch.int64)
+    w = _WIRE_LIMBS.get(handle.scheme)
+    shape, dtype = ((handle.n, w), torch.int32) if w else ((handle.n,), torch.int64)
     if out is not None and (out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or
                             out.device != dev):
         raise ValueError("wire_rows_device: out must be a contiguous tensor of the scheme's layout on the update's device")
     with torch.cuda.device(dev):
         span, ckpt = handle._use()
         rows = torch.empty(shape, dtype=dtype, device=dev) if out is None else out
-        _call(N.load().fbm_wire_decode, _WIRE_SCHEME[handle.scheme], span, handle.span_len, handle.base, ckpt,
-              handle.n_ckpt, handle.n, _ptr(rows), _stream())
+        if handle.scheme == "jlw":
+            _call(N.load().fbm_wire_decode_jlw, span, handle.span_len, handle.base, ckpt, handle.n, _ptr(rows), _stream())
+        else:
+            _call(N.load().fbm_wire_decode, _WIRE_SCHEME[handle.scheme], span, handle.span_len, handle.base, ckpt,
+                  handle.n_ckpt, handle.n, _ptr(rows), _stream())
     return rows
+
+
+def wire_fold_jlw(handle: WireHandle, acc: torch.Tensor, biprime: int, seed_ops: int = 0,
+                  n_items: Optional[int] = None) -> torch.Tensor:
+    """An uploaded "jlw" array folded into jlw_fold's accumulator straight from its bytes (fbm_wire_fold_jlw):
+    acc[c] <- (1 if seed_ops > 0 else acc[c]) * item c mod N^2 in place, on the current stream; the [n, 128] rows are
+    never written.  acc: int32 [n, 128], contiguous (any row slice of a larger buffer), on the handle's device;
+    bit for bit jlw_fold of the decoded rows.  n_items: fold the array's first n_items items only (None: all)."""
+    if handle.scheme != "jlw":
+        raise ValueError("wire_fold_jlw takes a 'jlw' array")
+    n = handle.n if n_items is None else int(n_items)
+    if not 0 <= n <= handle.n:
+        raise ValueError("wire_fold_jlw: n_items outside the array")
+    if acc.dtype != torch.int32 or tuple(acc.shape) != (n, JLW_LIMBS) or not acc.is_contiguous() or \
+            acc.device != handle.device:
+        raise ValueError(f"wire_fold_jlw takes a contiguous int32 [n, {JLW_LIMBS}] accumulator on the update's device")
+    bp = int_limbs(biprime, 64)
+    lib = N.load()
+    chunk = jl_chunk_ct()
+    with torch.cuda.device(handle.device):
+        span, ckpt = handle._use()
+        ws = torch.empty(int(lib.fbm_jlw_seal_workspace(0)), dtype=torch.uint8, device=acc.device)
+        for k0 in range(0, n, chunk):  # (as jlw_fold loops; a table word per item)
+            k1 = min(n, k0 + chunk)
+            _call(lib.fbm_wire_fold_jlw, span, handle.span_len, handle.base, ctypes.c_void_p(ckpt.value + 8 * k0), k1 - k0,
+                  _ptr(acc[k0:k1]), _np_ptr(bp), int(seed_ops), _ptr(ws), _stream())
+    return acc
 
 
 def wire_fold_lom(handle: WireHandle, acc: torch.Tensor, first: bool) -> torch.Tensor:
@@ -2457,7 +2502,7 @@ def wire_fold_lom(handle: WireHandle, acc: torch.Tensor, first: bool) -> torch.T
 
 def wire_decode(data, arrays: list, timing: Optional[dict] = None) -> List[np.ndarray]:
     """The packed rows of wire_scan's arrays of the message `data` (wire_upload, then fbm_wire_decode of each):
-    the rows come back as uint32 [n, 64] (jl) / uint64 [n] (lom) host arrays."""
+    the rows come back as uint32 [n, 64] (jl) / uint32 [n, 128] (jlw) / uint64 [n] (lom) host arrays."""
     import time
 
     handles = wire_upload(data, arrays, timing)

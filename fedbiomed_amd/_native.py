@@ -158,6 +158,13 @@ SIGNATURES = {
     "fbm_wire_scan": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp]),
     "fbm_wire_decode": (c_int, [c_int, c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp, c_vp]),
     "fbm_wire_fold_lom": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp, c_int, c_vp]),
+    # the wide family's items: rows [n][128], values below 2^4096 (additions to ABI 7)
+    "fbm_wire_encode_jlw_bound": (c_u64, [c_u64]),
+    "fbm_wire_encode_jlw_workspace": (c_u64, [c_u64]),
+    "fbm_wire_encode_jlw": (c_int, [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]),
+    "fbm_wire_scan_jlw": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp]),
+    "fbm_wire_decode_jlw": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
+    "fbm_wire_fold_jlw": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_int, c_vp, c_vp]),
     "fbm_wire_tokenize_workspace": (c_u64, [c_u64]),
     "fbm_wire_tokenize_lom": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]),
     "fbm_wire_scan_deferred": (c_int, [c_vp, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp]),
@@ -175,6 +182,7 @@ WIRE_MORE = 2  # FBM_WIRE_MORE
 WIRE_STREAM_STATE_WORDS = 16  # FBM_WIRE_STREAM_STATE_WORDS
 WIRE_JL = 0  # FBM_WIRE_JL
 WIRE_LOM = 1  # FBM_WIRE_LOM
+WIRE_JLW = 2  # FBM_WIRE_JLW
 WIRE_LOM_GROUP = 64  # FBM_WIRE_LOM_GROUP
 
 
@@ -225,6 +233,8 @@ TEST_SIGNATURES = {
     "fbm_test_lom_aggregate_kernel": (c_int, [c_int, c_u64, c_vp, ctypes.c_char_p, c_int]),
     "fbm_test_wire_encode": (c_int, [c_int, c_vp, c_u64, c_vp, c_u64, c_vp]),
     "fbm_test_wire_decode": (c_int, [c_int, c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp]),
+    "fbm_test_wire_encode_jlw": (c_int, [c_vp, c_u64, c_vp, c_u64, c_vp]),
+    "fbm_test_wire_decode_jlw": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_vp]),
     "fbm_test_wire_fold_lom": (c_int, [c_vp, c_u64, c_u64, c_vp, c_u64, c_u64, c_vp, c_int]),
     "fbm_test_wire_tokenize_lom": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
     "fbm_test_wire_tokenize_jl": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),

@@ -1693,6 +1693,115 @@ int fbm_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base
                [&] { return launch_wire_fold_lom(span, span_len, span_base, ckpt, n_ckpt, n_items, acc, first, s); });
 }
 
+// ---- the wide family's items (FBM_WIRE_JLW: rows [n][128], values below 2^4096) ----
+uint64_t fbm_wire_encode_jlw_bound(uint64_t n) { return 5 + n * (FBM_WIRE_JLW_ITEM_MAX + 1); }
+
+uint64_t fbm_wire_encode_jlw_workspace(uint64_t n) { return wire_encode_jlw_workspace(n); }
+
+// the checks fbm_wire_encode_jlw and its host hook share (fbm_wire_encode's)
+static int wire_encode_jlw_checks(const uint32_t* rows, uint64_t n, const uint8_t* out, uint64_t out_cap,
+                                  const uint64_t* total) {
+  if (n > 0xffffffffull) {
+    set_error("fbm_wire_encode_jlw: %llu items exceed a msgpack array", (unsigned long long)n);
+    return FBM_E_ARG;
+  }
+  if (!out || !total || (n > 0 && !rows)) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  if (out_cap < fbm_wire_encode_jlw_bound(n)) {
+    set_error("fbm_wire_encode_jlw: out_cap=%llu below fbm_wire_encode_jlw_bound's %llu", (unsigned long long)out_cap,
+              (unsigned long long)fbm_wire_encode_jlw_bound(n));
+    return FBM_E_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(rows) % 8) || (reinterpret_cast<uintptr_t>(total) % 8)) {
+    set_error("fbm_wire_encode_jlw: rows / total not aligned to 8 bytes");
+    return FBM_E_ARG;
+  }
+  return FBM_OK;
+}
+
+int fbm_wire_encode_jlw(const uint32_t* rows, uint64_t n, uint8_t* out, uint64_t out_cap, void* workspace,
+                        uint64_t* total, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc = wire_encode_jlw_checks(rows, n, out, out_cap, total);
+  if (rc) return rc;
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) % 8)) {
+    set_error("fbm_wire_encode_jlw: null or misaligned workspace");
+    return FBM_E_ARG;
+  }
+  return timed("wire_encode_jlw", s, [&] { return launch_wire_encode_jlw(rows, n, out, out_cap, workspace, total, s); });
+}
+
+int fbm_wire_scan_jlw(const uint8_t* data, uint64_t len, uint64_t min_items, fbm_wire_array* arrays, uint64_t arrays_cap,
+                      uint64_t* n_arrays, uint64_t* ckpt, uint64_t ckpt_cap, uint64_t* n_ckpt) {
+  if ((len > 0 && !data) || !n_arrays || !n_ckpt || (arrays_cap > 0 && !arrays) || (ckpt_cap > 0 && !ckpt)) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  fbm_wire_scan_out o = {arrays, arrays_cap, 0, ckpt, ckpt_cap, 0, FBM_WIRE_JLW_MAX_VLEN, FBM_WIRE_JLW};
+  const int r = fbm_wire_scan_impl(data, len, min_items, &o);
+  *n_arrays = o.n_arrays, *n_ckpt = o.n_ckpt;
+  if (r == FBM_WIRE_SCAN_GAVE_UP) {
+    set_error("fbm_wire_scan_jlw: not one well-formed msgpack object within the nesting bound");
+    return FBM_E_UNSUPPORTED;
+  }
+  if (r == FBM_WIRE_SCAN_FULL) {
+    set_error("fbm_wire_scan_jlw: arrays_cap / ckpt_cap too small");
+    return FBM_E_RANGE;
+  }
+  return FBM_OK;
+}
+
+// the checks fbm_wire_decode_jlw and its host hook share
+static int wire_decode_jlw_checks(const uint8_t* span, const uint64_t* ckpt, uint64_t n_items, const uint32_t* rows) {
+  if (n_items > 0 && (!span || !ckpt || !rows)) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(ckpt) % 8) || (reinterpret_cast<uintptr_t>(rows) % 8)) {
+    set_error("fbm_wire_decode_jlw: ckpt / rows not aligned to 8 bytes");
+    return FBM_E_ARG;
+  }
+  return FBM_OK;
+}
+
+int fbm_wire_decode_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                        uint64_t n_items, uint32_t* rows, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc = wire_decode_jlw_checks(span, ckpt, n_items, rows);
+  if (rc || n_items == 0) return rc;
+  return timed("wire_decode_jlw", s,
+               [&] { return launch_wire_decode_jlw(span, span_len, span_base, ckpt, n_items, rows, s); });
+}
+
+int fbm_wire_fold_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                      uint64_t n_items, uint32_t* acc, const uint32_t* biprime, int seed_ops, void* workspace,
+                      void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = jl_agg_checks(1, n_items, biprime, 1))) return rc;
+  if (seed_ops < 0) {
+    set_error("fbm_wire_fold_jlw: seed_ops=%d must be >= 0", seed_ops);
+    return FBM_E_ARG;
+  }
+  if (n_items == 0) return FBM_OK;
+  if (!span || !ckpt || !acc || !workspace) {
+    set_error("null pointer argument");
+    return FBM_E_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(ckpt) % 8) || (reinterpret_cast<uintptr_t>(acc) % 8)) {
+    set_error("fbm_wire_fold_jlw: ckpt / acc not aligned to 8 bytes");
+    return FBM_E_ARG;
+  }
+  JlwConsts c;
+  if ((rc = build_jlw_consts(biprime, nullptr, 0, nullptr, 0, c)) || (rc = launch_jlw_setup(c, (uint32_t*)workspace, s)))
+    return rc;
+  return timed("jlw_wire_fold", s, [&] {
+    return launch_jlw_wire_fold(span, span_len, span_base, ckpt, n_items, acc, seed_ops > 0, (const uint32_t*)workspace, s);
+  });
+}
+
 uint64_t fbm_wire_tokenize_workspace(uint64_t span_len) { return wire_tokenize_workspace(span_len); }
 
 // the checks fbm_wire_tokenize_lom / fbm_wire_tokenize_jl and their host hooks share (n_items > 0); `group`: items per
@@ -1968,6 +2077,18 @@ int fbm_test_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uin
                          uint64_t n_ckpt, uint64_t n_items, void* rows) {
   int rc = wire_decode_checks(scheme, span, ckpt, n_ckpt, n_items, rows);
   if (rc == FBM_OK && n_items) host_wire_decode(scheme, span, span_len, span_base, ckpt, n_ckpt, n_items, rows);
+  return rc;
+}
+
+int fbm_test_wire_encode_jlw(const uint32_t* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total) {
+  int rc = wire_encode_jlw_checks(rows, n, out, out_cap, total);
+  return rc ? rc : host_wire_encode_jlw(rows, n, out, out_cap, total);
+}
+
+int fbm_test_wire_decode_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                             uint64_t n_items, uint32_t* rows) {
+  int rc = wire_decode_jlw_checks(span, ckpt, n_items, rows);
+  if (rc == FBM_OK && n_items) host_wire_decode_jlw(span, span_len, span_base, ckpt, n_items, rows);
   return rc;
 }
 

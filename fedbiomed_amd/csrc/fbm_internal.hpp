@@ -360,6 +360,18 @@ void host_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64
                       uint64_t n_ckpt, uint64_t n, void* rows);
 void host_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n_ckpt,
                         uint64_t n, uint64_t* acc, int first);
+// FBM_WIRE_JLW, rows [n][128]: the encode's three passes, the decode, their host runs, and the fold into
+// launch_jlw_fold's accumulator straight from the bytes (fbm_jl_wide.hip: jlw_wire_fold_kernel)
+uint64_t wire_encode_jlw_workspace(uint64_t n);
+int launch_wire_encode_jlw(const uint32_t* rows, uint64_t n, uint8_t* out, uint64_t out_cap, void* workspace,
+                           uint64_t* total, hipStream_t s);
+int launch_wire_decode_jlw(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n,
+                           uint32_t* rows, hipStream_t s);
+int host_wire_encode_jlw(const uint32_t* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total);
+void host_wire_decode_jlw(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n,
+                          uint32_t* rows);
+int launch_jlw_wire_fold(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n,
+                         uint32_t* acc, bool seed, const uint32_t* cst, hipStream_t s);
 // fbm_wire_tokenize_lom: the workspace's bytes, whether the span's tiles fit one launch's grid, the three launches,
 // and the same three passes over host buffers
 uint64_t wire_tokenize_workspace(uint64_t span_len);

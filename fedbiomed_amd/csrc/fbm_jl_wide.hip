@@ -17,6 +17,7 @@
 // extended gcd in Kaliski's almost-Montgomery form (jw_kaliski).  FDH(2048, N^2).H runs in the wave: lanes
 // 0..6 hash the digests of the counters 1..7, r is gathered by ds_bpermute.  No scratch, no global tables.
 #include "fbm_internal.hpp"
+#include "fbm_wire.hpp"
 
 namespace fbm {
 
@@ -479,6 +480,43 @@ __global__ void __launch_bounds__(FBM_JW_BLOCK)
   }
 }
 
+// jlw_fold_kernel with its rows read straight from a stock peer's message ("wide items"): acc[i] <-
+// (seed ? 1 : acc[i]) item_i mod M, item i the big-endian bytes the table word ckpt[i] names (fbm_wire.hpp:
+// wire_jlw_load / wire_jlw_digit; one item per wave, lane j its digit j).  The [n][128] rows are never written.
+// A wave holds the next item's three raw dwords a lane across the current item's two products, as jlw_fold_kernel
+// holds its next row; the table word goes through the scalar unit (the wave's item is uniform), so the item's place,
+// length and shift cost no vector register.  Bounds: wire_jlw_item_of admits a table word only with its bytes inside
+// [span, span + span_len); wire_jlw_load reads a dword whole only where all four bytes lie inside, bytewise (inside
+// only) otherwise, and nothing for a digit above the value; ckpt and acc are read and written at i < n_items only.
+__device__ __forceinline__ uint64_t jw_uniform64(uint64_t v) {
+  return ((uint64_t)jw_first((uint32_t)(v >> 32)) << 32) | jw_first((uint32_t)v);
+}
+__global__ void __launch_bounds__(FBM_JW_BLOCK)
+    jlw_wire_fold_kernel(const uint8_t* __restrict__ span, uint64_t span_len, uint64_t base,
+                         const uint64_t* __restrict__ ckpt, uint64_t n_items, uint32_t* __restrict__ acc, int seed,
+                         const JlwConsts* __restrict__ c) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const JwMod k = jw_mod(c, lane);
+  const uint64_t stride = (uint64_t)gridDim.x * FBM_JW_WAVES;
+  uint64_t i = (uint64_t)blockIdx.x * FBM_JW_WAVES + wv;
+  if (i >= n_items) return;
+  wire_jlw_item next = wire_jlw_item_of(jw_uniform64(ckpt[i]), base, span_len);
+  uint32_t d[3];
+  wire_jlw_load(span, span_len, next, lane, d);
+#pragma unroll 1
+  for (; i < n_items; i += stride) {
+    const wire_jlw_item it = next;
+    uint64_t a = seed ? (lane == 0 ? 1ull : 0ull) : jw_digit(acc + i * 128, lane);
+    const uint64_t row = wire_jlw_digit(d, wire_jlw_shift(span, it), it, lane);
+    if (i + stride < n_items) {
+      next = wire_jlw_item_of(jw_uniform64(ckpt[i + stride]), base, span_len);
+      wire_jlw_load(span, span_len, next, lane, d);
+    }
+    a = jw_mm(a, jw_mm(row, k.r2, k, lane), k, lane);
+    reinterpret_cast<uint64_t*>(acc + i * 128)[lane] = a;
+  }
+}
+
 // ---- the group engine: four lanes per ciphertext, 16 ciphertexts per wave64, for large launches ----
 // A residue is 152 limbs of 27 bits, R' = 2^4104 >= 2^8 M: a Montgomery product of two values below 2 M (+ 1) is
 // below 2 M again, so nothing is subtracted between products; one compare-and-subtract ends a ciphertext.
@@ -867,6 +905,13 @@ int launch_jlw_fold(uint32_t* acc, const uint32_t* rows, int k, uint64_t n_ct, b
   hipLaunchKernelGGL(jlw_fold_kernel, dim3(jlw_grid(n_ct, 8)), dim3(FBM_JW_BLOCK), 0, s, acc, rows, k, n_ct, seed ? 1 : 0,
                      (const JlwConsts*)cst);
   return check_launch("jlw_fold_kernel");
+}
+
+int launch_jlw_wire_fold(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n,
+                         uint32_t* acc, bool seed, const uint32_t* cst, hipStream_t s) {
+  hipLaunchKernelGGL(jlw_wire_fold_kernel, dim3(jlw_grid(n, 8)), dim3(FBM_JW_BLOCK), 0, s, span, span_len, base, ckpt, n,
+                     acc, seed ? 1 : 0, (const JlwConsts*)cst);
+  return check_launch("jlw_wire_fold_kernel");
 }
 
 }  // namespace fbm

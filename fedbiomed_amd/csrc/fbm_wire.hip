@@ -223,6 +223,83 @@ __global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_decode_jl_kernel(const ui
   rows[i * 64 + lane] = w;
 }
 
+// ---- the wide family's rows [n][128] (FBM_WIRE_JLW; DESIGN.md 4.2, "wide items") -----------------------------
+// Encode: the narrow passes with items of up to 536 bytes (a uint16 still holds the size; a tile's 256 items stay
+// below 2^32 bytes).  The emit's bit length comes from two words per lane: a ballot over the 64 digits, then the top
+// digit's width.  Decode: one wave per item, lane j assembles digit j (words 2j, 2j + 1) by wire_jlw_digit_at --
+// three aligned dword loads, two funnel shifts, two byte swaps -- and the wave stores the row's 512 bytes whole.
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_sizes_jlw_kernel(const uint32_t* __restrict__ rows, uint64_t n,
+                                                                        uint16_t* __restrict__ sz,
+                                                                        uint64_t* __restrict__ partial) {
+  __shared__ uint32_t sh[FBM_WIRE_BLOCK];
+  const uint64_t i = (uint64_t)blockIdx.x * FBM_WIRE_TILE_JL + threadIdx.x;
+  uint32_t s = 0;
+  if (i < n) {
+    const uint32_t* row = rows + i * 128;
+    s = wire_jl_size(row, wire_jlw_bits(row));
+    sz[i] = (uint16_t)s;
+  }
+  uint32_t total;
+  wire_block_scan(s, sh, total);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_emit_jlw_kernel(const uint32_t* __restrict__ rows, uint64_t n,
+                                                                       const uint16_t* __restrict__ sz,
+                                                                       const uint64_t* __restrict__ partial,
+                                                                       uint8_t* __restrict__ out, uint64_t out_cap) {
+  __shared__ uint32_t sh[FBM_WIRE_BLOCK];
+  __shared__ uint32_t sh_off[FBM_WIRE_TILE_JL];
+  __shared__ uint32_t sh_sz[FBM_WIRE_TILE_JL];
+  const int t = threadIdx.x;
+  const uint64_t tile0 = (uint64_t)blockIdx.x * FBM_WIRE_TILE_JL;
+  const uint32_t s = tile0 + t < n ? sz[tile0 + t] : 0u;
+  uint32_t total;
+  sh_off[t] = wire_block_scan(s, sh, total);
+  sh_sz[t] = s;
+  __syncthreads();
+  const uint64_t base = partial[blockIdx.x];
+  const int wave = t >> 6, lane = t & 63;
+  for (int it = wave; it < FBM_WIRE_TILE_JL; it += FBM_WIRE_BLOCK / 64) {
+    const uint64_t i = tile0 + it;
+    if (i >= n) break;
+    const uint32_t S = sh_sz[it];
+    const uint64_t p = base + sh_off[it];
+    if (p > out_cap || out_cap - p < S) continue;  // (the caller's bound holds every item: never taken)
+    const uint32_t* row = rows + i * 128;
+    const uint64_t* row64 = reinterpret_cast<const uint64_t*>(row);
+    const uint64_t nz = __ballot(row64[lane] != 0);
+    int bits = 0;
+    if (nz) {
+      const int top = 63 - __builtin_clzll(nz);
+      bits = 64 * top + 64 - __builtin_clzll(row64[top]);
+    }
+    uint8_t* o = out + p;
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(o) & 3u);
+    uint32_t head = mis ? 4u - mis : 0u;
+    if (head > S) head = S;
+    const uint32_t ndw = (S - head) / 4;
+    const uint32_t tail0 = head + 4 * ndw;
+    if ((uint32_t)lane < head) o[lane] = wire_jlw_byte(row, bits, lane);
+    for (uint32_t d = lane; d < ndw; d += 64) {
+      const uint32_t k = head + 4 * d;
+      const uint32_t w = (uint32_t)wire_jlw_byte(row, bits, k) | ((uint32_t)wire_jlw_byte(row, bits, k + 1) << 8) |
+                         ((uint32_t)wire_jlw_byte(row, bits, k + 2) << 16) | ((uint32_t)wire_jlw_byte(row, bits, k + 3) << 24);
+      *reinterpret_cast<uint32_t*>(o + k) = w;
+    }
+    if (tail0 + lane < S) o[tail0 + lane] = wire_jlw_byte(row, bits, tail0 + lane);
+  }
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_decode_jlw_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                         uint64_t base, const uint64_t* __restrict__ ckpt,
+                                                                         uint64_t n, uint32_t* __restrict__ rows) {
+  const uint64_t i = (uint64_t)blockIdx.x * (FBM_WIRE_BLOCK / 64) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (i >= n) return;
+  reinterpret_cast<uint64_t*>(rows + i * 128)[lane] = wire_jlw_digit_at(span, span_len, base, ckpt[i], lane);
+}
+
 __global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_decode_lom_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
                                                                          uint64_t base, const uint64_t* __restrict__ ckpt,
                                                                          uint64_t n_groups, uint64_t n,
@@ -678,6 +755,40 @@ int launch_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, 
   return check_launch("wire_fold_lom_kernel");
 }
 
+// FBM_WIRE_JLW: the JL workspace's layout (tile sums, then a uint16 size per item)
+uint64_t wire_encode_jlw_workspace(uint64_t n) { return wire_encode_workspace(FBM_WIRE_JL, n); }
+
+int launch_wire_encode_jlw(const uint32_t* rows, uint64_t n, uint8_t* out, uint64_t out_cap, void* workspace,
+                           uint64_t* total, hipStream_t s) {
+  const uint64_t nb = wire_tiles(FBM_WIRE_JL, n);
+  unsigned g = 0;
+  int rc = wire_grid(nb, "fbm_wire_encode_jlw", g);
+  if (rc) return rc;
+  uint64_t* partial = reinterpret_cast<uint64_t*>(workspace);
+  uint16_t* sz = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(workspace) + (nb * 8 + 255) / 256 * 256 + 256);
+  if (g) {
+    hipLaunchKernelGGL(wire_sizes_jlw_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, rows, n, sz, partial);
+    if ((rc = check_launch("wire_sizes_jlw_kernel"))) return rc;
+  }
+  hipLaunchKernelGGL(wire_scan_kernel, dim3(1), dim3(FBM_WIRE_SCAN_THREADS), 0, s, partial, nb, n, out, out_cap, total);
+  if ((rc = check_launch("wire_scan_kernel"))) return rc;
+  if (g) {
+    hipLaunchKernelGGL(wire_emit_jlw_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, rows, n, sz, partial, out, out_cap);
+    if ((rc = check_launch("wire_emit_jlw_kernel"))) return rc;
+  }
+  return FBM_OK;
+}
+
+int launch_wire_decode_jlw(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n,
+                           uint32_t* rows, hipStream_t s) {
+  if (n == 0) return FBM_OK;
+  unsigned g = 0;
+  int rc = wire_grid((n + FBM_WIRE_BLOCK / 64 - 1) / (FBM_WIRE_BLOCK / 64), "fbm_wire_decode_jlw", g);
+  if (rc) return rc;
+  hipLaunchKernelGGL(wire_decode_jlw_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, base, ckpt, n, rows);
+  return check_launch("wire_decode_jlw_kernel");
+}
+
 uint64_t wire_tokenize_workspace(uint64_t span_len) {
   const uint64_t tiles = (span_len + 3 + FBM_WIRE_TOK_TILE - 1) / FBM_WIRE_TOK_TILE;  // whatever the alignment
   return wire_tok_maps_at(tiles) + (tiles * FBM_WIRE_TOK_MAP * 4 + 255) / 256 * 256 + 256;
@@ -810,6 +921,31 @@ void host_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64
     for (int j = 0; j < FBM_WIRE_LOM_GROUP; ++j)
       if (g * FBM_WIRE_LOM_GROUP + j < n) ((uint64_t*)rows)[g * FBM_WIRE_LOM_GROUP + j] = wire_lom_group_item(buf, avail, j);
   }
+}
+
+int host_wire_encode_jlw(const uint32_t* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total) {
+  uint64_t p = 0;
+  const uint32_t hdr = wire_header_size(n);
+  for (uint32_t k = 0; k < hdr; ++k, ++p)
+    if (p < out_cap) out[p] = wire_header_byte(n, k);
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint32_t* row = rows + i * 128;
+    const int bits = wire_jlw_bits(row);
+    const uint32_t S = wire_jl_size(row, bits);
+    for (uint32_t k = 0; k < S; ++k, ++p)
+      if (p < out_cap) out[p] = wire_jlw_byte(row, bits, k);
+  }
+  *total = p;
+  return p <= out_cap ? FBM_OK : FBM_E_ARG;
+}
+
+void host_wire_decode_jlw(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n,
+                          uint32_t* rows) {
+  for (uint64_t i = 0; i < n; ++i)
+    for (int j = 0; j < 64; ++j) {
+      const uint64_t v = wire_jlw_digit_at(span, span_len, base, ckpt[i], j);
+      rows[i * 128 + 2 * j] = (uint32_t)v, rows[i * 128 + 2 * j + 1] = (uint32_t)(v >> 32);
+    }
 }
 
 void host_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t base, const uint64_t* ckpt, uint64_t n_ckpt,

@@ -11,6 +11,8 @@
 #include "fbm_common.hpp"
 
 #define FBM_WIRE_ITEM_MAX 280  // a 2048-bit value
+#define FBM_WIRE_JLW_ITEM_MAX 536  // a 4096-bit value (FBM_WIRE_JLW): prefix, c5 + BE16, 513 bytes
+#define FBM_WIRE_JLW_VLEN_MAX 513
 #define FBM_WIRE_NATIVE_MAX 9
 
 namespace fbm {
@@ -48,8 +50,8 @@ FBM_HD uint32_t wire_jl_size(const uint32_t* row, int bits) {
   const uint32_t L = wire_jl_bin_len(bits);
   return 20u + (L <= 255 ? 2u : 3u) + L;
 }
-// byte k of the item of a row of `bits` bits (k < wire_jl_size)
-FBM_HD uint8_t wire_jl_byte(const uint32_t* row, int bits, uint32_t k) {
+// byte k of the item of a row of `bits` bits (k < wire_jl_size); the row holds `row_bytes` bytes
+FBM_HD uint8_t wire_jl_byte_of(const uint32_t* row, int bits, uint32_t k, uint32_t row_bytes) {
   if (bits <= 64) {
     const uint64_t v = (uint64_t)row[0] | ((uint64_t)row[1] << 32);
     return wire_native_byte(v, wire_native_size(v), k);
@@ -71,8 +73,18 @@ FBM_HD uint8_t wire_jl_byte(const uint32_t* row, int bits, uint32_t k) {
     hdr = 23;
   }
   const uint32_t i = L - 1 - (k - hdr);  // the byte's little-endian index
-  return i >= 256 ? 0 : (uint8_t)(row[i >> 2] >> (8 * (i & 3)));
+  return i >= row_bytes ? 0 : (uint8_t)(row[i >> 2] >> (8 * (i & 3)));
 }
+FBM_HD uint8_t wire_jl_byte(const uint32_t* row, int bits, uint32_t k) { return wire_jl_byte_of(row, bits, k, 256); }
+// the same for a 128-limb row (FBM_WIRE_JLW; wire_jl_size holds for it as it stands)
+FBM_HD int wire_jlw_bits(const uint32_t* row) {
+  for (int j = 127; j >= 0; --j) {
+    const uint32_t w = row[j];
+    if (w) return 32 * j + 32 - __builtin_clz(w);
+  }
+  return 0;
+}
+FBM_HD uint8_t wire_jlw_byte(const uint32_t* row, int bits, uint32_t k) { return wire_jl_byte_of(row, bits, k, 512); }
 
 // ---- decode -----------------------------------------------------------------------------------------
 // limb j of the value whose vlen big-endian bytes start at v (bytes past the 256th are the sign byte: zero)
@@ -84,6 +96,71 @@ FBM_HD uint32_t wire_jl_limb(const uint8_t* v, uint32_t vlen, int j) {
   }
   return w;
 }
+// ---- decode (FBM_WIRE_JLW): the 64-bit digit j (words 2j, 2j + 1) of a value of up to 513 big-endian bytes ----
+// A table word names the value's bytes [voff, voff + vlen) of the message; `end` is the span offset one past the last
+// of them.  Digit j is the eight bytes that end at end - 8j, most significant first, so it is the byte-swapped
+// little-endian word at p = end - 8j - 8.  Lanes are 8 bytes apart: the misalignment of p against a dword, sh =
+// (span's address + end) & 3, is the same for every digit of an item.  The three aligned dwords from p - sh on hold the
+// eight bytes; two funnel shifts by 8 sh bits and two byte swaps give the digit (plain C++ here, so that the host run
+// executes the same lines: on gfx950 they compile to v_alignbit_b32 / v_lshrrev_b64 and v_perm_b32).  What lies in front of voff --
+// the top digit's missing bytes, every byte of a digit above the value -- is masked off: they are the digit's high
+// bytes.  The byte at index 512 of a 513-byte value is the sign byte (zero) and belongs to no digit.
+// A dword that lies wholly inside the span is read whole (its address is aligned by construction), one that straddles
+// an end of the span bytewise (wire_tok_word: bytes outside count as 0 and are not read), and a digit above the value
+// reads nothing.  A table word whose bytes do not lie inside the span, or whose vlen is outside 1..513, is the value 0.
+FBM_HD uint32_t wire_tok_word(const uint8_t* span, uint64_t span_len, int64_t off);  // (below)
+struct wire_jlw_item {
+  int64_t end;    // span offset one past the value's last byte
+  uint32_t vlen;  // 0: the item counts as the value 0, nothing is read
+};
+FBM_HD wire_jlw_item wire_jlw_item_of(uint64_t ck, uint64_t base, uint64_t span_len) {
+  const uint64_t voff = ck >> 16;
+  const uint32_t vlen = (uint32_t)(ck & 0xffff);
+  wire_jlw_item it = {0, 0};
+  if (vlen >= 1 && vlen <= FBM_WIRE_JLW_VLEN_MAX && voff >= base && voff - base <= span_len && span_len - (voff - base) >= vlen)
+    it.end = (int64_t)(voff - base) + vlen, it.vlen = vlen;
+  return it;
+}
+// bytes of digit j that the value holds: 0..8
+FBM_HD uint32_t wire_jlw_held(const wire_jlw_item& it, int j) {
+  const int32_t left = (int32_t)it.vlen - 8 * j;
+  return left <= 0 ? 0u : left >= 8 ? 8u : (uint32_t)left;
+}
+FBM_HD uint32_t wire_jlw_shift(const uint8_t* span, const wire_jlw_item& it) {
+  return (uint32_t)((reinterpret_cast<uintptr_t>(span) + (uint64_t)it.end) & 3u);
+}
+// the three aligned dwords that cover digit j's eight bytes (sh == 0: two) -> d[0..2]
+FBM_HD void wire_jlw_load(const uint8_t* span, uint64_t span_len, const wire_jlw_item& it, int j, uint32_t* d) {
+  d[0] = d[1] = d[2] = 0;
+  if (wire_jlw_held(it, j) == 0) return;
+  const uint32_t sh = wire_jlw_shift(span, it);
+  const int64_t q = it.end - 8 * j - 8 - (int64_t)sh;  // span + q is 4-byte aligned; q > -12
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const int64_t off = q + 4 * t;
+    if (t == 2 && sh == 0) break;
+    if (off >= 0 && (uint64_t)off + 4 <= span_len)
+      d[t] = *reinterpret_cast<const uint32_t*>(span + off);
+    else
+      d[t] = wire_tok_word(span, span_len, off);
+  }
+}
+FBM_HD uint64_t wire_jlw_digit(const uint32_t* d, uint32_t sh, const wire_jlw_item& it, int j) {
+  const uint32_t held = wire_jlw_held(it, j);
+  if (held == 0) return 0;
+  const uint32_t w0 = (uint32_t)((((uint64_t)d[1] << 32) | d[0]) >> (8 * sh));  // bytes p .. p + 3, p's first
+  const uint32_t w1 = (uint32_t)((((uint64_t)d[2] << 32) | d[1]) >> (8 * sh));  // bytes p + 4 .. p + 7
+  const uint64_t v = ((uint64_t)__builtin_bswap32(w0) << 32) | __builtin_bswap32(w1);
+  return held == 8 ? v : v & ((1ull << (8 * held)) - 1ull);
+}
+// digit j of the item of table word ck, on its own (the decode kernel and the host run)
+FBM_HD uint64_t wire_jlw_digit_at(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t ck, int j) {
+  const wire_jlw_item it = wire_jlw_item_of(ck, base, span_len);
+  uint32_t d[3];
+  wire_jlw_load(span, span_len, it, j, d);
+  return wire_jlw_digit(d, wire_jlw_shift(span, it), it, j);
+}
+
 // bytes of the native unsigned form that starts with b; 0: not one
 FBM_HD uint32_t wire_native_len(uint8_t b) {
   return b <= 0x7f ? 1u : b == 0xcc ? 2u : b == 0xcd ? 3u : b == 0xce ? 5u : b == 0xcf ? 9u : 0u;

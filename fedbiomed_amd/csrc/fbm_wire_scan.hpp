@@ -20,6 +20,9 @@
 // a native form is not walked here when the caller brings its end offset from the device tokenizer
 // (fbm_wire_tokenize_lom); fbm_wire_scan_deferred2 does the same for a large array of big-int maps
 // (fbm_wire_tokenize_jl); see fbm_wire_defer below.
+//
+// fbm_wire_scan_jlw is the pass with the map item's bound at L <= 513 (a value < 2^4096) and FBM_WIRE_JLW as the
+// scheme of an array that holds a map item: fbm_wire_scan_out carries both, every other caller leaves the defaults.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -39,8 +42,12 @@ static const uint8_t FBM_WIRE_PREFIX[FBM_WIRE_PREFIX_LEN] = {0x82, 0xa8, '_', '_
 
 // One accepted item at d[pos..]: returns its byte count (0: not an accepted form, or truncated), the span of
 // its big-endian value bytes and whether it is a native form.
+// max_vlen: the largest L of a map item, 257 (a value < 2^2048) or FBM_WIRE_JLW_MAX_VLEN = 513 (< 2^4096,
+// fbm_wire_scan_jlw); at that L the first byte is the zero sign byte.
+#define FBM_WIRE_JL_MAX_VLEN 257
+#define FBM_WIRE_JLW_MAX_VLEN 513
 static inline uint64_t fbm_wire_item(const uint8_t* d, uint64_t pos, uint64_t len, uint64_t* voff, uint32_t* vlen,
-                                     int* native) {
+                                     int* native, uint32_t max_vlen = FBM_WIRE_JL_MAX_VLEN) {
   if (pos >= len) return 0;
   const uint64_t left = len - pos;  // >= 1
   const uint8_t b = d[pos];
@@ -66,8 +73,8 @@ static inline uint64_t fbm_wire_item(const uint8_t* d, uint64_t pos, uint64_t le
   } else {
     return 0;
   }
-  if (L < 1 || L > 257 || len - v < L) return 0;
-  if (d[v] >= 0x80 || (L == 257 && d[v] != 0)) return 0;  // a negative value, or one of 2^2048 or more
+  if (L < 1 || L > max_vlen || len - v < L) return 0;
+  if (d[v] >= 0x80 || (L == max_vlen && d[v] != 0)) return 0;  // a negative value, or one of 2^2048 (2^4096) or more
   *voff = v, *vlen = L, *native = 0;
   return v + L - pos;
 }
@@ -77,6 +84,8 @@ struct fbm_wire_scan_out {
   uint64_t arrays_cap, n_arrays;
   uint64_t* ckpt;
   uint64_t ckpt_cap, n_ckpt;
+  uint32_t max_vlen = FBM_WIRE_JL_MAX_VLEN;  // the map items' bound, and the scheme an array that holds one is
+  int32_t map_scheme = FBM_WIRE_JL;          // recorded under (fbm_wire_scan_jlw: 513, FBM_WIRE_JLW)
 };
 
 // items [first, first + n) of a candidate array: 1 recorded (*end = one past it), 0 not, -1 a table is full
@@ -92,7 +101,7 @@ static inline int fbm_wire_candidate(const uint8_t* d, uint64_t len, uint64_t be
       if (o->n_ckpt >= o->ckpt_cap) return -1;
       o->ckpt[o->n_ckpt++] = p;
     }
-    const uint64_t c = fbm_wire_item(d, p, len, &voff, &vlen, &native);
+    const uint64_t c = fbm_wire_item(d, p, len, &voff, &vlen, &native, o->max_vlen);
     if (c == 0) {
       o->n_ckpt = ck0;
       return 0;
@@ -104,7 +113,7 @@ static inline int fbm_wire_candidate(const uint8_t* d, uint64_t len, uint64_t be
       uint32_t ql = 0;
       int qn = 0;
       for (uint64_t j = 0; j < i; ++j) {
-        const uint64_t cj = fbm_wire_item(d, q, len, &qo, &ql, &qn);  // (accepted once already: cj > 0)
+        const uint64_t cj = fbm_wire_item(d, q, len, &qo, &ql, &qn, o->max_vlen);  // (accepted once already: cj > 0)
         if (o->n_ckpt >= o->ckpt_cap) return -1;
         o->ckpt[o->n_ckpt++] = (qo << 16) | ql;
         q += cj;
@@ -119,7 +128,7 @@ static inline int fbm_wire_candidate(const uint8_t* d, uint64_t len, uint64_t be
   fbm_wire_array* a = &o->arrays[o->n_arrays++];
   a->begin = begin, a->end = p, a->n_items = n;
   a->ckpt_first = ck0, a->ckpt_count = o->n_ckpt - ck0;
-  a->scheme = lom ? FBM_WIRE_LOM : FBM_WIRE_JL, a->pad = 0;
+  a->scheme = lom ? FBM_WIRE_LOM : o->map_scheme, a->pad = 0;
   *end = p;
   return 1;
 }

@@ -136,6 +136,13 @@ def _any_resident(params) -> bool:
     return isinstance(params, list) and any(isinstance(p, wire.ResidentUpdate) for p in params)
 
 
+def _any_wide_reply(params) -> bool:
+    """Whether a wide biprime's `aggregate` has a reply that is not a plain list: resident, packed "jlw", a tensor."""
+    return isinstance(params, list) and any(
+        isinstance(p, (wire.ResidentUpdate, torch.Tensor)) or (isinstance(p, wire.EncryptedParams) and p.scheme == "jlw")
+        for p in params)
+
+
 class JlStreamAggregation:
     """Extension (not in the reference): `SecaggCrypter.aggregate` one reply at a time.
 
@@ -899,6 +906,9 @@ class SecaggCrypter:
         a `wire.ResidentUpdate`, the replies go through `begin_aggregate` / `add` / `finish` in their order: the
         same result bit for bit, with the stream's error sites (a reply's checks as it is added, the rest at
         the end)."""
+        if D.jl_wide(biprime) and isinstance(key, int) and _any_wide_reply(params):
+            return self._aggregate_wide_replies(current_round, num_nodes, params, key, biprime, total_sample_size,
+                                                clipping_range, num_expected_params, target_range)
         if _any_resident(params):
             agg = self.begin_aggregate(current_round, num_nodes, key, biprime, total_sample_size, clipping_range,
                                        num_expected_params, target_range)
@@ -988,6 +998,56 @@ class SecaggCrypter:
             cts = torch.from_numpy(rows.copy()).to(D.device())
             out = self.aggregate_tensor(current_round, cts, key, biprime, total_sample_size, clipping_range,
                                         num_expected_params, target_range)
+            res = D.to_host(out).numpy().tolist()
+        return res
+
+    def _aggregate_wide_replies(self, current_round, num_nodes, params, key, biprime, total_sample_size,
+                                clipping_range, num_expected_params, target_range) -> List[float]:
+        """`_aggregate_wide` where a reply is already on the device or packed: a `wire.ResidentUpdate` of scheme
+        "jlw" (`wire.loads_reference(resident=True, jl_limbs=128)`), a consistent "jlw" `wire.EncryptedParams` or an
+        int32 [n_ct, 128] device tensor; the others may be List[int].  The same checks in the same order, then one
+        [n_ct, 128] accumulator takes the replies in arrival order -- a resident one straight from its bytes
+        (D.wire_fold_jlw), the others as rows (D.jlw_fold, uploaded where they are on the host) -- and the
+        aggregate of that one row under the slot of `num_nodes` parties ends it.  The shortest
+        reply fixes the length (the reference's zip).  A ResidentUpdate of another scheme is FB624."""
+        if len(params) != num_nodes:
+            raise FedbiomedSecaggCrypterError(
+                f"{ErrorNumbers.FB624.value}: Num of parameters that are received from nodes "
+                f"does not match the number of nodes has been set for the encrypter. There might "
+                f"be some nodes did not answered to training request or num of clients of "
+                "`ParameterEncrypter` has not been set properly before train request.")
+        dev, W = D.device(), D.JLW_LIMBS
+        for p in params:
+            if isinstance(p, wire.ResidentUpdate):
+                _resident_handle(p, "jlw")
+            elif isinstance(p, torch.Tensor):
+                if not p.is_cuda or p.dtype != torch.int32 or p.dim() != 2 or p.shape[1] != W:
+                    raise FedbiomedSecaggCrypterError(
+                        f"{ErrorNumbers.FB624.value}: a tensor reply is an int32 [n_ct, {W}] device tensor")
+            else:
+                _check_int_list(p)
+        n_ct = min(p.shape[0] if isinstance(p, torch.Tensor) else len(p) for p in params)  # zip truncates
+        if n_ct == 0:
+            return []
+        n2, nb = biprime * biprime, 4 * W
+        with D.deferred_checks():
+            acc = torch.empty((n_ct, W), dtype=torch.int32, device=dev)
+            for j, p in enumerate(params):
+                seed = len(params) if j == 0 else 0
+                if isinstance(p, wire.ResidentUpdate):
+                    D.wire_fold_jlw(p.handle, acc, biprime, seed, n_items=n_ct)
+                    continue
+                if isinstance(p, torch.Tensor):
+                    rows = p[:n_ct]
+                elif isinstance(p, wire.EncryptedParams) and p.scheme == "jlw" and p.consistent():
+                    rows = torch.from_numpy(np.ascontiguousarray(p.packed[:n_ct]).view(np.int32)).to(dev)
+                else:
+                    blob = b"".join((int(c) % n2).to_bytes(nb, "little") for c in p[:n_ct])
+                    rows = torch.from_numpy(np.frombuffer(blob, dtype=np.int32).reshape(n_ct, W).copy()).to(dev)
+                D.jlw_fold(acc, rows, biprime, seed)
+            out, _ = D.jlw_aggregate(acc[None], biprime, key, current_round, num_expected_params, total_sample_size,
+                                     clip=clipping_range, target=target_range,
+                                     slot=D.jl_slot(target_range or SAParameters.TARGET_RANGE, len(params)))
             res = D.to_host(out).numpy().tolist()
         return res
 

@@ -66,10 +66,15 @@ def enabled() -> bool:
     return _ENABLED
 
 
+SCHEMES = ("jl", "jlw", "lom")
+_JL_LIMBS = {"jl": 64, "jlw": 128}  # 32-bit limbs of a packed row
+
+
 class EncryptedParams(list):
     """A reference-compatible ``List[int]`` update plus its packed device form.
 
     scheme "jl": ``packed`` is uint32 ``[n_ct, 64]`` (ciphertext k = little-endian limbs);
+    scheme "jlw": uint32 ``[n_ct, 128]`` (a biprime of 1025 to 2048 bits: ciphertexts below 2^4096);
     scheme "lom": ``packed`` is uint64 ``[n]``.
     """
 
@@ -77,18 +82,20 @@ class EncryptedParams(list):
 
     def __init__(self, values: Iterable[int], scheme: str, packed: np.ndarray):
         super().__init__(values)
-        if scheme not in ("jl", "lom"):
-            raise ValueError("scheme must be 'jl' or 'lom'")
+        if scheme not in SCHEMES:
+            raise ValueError("scheme must be 'jl', 'jlw' or 'lom'")
         self.scheme = scheme
         self.packed = packed
 
     @classmethod
     def from_ints(cls, scheme: str, values) -> "EncryptedParams":
-        """Pack a plain update (JL ciphertexts must lie in [0, 2^2048), LOM words in [0, 2^64))."""
+        """Pack a plain update (JL ciphertexts must lie in [0, 2^2048), wide ones in [0, 2^4096), LOM words in
+        [0, 2^64))."""
         values = [int(v) for v in values]
-        if scheme == "jl":
-            blob = b"".join(v.to_bytes(256, "little") for v in values)
-            packed = np.frombuffer(blob, dtype="<u4").reshape(len(values), 64).copy()
+        if scheme in _JL_LIMBS:
+            w = _JL_LIMBS[scheme]
+            blob = b"".join(v.to_bytes(4 * w, "little") for v in values)
+            packed = np.frombuffer(blob, dtype="<u4").reshape(len(values), w).copy()
         else:
             packed = np.array(values, dtype=np.uint64)
         return cls(values, scheme, packed)
@@ -96,11 +103,11 @@ class EncryptedParams(list):
     @classmethod
     def from_packed(cls, scheme: str, packed: np.ndarray) -> "EncryptedParams":
         packed = np.ascontiguousarray(packed)
-        if scheme == "jl":
+        if scheme in _JL_LIMBS:
             from . import _device as D  # (the C conversion module: the ints' digits written on host threads)
 
-            packed = packed.view(np.uint32).reshape(-1, 64)
-            values = D.limbs_to_ints(packed)
+            packed = packed.view(np.uint32).reshape(-1, _JL_LIMBS[scheme])
+            values = D.limbs_to_ints(packed) if scheme == "jl" else D.limbs_to_ints_n(packed, 128)
         else:
             packed = packed.view(np.uint64).reshape(-1)
             values = packed.tolist()
@@ -165,7 +172,7 @@ def from_wire(obj: Any) -> Any:
     (anything else is returned unchanged)."""
     if isinstance(obj, dict) and obj.get("__type__") == WIRE_TYPE:
         scheme, dtype, shape, data = obj["value"]
-        if scheme not in ("jl", "lom") or np.dtype(dtype) not in (np.dtype("<u4"), np.dtype("<u8")):
+        if scheme not in SCHEMES or np.dtype(dtype) not in (np.dtype("<u4"), np.dtype("<u8")):
             raise ValueError("malformed EncryptedParams wire map")
         arr = np.frombuffer(data, dtype=np.dtype(dtype)).reshape(shape).copy()
         return EncryptedParams.from_packed(scheme, arr)
@@ -254,8 +261,8 @@ class ResidentUpdate:
     __slots__ = ("scheme", "n_items", "_handle", "_values")
 
     def __init__(self, scheme: str, n_items: int, handle):
-        if scheme not in ("jl", "lom"):
-            raise ValueError("scheme must be 'jl' or 'lom'")
+        if scheme not in SCHEMES:
+            raise ValueError("scheme must be 'jl', 'jlw' or 'lom'")
         self.scheme, self.n_items, self._handle, self._values = scheme, int(n_items), handle, None
 
     @property
@@ -332,8 +339,8 @@ def _decode_arrays(data: bytes, arrays: list) -> list:
 
 def reference_bytes(update) -> bytes:
     """Exactly ``msgpack.packb(list_of_ints, default=<reference _default>, strict_types=True)`` for a consistent
-    `EncryptedParams` or a device tensor in either layout (int32 ``[n_ct, 64]``: JL; int64 ``[n]``: LOM), made on
-    the device.  An `EncryptedParams` whose packed form was dropped goes through msgpack like a plain list."""
+    `EncryptedParams` or a device tensor in one of the layouts (int32 ``[n_ct, 64]``: JL; int32 ``[n_ct, 128]``: a
+    wide biprime's JL; int64 ``[n]``: LOM), made on the device.  An `EncryptedParams` whose packed form was dropped goes through msgpack like a plain list."""
     if isinstance(update, EncryptedParams):
         if update.consistent():
             _STATS["fast"] += 1
@@ -347,10 +354,13 @@ def reference_bytes(update) -> bytes:
     if isinstance(update, torch.Tensor) and update.is_cuda:
         if update.dtype == torch.int32 and update.dim() == 2 and update.shape[1] == 64:
             scheme = "jl"
+        elif update.dtype == torch.int32 and update.dim() == 2 and update.shape[1] == 128:
+            scheme = "jlw"
         elif update.dtype == torch.int64 and update.dim() == 1:
             scheme = "lom"
         else:
-            raise ValueError("reference_bytes takes int32 [n_ct, 64] (JL) or int64 [n] (LOM) device tensors")
+            raise ValueError("reference_bytes takes int32 [n_ct, 64] (JL), int32 [n_ct, 128] (wide JL) or int64 [n] "
+                             "(LOM) device tensors")
         _STATS["fast"] += 1
         return _encode_rows(scheme, update)
     raise TypeError("reference_bytes takes an EncryptedParams or a device tensor")
@@ -646,7 +656,8 @@ def _loads_streamed(msg: StreamedMessage, object_hook, min_items: int, resident:
 
 
 def loads_reference(data, object_hook=None, min_items: int = 1024, resident: bool = False,
-                    device_scan_min_items: Optional[int] = None, device_scan_jl_min_items: Optional[int] = None) -> Any:
+                    device_scan_min_items: Optional[int] = None, device_scan_jl_min_items: Optional[int] = None,
+                    jl_limbs: int = 64) -> Any:
     """``msgpack.unpackb(data, object_hook=object_hook, strict_map_key=False)`` with every integer array of at
     least `min_items` items the host scanner records read on the device: it comes back as an `EncryptedParams`
     (which compares as the list of ints msgpack would have made) whose ``packed`` is ready for `aggregate` /
@@ -672,9 +683,23 @@ def loads_reference(data, object_hook=None, min_items: int = 1024, resident: boo
     chunks' slices -- is read as above (a further large array in the tail goes the usual way), and the array comes
     back as a `ResidentUpdate` on the streamed block and table (`reference_stats` counts "streamed").  An array the
     tokenizer refuses (mixed, a negative int, cut off by the message's end) and a reduced message that does not
-    unpack make this the call on ``bytes(data)``, with that call's result or error ("stream_fallback")."""
+    unpack make this the call on ``bytes(data)``, with that call's result or error ("stream_fallback").
+
+    ``jl_limbs=128`` (a deployment whose biprime has 1025 to 2048 bits: ciphertexts below 2^4096): the scan is
+    fbm_wire_scan_jlw, which takes the big-int map with up to 513 value bytes, and an array that holds one comes back
+    as an `EncryptedParams` / `ResidentUpdate` of scheme "jlw" (packed ``[n, 128]``).  Every array is then walked by
+    the host scanner: the device tokenizers keep their 2^2048 domain and are not asked, and a `StreamedMessage` is
+    read from its joined bytes.  With the default 64 nothing changes: a value of 2^2048 or more leaves its array to
+    msgpack."""
+    if jl_limbs not in (64, 128):
+        raise ValueError("jl_limbs must be 64 or 128")
     dmin = DEVICE_SCAN_MIN_ITEMS if device_scan_min_items is None else int(device_scan_min_items)
     jmin = DEVICE_SCAN_JL_MIN_ITEMS if device_scan_jl_min_items is None else int(device_scan_jl_min_items)
+    if jl_limbs == 128:
+        if isinstance(data, StreamedMessage):
+            data._fell_back()
+            data = bytes(data)
+        return _loads_reference(data, object_hook, min_items, resident, dmin, jmin, jl_limbs=128)
     if isinstance(data, StreamedMessage):
         out = _loads_streamed(data, object_hook, min_items, resident, dmin, jmin)
         if out is not _NOT_STREAMED:
@@ -684,7 +709,7 @@ def loads_reference(data, object_hook=None, min_items: int = 1024, resident: boo
 
 
 def _loads_reference(data: bytes, object_hook, min_items: int, resident: bool, dmin: int, jmin: int,
-                     count_plain: bool = True) -> Any:
+                     count_plain: bool = True, jl_limbs: int = 64) -> Any:
     """`loads_reference` for ``bytes``; count_plain: whether a message without arrays counts as "fallback"."""
     import os
     import time
@@ -695,15 +720,15 @@ def _loads_reference(data: bytes, object_hook, min_items: int, resident: bool, d
 
     _LAST.clear()
     held: Dict[int, Any] = {}  # the arrays the device tokenized: index -> handle
-    if resident:
+    if resident and jl_limbs == 64:
         # (an array of maps is this library's only under a hook that reads them: otherwise it never goes up)
         arrays, held = _scan_resident(data, min_items, max(dmin, 1), max(jmin, 1) if _hook_reads_ints(object_hook) else 0)
-    else:
+    else:  # (jl_limbs == 128: the host scanner walks every array, the tokenizers' domain ends at 2^2048)
         t0 = time.perf_counter()
-        arrays = D.wire_scan(data, min_items)
+        arrays = D.wire_scan(data, min_items) if jl_limbs == 64 else D.wire_scan(data, min_items, jl_limbs)
         _LAST["scan"] = time.perf_counter() - t0
     if arrays and not _hook_reads_ints(object_hook):
-        keep = [i for i, a in enumerate(arrays) if a[3] != "jl"]  # (a tokenized "jl" array exists only under such a hook)
+        keep = [i for i, a in enumerate(arrays) if a[3] == "lom"]  # (a tokenized "jl" array exists only under such a hook)
         arrays, held = [arrays[i] for i in keep], {k: held[i] for k, i in enumerate(keep) if i in held}
     if not arrays:
         _STATS["fallback"] += 1 if count_plain else 0

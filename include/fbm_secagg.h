@@ -539,6 +539,44 @@ int fbm_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t
 int fbm_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
                       uint64_t n_ckpt, uint64_t n_items, uint64_t* acc, int first, void* stream);
 
+/* ---- the same for the wide family's ciphertexts (fbm_jlw_*: N^2 < 2^4096; additions to ABI 7) ---------------
+ * A value of 2^2048 or more goes out as the same map with a bin of up to 513 bytes (c5 + BE16): 536 bytes an item.
+ * The entry points above keep their 2^2048 domain and their two schemes; these take rows of 128 limbs.
+ *
+ * fbm_wire_encode_jlw: fbm_wire_encode for rows [n][128] uint32 (device, 8-byte aligned), byte for byte what
+ * packb writes for the same ints (a value below 2^64 in its shortest native form); out_cap >=
+ * fbm_wire_encode_jlw_bound(n) = 5 + 537 n, workspace of fbm_wire_encode_jlw_workspace(n) bytes; the argument
+ * errors are fbm_wire_encode's.
+ *
+ * fbm_wire_scan_jlw: fbm_wire_scan with the map item's bound at 1 <= L <= 513 (a first byte < 0x80, and a zero
+ * first byte where L == 513: a value < 2^4096); every other rule unchanged.  An array that holds at least one map
+ * item is recorded as FBM_WIRE_JLW, one checkpoint per item in FBM_WIRE_JL's form (byte count 1..513); an all-native
+ * array stays FBM_WIRE_LOM.
+ *
+ * fbm_wire_decode_jlw: a recorded FBM_WIRE_JLW array (n_items checkpoints) -> rows [n_items][128] uint32 (device,
+ * 8-byte aligned), zero-padded.  Every read is checked against the span; a checkpoint whose bytes do not lie inside
+ * it, or whose byte count is outside 1..513, gives a zero row.
+ *
+ * fbm_wire_fold_jlw: decode and fold in one pass, into fbm_jlw_fold's accumulator; the rows are never written:
+ *     acc[i] <- (seed_ops > 0 ? 1 : acc[i]) * item i  mod N^2,  i < n_items
+ * acc: device, [n_items][128] uint32, 8-byte aligned, canonical after the call; biprime as fbm_jlw_fold's; workspace:
+ * fbm_jlw_seal_workspace(0) bytes (the modulus' constants; nothing secret).  A checkpoint as above counts as the
+ * value 0; no access falls outside span, ckpt and acc, whatever the table holds.  fbm_jlw_fold's argument checks
+ * (the biprime, n_items <= FBM_JL_MAX_CT, seed_ops >= 0; n_items == 0 is FBM_OK) and fbm_wire_fold_lom's (null
+ * pointers, ckpt and acc off an 8-byte boundary) all come before any kernel. */
+#define FBM_WIRE_JLW 2 /* rows [n][128] uint32, little-endian limbs (one ciphertext < 2^4096 each) */
+uint64_t fbm_wire_encode_jlw_bound(uint64_t n);
+uint64_t fbm_wire_encode_jlw_workspace(uint64_t n);
+int fbm_wire_encode_jlw(const uint32_t* rows, uint64_t n, uint8_t* out, uint64_t out_cap, void* workspace,
+                        uint64_t* total, void* stream);
+int fbm_wire_scan_jlw(const uint8_t* data, uint64_t len, uint64_t min_items, fbm_wire_array* arrays,
+                      uint64_t arrays_cap, uint64_t* n_arrays, uint64_t* ckpt, uint64_t ckpt_cap, uint64_t* n_ckpt);
+int fbm_wire_decode_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                        uint64_t n_items, uint32_t* rows, void* stream);
+int fbm_wire_fold_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                      uint64_t n_items, uint32_t* acc, const uint32_t* biprime, int seed_ops, void* workspace,
+                      void* stream);
+
 /* The table of an all-native array made on the device, so that the host never steps through its items (these
  * three arrived under ABI 7 as well).  The start of an item depends on every length before it: a 9-state
  * automaton over bytes (payload bytes still to skip, plus one absorbing state for a byte that starts no native

@@ -141,6 +141,10 @@ int fbm_test_short_cache(uint32_t* out, int cap_words);
 int fbm_test_wire_encode(int scheme, const void* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total);
 int fbm_test_wire_decode(int scheme, const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
                          uint64_t n_ckpt, uint64_t n_items, void* rows);
+/* the same for fbm_wire_encode_jlw / fbm_wire_decode_jlw (rows of 128 limbs; wire_jlw_byte, wire_jlw_digit_at) */
+int fbm_test_wire_encode_jlw(const uint32_t* rows, uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* total);
+int fbm_test_wire_decode_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,
+                             uint64_t n_items, uint32_t* rows);
 /* fbm_wire_fold_lom over HOST buffers (host_wire_fold_lom, the same per-item routine), same arguments and
  * argument errors. */
 int fbm_test_wire_fold_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, const uint64_t* ckpt,

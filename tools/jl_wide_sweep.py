@@ -17,6 +17,13 @@ alone and a continuing D.jlw_fold of one row, alternating within a repetition, t
 fastest unprepared one:
 
     python tools/jl_wide_sweep.py --seal --out profiles/jl_wide_seal.jsonl
+
+--wire ("wide items"): a stock peer's reply of --items ciphertexts, resident on the device: its decode
+into rows followed by D.jlw_fold, D.wire_fold_jlw straight from the bytes, wire.reference_bytes of the rows, and
+on the host msgpack's unpackb with the reference's hook and packb of the same message; then whether the slowest fused
+run lies below the fastest split one:
+
+    python tools/jl_wide_sweep.py --wire --out profiles/jl_wide_wire.jsonl
 """
 import argparse
 import json
@@ -38,6 +45,8 @@ def main():
     ap.add_argument("--counts", type=int, nargs="+", default=[1, 256, 2048, 4096])
     ap.add_argument("--engine", nargs="+", choices=["auto", "wave", "group"], default=None)
     ap.add_argument("--seal", action="store_true")
+    ap.add_argument("--wire", action="store_true")
+    ap.add_argument("--items", type=int, default=31250)
     args = ap.parse_args()
     import torch
 
@@ -76,6 +85,46 @@ def main():
         rows.append({"what": "seal_summary", "n_ct": n_ct,
                      "slowest_prepared_over_fastest_unprepared": max(ms["encrypt_tensor_factor"]) / min(ms["encrypt_tensor"]),
                      "fold_bytes": 512 * 3 * n_ct, "fold_gb_per_s": 512 * 3 * n_ct / min(ms["jlw_fold_k1"]) / 1e6})
+        return emit(rows, args.out)
+    if args.wire:  # DESIGN 4.2, "wide items": a stock peer's reply of --items full-width ciphertexts
+        import msgpack
+
+        from fedbiomed_amd import wire
+
+        def ref_default(o):  # the reference Serializer's rules (serializer.py:96-110, :140-149)
+            return {"__type__": "int", "value": o.to_bytes((o.bit_length() + 7) // 8 + 1, "big", signed=True)}
+
+        def ref_hook(o):
+            return int.from_bytes(o["value"], "big", signed=True) if o.get("__type__") == "int" else o
+
+        rng = random.Random(5)
+        vals = [rng.randrange(n * n) for _ in range(args.items)]
+        data = msgpack.packb(vals, default=ref_default, strict_types=True)
+        up = wire.loads_reference(data, object_hook=ref_hook, min_items=1, resident=True, jl_limbs=128)
+        acc = D.wire_rows_device(up.handle).clone()
+        rows_buf = torch.empty_like(acc)
+        assert wire.reference_bytes(acc) == data and D.limbs_to_ints_w(acc[:64], 128) == vals[:64]
+        a2 = acc.clone()
+        assert torch.equal(D.wire_fold_jlw(up.handle, a2, n), D.jlw_fold(acc.clone(), acc, n))
+
+        def host_route():
+            msgpack.packb(msgpack.unpackb(data, object_hook=ref_hook, strict_map_key=False), default=ref_default,
+                          strict_types=True)
+
+        legs = [("decode_then_fold", lambda: D.jlw_fold(acc, D.wire_rows_device(up.handle, out=rows_buf), n)),
+                ("wire_fold_jlw", lambda: D.wire_fold_jlw(up.handle, acc, n)),
+                ("reference_bytes", lambda: wire.reference_bytes(rows_buf)),
+                ("host_unpackb_packb", host_route)]
+        for _, fn in legs:
+            timed(fn)
+        for rep in range(args.reps):
+            for what, fn in legs:
+                rows.append({"what": what, "items": args.items, "message_bytes": len(data), "rep": rep,
+                             "n_bits": n.bit_length(), "ms": timed(fn)})
+        ms = {w: [r["ms"] for r in rows if r["what"] == w] for w, _ in legs}
+        rows.append({"what": "wire_summary", "items": args.items,
+                     "slowest_fused_over_fastest_split": max(ms["wire_fold_jlw"]) / min(ms["decode_then_fold"]),
+                     "fused_wins": max(ms["wire_fold_jlw"]) < min(ms["decode_then_fold"])})
         return emit(rows, args.out)
     for n_ct in args.counts if args.engine else []:
         def run_engine(eng):
