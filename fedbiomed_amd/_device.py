@@ -2199,13 +2199,16 @@ def wire_upload(data, arrays: list, timing: Optional[dict] = None) -> List[WireH
             for (b, e, n, scheme, ck), so, co in zip(arrays, s_off, c_off)]
 
 
-def wire_scan_deferred(data, min_items: int, defer_items: int, resolved, defer_jl_items: int = 0) -> Tuple[str, Any]:
+def wire_scan_deferred(data, min_items: int, defer_items: int, resolved, defer_jl_items: int = 0,
+                       jl_limbs: int = 64) -> Tuple[str, Any]:
     """One pass of fbm_wire_scan_deferred2 over a message, no device call: ("pending", (begin, first, n_items)) for
     the deferral candidate that `resolved` (end offsets, 0: walk it on the host) does not answer yet -- with
     `defer_jl_items` the arrays of big-int maps are candidates too and the tuple has the candidate's scheme as a
     fourth entry --, else ("done", arrays) with wire_scan's list -- the checkpoints of an array left to the device
-    are None -- or ("done", None) where the scan gives up."""
+    are None -- or ("done", None) where the scan gives up.  jl_limbs=128: fbm_wire_scan_deferred_jlw -- map items of up
+    to 513 bytes, the scheme of a candidate or an array that holds one "jlw"."""
     lib = N.load()
+    scan = lib.fbm_wire_scan_deferred2 if jl_limbs == 64 else lib.fbm_wire_scan_deferred_jlw
     buf = np.frombuffer(data, dtype=np.uint8)
     n = buf.size
     n_arr, n_ck = ctypes.c_uint64(0), ctypes.c_uint64(0)
@@ -2215,10 +2218,9 @@ def wire_scan_deferred(data, min_items: int, defer_items: int, resolved, defer_j
     for a_cap, c_cap in ((1024, n // 8 + 1024), (n // max(int(min_items), 1) + 1, n + 16)):
         arrays = (N.WireArray * a_cap)()
         ckpt = np.empty(c_cap, dtype=np.uint64)
-        rc = lib.fbm_wire_scan_deferred2(_np_ptr(buf) if n else None, n, max(int(min_items), 1), max(int(defer_items), 0),
-                                         defer_jl_items, _np_ptr(res) if res.size else None, res.size,
-                                         ctypes.addressof(arrays), a_cap, ctypes.addressof(n_arr), _np_ptr(ckpt), c_cap,
-                                         ctypes.addressof(n_ck), ctypes.addressof(pend))
+        rc = scan(_np_ptr(buf) if n else None, n, max(int(min_items), 1), max(int(defer_items), 0), defer_jl_items,
+                  _np_ptr(res) if res.size else None, res.size, ctypes.addressof(arrays), a_cap, ctypes.addressof(n_arr),
+                  _np_ptr(ckpt), c_cap, ctypes.addressof(n_ck), ctypes.addressof(pend))
         if rc == N.FBM_E_RANGE:
             continue
         if rc == N.WIRE_PENDING:
@@ -2235,7 +2237,7 @@ def wire_scan_deferred(data, min_items: int, defer_items: int, resolved, defer_j
 
 def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[dict] = None,
                        counts: Optional[dict] = None, sync_phases: bool = False,
-                       defer_jl_items: int = 0) -> Tuple[Optional[list], dict]:
+                       defer_jl_items: int = 0, jl_limbs: int = 64) -> Tuple[Optional[list], dict]:
     """wire_scan with the arrays of at least `defer_items` native items, and with `defer_jl_items` (0: none) those
     of at least that many big-int maps, tokenized on the device (fbm_wire_scan_deferred2 + fbm_wire_tokenize_lom /
     fbm_wire_tokenize_jl; a "jl" array's table has a word per item).  At the first such array the message from that array's
@@ -2246,7 +2248,8 @@ def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[
     WireHandle per such array under its index; (None, {}) where the scan gives up.  No device call while no array
     qualifies.  timing: receives scan / h2d / devscan seconds (sync_phases: the upload is synchronised, so that h2d
     is its time and not its enqueue); counts: device_scan / device_scan_refused are incremented for a "lom" array,
-    device_scan_jl / device_scan_jl_refused for a "jl" one."""
+    device_scan_jl / device_scan_jl_refused for a "jl" one.  jl_limbs=128: the scan is fbm_wire_scan_deferred_jlw and
+    an array of maps, "jlw", goes through fbm_wire_tokenize_jlw (counted under the "jl" keys)."""
     import time
 
     lib = N.load()
@@ -2257,13 +2260,13 @@ def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[
     t_scan = t_h2d = t_dev = 0.0
     while True:
         t0 = time.perf_counter()
-        kind, val = wire_scan_deferred(data, min_items, defer_items, resolved, defer_jl_items)
+        kind, val = wire_scan_deferred(data, min_items, defer_items, resolved, defer_jl_items, jl_limbs)
         t_scan += time.perf_counter() - t0
         if kind != "pending":
             arrays = val
             break
         begin, first, n_items = val[:3]
-        jl = len(val) > 3 and val[3] == "jl"
+        jl = len(val) > 3 and val[3] != "lom"
         t0 = time.perf_counter()
         if blk is None:
             dev, blk_base = device(), begin
@@ -2277,8 +2280,9 @@ def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[
         t_h2d += t1 - t0
         n_ck = n_items if jl else (n_items + N.WIRE_LOM_GROUP - 1) // N.WIRE_LOM_GROUP
         span_len = size - blk_base
-        ws_bytes, tokenize = (lib.fbm_wire_tokenize_jl_workspace, lib.fbm_wire_tokenize_jl) if jl else \
-            (lib.fbm_wire_tokenize_workspace, lib.fbm_wire_tokenize_lom)
+        ws_bytes, tokenize = (lib.fbm_wire_tokenize_workspace, lib.fbm_wire_tokenize_lom) if not jl else \
+            (lib.fbm_wire_tokenize_jl_workspace, lib.fbm_wire_tokenize_jl) if val[3] == "jl" else \
+            (lib.fbm_wire_tokenize_jlw_workspace, lib.fbm_wire_tokenize_jlw)
         with torch.cuda.device(dev):
             tab = torch.empty(n_ck, dtype=torch.int64, device=dev)
             res = torch.empty(2, dtype=torch.int64, device=dev)
@@ -2312,15 +2316,17 @@ def wire_scan_resident(data, min_items: int, defer_items: int, timing: Optional[
     return arrays, handles
 
 
-def wire_scan_prefix(data, min_items: int, defer_items: int, defer_jl_items: int = 0) -> Tuple[str, Any]:
+def wire_scan_prefix(data, min_items: int, defer_items: int, defer_jl_items: int = 0, jl_limbs: int = 64) -> Tuple[str, Any]:
     """fbm_wire_scan_prefix over the first bytes of a message, no device call: ("pending", (begin, first, n_items,
     scheme)) once they hold the message's first deferral candidate, ("more", None) while they do not decide,
-    ("none", None) where they are a whole message without one and ("bad", None) where no further byte mends them."""
+    ("none", None) where they are a whole message without one and ("bad", None) where no further byte mends them.
+    jl_limbs=128: fbm_wire_scan_prefix_jlw (map items of up to 513 bytes; a candidate of maps is "jlw")."""
     lib = N.load()
     buf = np.frombuffer(data, dtype=np.uint8)
     pend = N.WirePending2()
-    rc = lib.fbm_wire_scan_prefix(_np_ptr(buf) if buf.size else None, buf.size, max(int(min_items), 1), max(int(defer_items), 0),
-                                  max(int(defer_jl_items), 0), ctypes.addressof(pend))
+    scan = lib.fbm_wire_scan_prefix if jl_limbs == 64 else lib.fbm_wire_scan_prefix_jlw
+    rc = scan(_np_ptr(buf) if buf.size else None, buf.size, max(int(min_items), 1), max(int(defer_items), 0),
+              max(int(defer_jl_items), 0), ctypes.addressof(pend))
     if rc == N.WIRE_PENDING:
         return "pending", (int(pend.begin), int(pend.first), int(pend.n_items), _WIRE_NAME[pend.scheme])
     if rc == N.WIRE_MORE:
@@ -2356,13 +2362,14 @@ class WireStream:
     copies a chunk's share of it into a pinned staging buffer and from there into the block, then feeds the
     tokenizer what has become final -- all on `ctx`'s stream, which the caller owns and keeps from message to message
     with the staging ring (`ctx`: a dict this class fills).  Nothing synchronises the device before `result`; a
-    staging buffer is waited for only where its own copy, WIRE_STREAM_SLOTS chunks ago, has not finished."""
+    staging buffer is waited for only where its own copy, WIRE_STREAM_SLOTS chunks ago, has not finished.  Scheme "jlw":
+    fbm_wire_stream_begin_jlw / fbm_wire_stream_feed_jlw, a table word per item as for "jl"."""
 
     def __init__(self, scheme: str, begin: int, first: int, n_items: int, cap: int, ctx: dict):
         self.scheme, self.begin, self.first, self.n, self.cap = scheme, begin, first, n_items, cap
         self.failed, self._ctx, self._lib = False, ctx, N.load()
         self.device = dev = device()
-        self.n_ckpt = n_items if scheme == "jl" else (n_items + N.WIRE_LOM_GROUP - 1) // N.WIRE_LOM_GROUP
+        self.n_ckpt = n_items if scheme != "lom" else (n_items + N.WIRE_LOM_GROUP - 1) // N.WIRE_LOM_GROUP
         with torch.cuda.device(dev):
             if ctx.get("stream") is None:
                 ctx["stream"], ctx["ring"], ctx["at"] = torch.cuda.Stream(dev), [], 0
@@ -2372,9 +2379,15 @@ class WireStream:
                 self.blk = torch.empty(cap - begin, dtype=torch.uint8, device=dev)
                 self.tab = torch.empty(self.n_ckpt, dtype=torch.int64, device=dev)
                 self.state = torch.empty(N.WIRE_STREAM_STATE_WORDS, dtype=torch.int64, device=dev)
-                self.ws = torch.empty(int(self._lib.fbm_wire_stream_workspace(sch, cap - begin)), dtype=torch.uint8, device=dev)
-                _call(self._lib.fbm_wire_stream_begin, sch, first, n_items, _ptr(self.state),
-                      ctypes.c_void_p(self.stream.cuda_stream))
+                ws_bytes = self._lib.fbm_wire_stream_jlw_workspace(cap - begin) if scheme == "jlw" else \
+                    self._lib.fbm_wire_stream_workspace(sch, cap - begin)
+                self.ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+                if scheme == "jlw":  # (entry points of its own: the narrow ones keep their two schemes)
+                    _call(self._lib.fbm_wire_stream_begin_jlw, first, n_items, _ptr(self.state),
+                          ctypes.c_void_p(self.stream.cuda_stream))
+                else:
+                    _call(self._lib.fbm_wire_stream_begin, sch, first, n_items, _ptr(self.state),
+                          ctypes.c_void_p(self.stream.cuda_stream))
 
     def _slot(self, nbytes: int) -> torch.Tensor:
         ring, at = self._ctx["ring"], self._ctx["at"]
@@ -2408,9 +2421,10 @@ class WireStream:
                 slot[1] = torch.cuda.Event()
                 slot[1].record(self.stream)
             if feed:
-                rc = self._lib.fbm_wire_stream_feed(_WIRE_SCHEME[self.scheme], _ptr(self.blk), self.begin, avail, 1 if last else 0,
-                                                    _ptr(self.tab), self.n_ckpt, _ptr(self.state), _ptr(self.ws),
-                                                    ctypes.c_void_p(self.stream.cuda_stream))
+                feed_args = (_ptr(self.blk), self.begin, avail, 1 if last else 0, _ptr(self.tab), self.n_ckpt, _ptr(self.state),
+                             _ptr(self.ws), ctypes.c_void_p(self.stream.cuda_stream))
+                rc = self._lib.fbm_wire_stream_feed_jlw(*feed_args) if self.scheme == "jlw" else \
+                    self._lib.fbm_wire_stream_feed(_WIRE_SCHEME[self.scheme], *feed_args)
                 if rc != N.FBM_OK:
                     self.failed = True
                     if rc not in (N.FBM_E_ARG, N.FBM_E_UNSUPPORTED):

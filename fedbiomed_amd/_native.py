@@ -177,6 +177,15 @@ SIGNATURES = {
     "fbm_wire_stream_begin": (c_int, [c_int, c_u64, c_u64, c_vp, c_vp]),
     "fbm_wire_stream_feed": (c_int, [c_int, c_vp, c_u64, c_u64, c_int, c_vp, c_u64, c_vp, c_vp, c_vp]),
     "fbm_wire_scan_prefix": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp]),
+    # the wide family's arrays tokenized on the device, at once or chunk by chunk (additions to ABI 7)
+    "fbm_wire_tokenize_jlw_workspace": (c_u64, [c_u64]),
+    "fbm_wire_tokenize_jlw": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]),
+    "fbm_wire_scan_deferred_jlw": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64,
+                                           c_vp, c_vp]),
+    "fbm_wire_scan_prefix_jlw": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp]),
+    "fbm_wire_stream_jlw_workspace": (c_u64, [c_u64]),
+    "fbm_wire_stream_begin_jlw": (c_int, [c_u64, c_u64, c_vp, c_vp]),
+    "fbm_wire_stream_feed_jlw": (c_int, [c_vp, c_u64, c_u64, c_int, c_vp, c_u64, c_vp, c_vp, c_vp]),
 }
 WIRE_MORE = 2  # FBM_WIRE_MORE
 WIRE_STREAM_STATE_WORDS = 16  # FBM_WIRE_STREAM_STATE_WORDS
@@ -240,6 +249,9 @@ TEST_SIGNATURES = {
     "fbm_test_wire_tokenize_jl": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
     "fbm_test_wire_stream_begin": (c_int, [c_int, c_u64, c_u64, c_vp]),
     "fbm_test_wire_stream_feed": (c_int, [c_int, c_vp, c_u64, c_u64, c_int, c_vp, c_u64, c_vp, c_vp]),
+    "fbm_test_wire_tokenize_jlw": (c_int, [c_vp, c_u64, c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
+    "fbm_test_wire_stream_begin_jlw": (c_int, [c_u64, c_u64, c_vp]),
+    "fbm_test_wire_stream_feed_jlw": (c_int, [c_vp, c_u64, c_u64, c_int, c_vp, c_u64, c_vp, c_vp]),
     "fbm_prof_enable": (c_int, [c_int]),
     "fbm_prof_report": (c_int, [ctypes.c_char_p, c_int]),
 }

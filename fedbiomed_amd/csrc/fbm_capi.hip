@@ -1864,6 +1864,19 @@ int fbm_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t span_b
   });
 }
 
+uint64_t fbm_wire_tokenize_jlw_workspace(uint64_t span_len) { return wire_tokenize_jlw_workspace(span_len); }
+
+int fbm_wire_tokenize_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first, uint64_t n_items,
+                          uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n_items == 0) return FBM_OK;
+  int rc = wire_tokenize_checks(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace, 1);
+  if (rc) return rc;
+  return timed("wire_tokenize_jlw", s, [&] {
+    return launch_wire_tokenize_jlw(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace, s);
+  });
+}
+
 int fbm_wire_scan_deferred(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items,
                            const uint64_t* resolved, uint64_t n_resolved, fbm_wire_array* arrays, uint64_t arrays_cap,
                            uint64_t* n_arrays, uint64_t* ckpt, uint64_t ckpt_cap, uint64_t* n_ckpt,
@@ -1875,16 +1888,18 @@ int fbm_wire_scan_deferred(const uint8_t* data, uint64_t len, uint64_t min_items
   return rc;
 }
 
-int fbm_wire_scan_deferred2(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items,
-                            uint64_t defer_items_jl, const uint64_t* resolved, uint64_t n_resolved,
-                            fbm_wire_array* arrays, uint64_t arrays_cap, uint64_t* n_arrays, uint64_t* ckpt,
-                            uint64_t ckpt_cap, uint64_t* n_ckpt, fbm_wire_pending2* pending) {
+// fbm_wire_scan_deferred2 and fbm_wire_scan_deferred_jlw: the pass under the map items' bound and scheme
+static int wire_scan_deferred_run(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items,
+                                  uint64_t defer_items_jl, const uint64_t* resolved, uint64_t n_resolved,
+                                  fbm_wire_array* arrays, uint64_t arrays_cap, uint64_t* n_arrays, uint64_t* ckpt,
+                                  uint64_t ckpt_cap, uint64_t* n_ckpt, fbm_wire_pending2* pending, uint32_t max_vlen,
+                                  int32_t map_scheme) {
   if ((len > 0 && !data) || !n_arrays || !n_ckpt || (arrays_cap > 0 && !arrays) || (ckpt_cap > 0 && !ckpt) ||
       ((defer_items > 0 || defer_items_jl > 0) && (!pending || (n_resolved > 0 && !resolved)))) {
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
-  fbm_wire_scan_out o = {arrays, arrays_cap, 0, ckpt, ckpt_cap, 0};
+  fbm_wire_scan_out o = {arrays, arrays_cap, 0, ckpt, ckpt_cap, 0, max_vlen, map_scheme};
   const fbm_wire_defer df = {defer_items, resolved, n_resolved, nullptr, defer_items_jl, pending};
   const int r = fbm_wire_scan_run(data, len, min_items, &o, &df);
   *n_arrays = o.n_arrays, *n_ckpt = o.n_ckpt;
@@ -1904,13 +1919,29 @@ int fbm_wire_scan_deferred2(const uint8_t* data, uint64_t len, uint64_t min_item
   return FBM_OK;
 }
 
-int fbm_wire_scan_prefix(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
-                         uint64_t defer_items_jl, fbm_wire_pending2* pending) {
+int fbm_wire_scan_deferred2(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items,
+                            uint64_t defer_items_jl, const uint64_t* resolved, uint64_t n_resolved,
+                            fbm_wire_array* arrays, uint64_t arrays_cap, uint64_t* n_arrays, uint64_t* ckpt,
+                            uint64_t ckpt_cap, uint64_t* n_ckpt, fbm_wire_pending2* pending) {
+  return wire_scan_deferred_run(data, len, min_items, defer_items, defer_items_jl, resolved, n_resolved, arrays, arrays_cap,
+                                n_arrays, ckpt, ckpt_cap, n_ckpt, pending, FBM_WIRE_JL_MAX_VLEN, FBM_WIRE_JL);
+}
+
+int fbm_wire_scan_deferred_jlw(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items,
+                               uint64_t defer_items_jlw, const uint64_t* resolved, uint64_t n_resolved,
+                               fbm_wire_array* arrays, uint64_t arrays_cap, uint64_t* n_arrays, uint64_t* ckpt,
+                               uint64_t ckpt_cap, uint64_t* n_ckpt, fbm_wire_pending2* pending) {
+  return wire_scan_deferred_run(data, len, min_items, defer_items, defer_items_jlw, resolved, n_resolved, arrays, arrays_cap,
+                                n_arrays, ckpt, ckpt_cap, n_ckpt, pending, FBM_WIRE_JLW_MAX_VLEN, FBM_WIRE_JLW);
+}
+
+static int wire_scan_prefix_run(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
+                                uint64_t defer_items_jl, fbm_wire_pending2* pending, uint32_t max_vlen, int32_t map_scheme) {
   if ((len > 0 && !data) || !pending) {
     set_error("null pointer argument");
     return FBM_E_ARG;
   }
-  const int r = fbm_wire_scan_prefix_run(data, len, min_items, defer_items_lom, defer_items_jl, pending);
+  const int r = fbm_wire_scan_prefix_run(data, len, min_items, defer_items_lom, defer_items_jl, pending, max_vlen, map_scheme);
   if (r == FBM_WIRE_SCAN_PENDING) return FBM_WIRE_PENDING;
   if (r == FBM_WIRE_SCAN_MORE) return FBM_WIRE_MORE;
   if (r == FBM_WIRE_SCAN_GAVE_UP) {
@@ -1918,6 +1949,16 @@ int fbm_wire_scan_prefix(const uint8_t* data, uint64_t len, uint64_t min_items, 
     return FBM_E_UNSUPPORTED;
   }
   return FBM_OK;
+}
+
+int fbm_wire_scan_prefix(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
+                         uint64_t defer_items_jl, fbm_wire_pending2* pending) {
+  return wire_scan_prefix_run(data, len, min_items, defer_items_lom, defer_items_jl, pending, FBM_WIRE_JL_MAX_VLEN, FBM_WIRE_JL);
+}
+
+int fbm_wire_scan_prefix_jlw(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
+                             uint64_t defer_items_jlw, fbm_wire_pending2* pending) {
+  return wire_scan_prefix_run(data, len, min_items, defer_items_lom, defer_items_jlw, pending, FBM_WIRE_JLW_MAX_VLEN, FBM_WIRE_JLW);
 }
 
 }  // extern "C"
@@ -1945,9 +1986,10 @@ wire_stream_rec* wire_stream_find(uint64_t* state) {  // (the mutex held)
 }
 }  // namespace
 
-// the argument checks fbm_wire_stream_begin / _feed and their host hooks share
-static int wire_stream_begin_checks(int scheme, uint64_t n_items, const uint64_t* state) {
-  if (scheme != FBM_WIRE_JL && scheme != FBM_WIRE_LOM) {
+// the argument checks fbm_wire_stream_begin / _feed and their host hooks share (wide: the _jlw entry points, whose
+// scheme is FBM_WIRE_JLW; the narrow ones refuse it like any other value)
+static int wire_stream_begin_checks(int scheme, uint64_t n_items, const uint64_t* state, bool wide = false) {
+  if (wide ? scheme != FBM_WIRE_JLW : scheme != FBM_WIRE_JL && scheme != FBM_WIRE_LOM) {
     set_error("fbm_wire_stream_begin: scheme=%d must be FBM_WIRE_JL or FBM_WIRE_LOM", scheme);
     return FBM_E_ARG;
   }
@@ -1967,8 +2009,8 @@ static int wire_stream_begin_checks(int scheme, uint64_t n_items, const uint64_t
 }
 
 static int wire_stream_feed_checks(int scheme, const uint8_t* span, uint64_t avail_len, const uint64_t* ckpt, uint64_t n_ckpt,
-                                   const uint64_t* state, const void* workspace, const uint64_t* rec) {
-  if (scheme != FBM_WIRE_JL && scheme != FBM_WIRE_LOM) {
+                                   const uint64_t* state, const void* workspace, const uint64_t* rec, bool wide = false) {
+  if (wide ? scheme != FBM_WIRE_JLW : scheme != FBM_WIRE_JL && scheme != FBM_WIRE_LOM) {
     set_error("fbm_wire_stream_feed: scheme=%d must be FBM_WIRE_JL or FBM_WIRE_LOM", scheme);
     return FBM_E_ARG;
   }
@@ -1985,7 +2027,7 @@ static int wire_stream_feed_checks(int scheme, const uint8_t* span, uint64_t ava
     return FBM_E_ARG;
   }
   if (rec[FBM_WIRE_SEG_SCHEME] == (uint64_t)scheme + 1) {  // (any other: wire_seg_plan_of's refusal)
-    const uint64_t n = rec[FBM_WIRE_SEG_ITEMS], group = scheme == FBM_WIRE_JL ? 1 : FBM_WIRE_LOM_GROUP;
+    const uint64_t n = rec[FBM_WIRE_SEG_ITEMS], group = scheme == FBM_WIRE_LOM ? FBM_WIRE_LOM_GROUP : 1;
     if (n_ckpt != (n + group - 1) / group) {
       set_error("fbm_wire_stream_feed: %llu checkpoints for %llu items (one per %llu items)", (unsigned long long)n_ckpt,
                 (unsigned long long)n, (unsigned long long)group);
@@ -1999,15 +2041,10 @@ static int wire_stream_feed_checks(int scheme, const uint8_t* span, uint64_t ava
   return FBM_OK;
 }
 
-extern "C" {
-
-uint64_t fbm_wire_stream_workspace(int scheme, uint64_t cap_len) {
-  return scheme == FBM_WIRE_JL ? wire_tokenize_jl_workspace(cap_len) : wire_tokenize_workspace(cap_len);
-}
-
-int fbm_wire_stream_begin(int scheme, uint64_t first, uint64_t n_items, uint64_t* state, void* stream) {
+// fbm_wire_stream_begin / _feed and their _jlw twins
+static int wire_stream_begin_run(int scheme, uint64_t first, uint64_t n_items, uint64_t* state, void* stream, bool wide) {
   hipStream_t s = (hipStream_t)stream;
-  int rc = wire_stream_begin_checks(scheme, n_items, state);
+  int rc = wire_stream_begin_checks(scheme, n_items, state, wide);
   if (rc) return rc;
   rc = timed("wire_stream_begin", s, [&] { return launch_wire_stream_begin(scheme, first, n_items, state, s); });
   if (rc) return rc;
@@ -2024,8 +2061,8 @@ int fbm_wire_stream_begin(int scheme, uint64_t first, uint64_t n_items, uint64_t
   return FBM_OK;
 }
 
-int fbm_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last, uint64_t* ckpt,
-                         uint64_t n_ckpt, uint64_t* state, void* workspace, void* stream) {
+static int wire_stream_feed_run(int scheme, const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last, uint64_t* ckpt,
+                                uint64_t n_ckpt, uint64_t* state, void* workspace, void* stream, bool wide) {
   hipStream_t s = (hipStream_t)stream;
   uint64_t rec[FBM_WIRE_STREAM_STATE_WORDS];
   bool have = false;
@@ -2033,7 +2070,7 @@ int fbm_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, ui
     std::lock_guard<std::mutex> lock(g_wire_streams_mu);
     if (wire_stream_rec* r = state ? wire_stream_find(state) : nullptr) memcpy(rec, r->rec, sizeof rec), have = true;
   }
-  int rc = wire_stream_feed_checks(scheme, span, avail_len, ckpt, n_ckpt, state, workspace, have ? rec : nullptr);
+  int rc = wire_stream_feed_checks(scheme, span, avail_len, ckpt, n_ckpt, state, workspace, have ? rec : nullptr, wide);
   if (rc) return rc;
   wire_seg_plan p;
   if (const char* err = wire_seg_plan_of(rec, scheme, span, span_base, avail_len, last, &p)) {
@@ -2055,6 +2092,32 @@ int fbm_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, ui
       memcpy(r->rec, rec, sizeof rec);
   }
   return FBM_OK;
+}
+
+extern "C" {
+
+uint64_t fbm_wire_stream_workspace(int scheme, uint64_t cap_len) {
+  return scheme == FBM_WIRE_JL ? wire_tokenize_jl_workspace(cap_len) : wire_tokenize_workspace(cap_len);
+}
+
+int fbm_wire_stream_begin(int scheme, uint64_t first, uint64_t n_items, uint64_t* state, void* stream) {
+  return wire_stream_begin_run(scheme, first, n_items, state, stream, false);
+}
+
+int fbm_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last, uint64_t* ckpt,
+                         uint64_t n_ckpt, uint64_t* state, void* workspace, void* stream) {
+  return wire_stream_feed_run(scheme, span, span_base, avail_len, last, ckpt, n_ckpt, state, workspace, stream, false);
+}
+
+uint64_t fbm_wire_stream_jlw_workspace(uint64_t cap_len) { return wire_tokenize_jlw_workspace(cap_len); }
+
+int fbm_wire_stream_begin_jlw(uint64_t first, uint64_t n_items, uint64_t* state, void* stream) {
+  return wire_stream_begin_run(FBM_WIRE_JLW, first, n_items, state, stream, true);
+}
+
+int fbm_wire_stream_feed_jlw(const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last, uint64_t* ckpt,
+                             uint64_t n_ckpt, uint64_t* state, void* workspace, void* stream) {
+  return wire_stream_feed_run(FBM_WIRE_JLW, span, span_base, avail_len, last, ckpt, n_ckpt, state, workspace, stream, true);
 }
 
 }  // extern "C"
@@ -2108,6 +2171,14 @@ int fbm_test_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t s
   return rc;
 }
 
+int fbm_test_wire_tokenize_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
+                               uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  if (n_items == 0) return FBM_OK;
+  int rc = wire_tokenize_checks(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace, 1);
+  if (rc == FBM_OK) host_wire_tokenize_jlw(span, span_len, span_base, first, n_items, ckpt, n_ckpt, result, workspace);
+  return rc;
+}
+
 int fbm_test_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
                                uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
   if (n_items == 0) return FBM_OK;
@@ -2127,6 +2198,23 @@ int fbm_test_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_bas
   int rc = wire_stream_feed_checks(scheme, span, avail_len, ckpt, n_ckpt, state, workspace, state);
   if (rc) return rc;
   if (const char* err = wire_seg_host_feed(scheme, span, span_base, avail_len, last, ckpt, n_ckpt, state, workspace)) {
+    set_error("fbm_wire_stream_feed: %s", err);
+    return FBM_E_ARG;
+  }
+  return FBM_OK;
+}
+
+int fbm_test_wire_stream_begin_jlw(uint64_t first, uint64_t n_items, uint64_t* state) {
+  int rc = wire_stream_begin_checks(FBM_WIRE_JLW, n_items, state, true);
+  if (rc == FBM_OK) wire_seg_begin(FBM_WIRE_JLW, first, n_items, state);
+  return rc;
+}
+
+int fbm_test_wire_stream_feed_jlw(const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last, uint64_t* ckpt,
+                                  uint64_t n_ckpt, uint64_t* state, void* workspace) {
+  int rc = wire_stream_feed_checks(FBM_WIRE_JLW, span, avail_len, ckpt, n_ckpt, state, workspace, state, true);
+  if (rc) return rc;
+  if (const char* err = wire_seg_host_feed(FBM_WIRE_JLW, span, span_base, avail_len, last, ckpt, n_ckpt, state, workspace)) {
     set_error("fbm_wire_stream_feed: %s", err);
     return FBM_E_ARG;
   }

@@ -381,6 +381,12 @@ int launch_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t bas
                             uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s);
 void host_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
                            uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
+// fbm_wire_tokenize_jlw: the same for an array of wide big-int maps (values below 2^4096; a tile's map is 32 words)
+uint64_t wire_tokenize_jlw_workspace(uint64_t span_len);
+int launch_wire_tokenize_jlw(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                             uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s);
+void host_wire_tokenize_jlw(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                            uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
 bool wire_tokenize_fits(uint64_t span_len);
 int launch_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
                              uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s);

@@ -31,6 +31,7 @@
 //   wire_tok_*_kernel      the FBM_WIRE_LOM table itself, made on the device from the array's bytes
 //                           (fbm_wire_tokenize_lom): see "tokenize" below
 //   wire_tokj_*_kernel     the FBM_WIRE_JL table of an array of big-int maps (fbm_wire_tokenize_jl): "tokenize (JL)"
+//   wire_jlwtok_*_kernel   the FBM_WIRE_JLW table of an array of wide big-int maps (fbm_wire_tokenize_jlw): "tokenize (JLW)"
 // Every read of the message is checked against its length and every write against the output's capacity,
 // whatever the table holds.
 #include "fbm_internal.hpp"
@@ -637,6 +638,131 @@ __global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_tokj_emit_kernel(const ui
   if (lane == 0 && end >= 0) result[1] = (uint64_t)((int64_t)base + tbase + end);
 }
 
+// ---- tokenize (JLW): the table of an array of wide big-int maps made on the device (fbm_wire_tokenize_jlw) -----
+// The three launches above for items of up to 536 bytes (fbm_wire.hpp, "tokenize (JLW)"): the same tiles, one wave per
+// tile and four tiles per workgroup, the same staging (wire_tokj_stage).  What the reach changes:
+//   1. wire_jlwtok_maps_kernel  lane l tests the entry offsets l, l + 64, .. < 536 -- nine rounds -- and a ballot packs
+//                               the <= 27 matches into the tile's 32 slots
+//   2. wire_jlwtok_scan_kernel  one workgroup of FBM_WIRE_SCAN_THREADS threads; a thread's composites from its first
+//                               tile's 32 entries lie in LDS as [slot][thread] 8-byte states
+//   3. wire_jlwtok_emit_kernel  lane 0 walks the tile's items (8 of full width, 179 at most) from its entry state
+// Algorithmic bytes: the stream read twice, 136 bytes per tile written and read back, 8 per item written.
+// LDS: pass 1 16512 bytes and pass 3 22272 bytes, as the JL tokenizer's; pass 2 (FBM_WIRE_JLWTOK_SLOTS + 1) 8-byte words
+// per thread, 67584 bytes: more than 64 KiB, which one workgroup of a gfx950 CU (160 KiB of LDS) may hold, and the
+// scan is one workgroup.  Bound: as the JL tokenizer's, a dependent walk per tile by one lane.
+static_assert(FBM_WIRE_JLWTOK_REACH <= 9 * 64, "nine rounds of 64 lanes cover the entry offsets");
+static_assert(FBM_WIRE_SCAN_THREADS == FBM_WIRE_TOK_SCAN_THREADS, "wire_tok_run cuts the runs of the scan's threads");
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_jlwtok_maps_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                          int64_t origin, uint64_t tiles,
+                                                                          uint32_t* __restrict__ maps) {
+  __shared__ uint32_t sh_tile[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOKJ_WORDS];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t tile = (uint64_t)blockIdx.x * FBM_WIRE_TOK_WAVES + wave;
+  const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+  wire_tokj_stage(span, span_len, tbase, sh_tile[wave]);
+  if (tile >= tiles) return;  // (the whole wave)
+  const uint32_t* w = sh_tile[wave];
+  const int64_t left = (int64_t)span_len - tbase;
+  uint32_t used = 0;
+#pragma unroll 1
+  for (int r = 0; r < (FBM_WIRE_JLWTOK_REACH + 63) / 64; ++r) {
+    const uint32_t e = (uint32_t)(r * 64 + lane);
+    const bool match = e < FBM_WIRE_JLWTOK_REACH && wire_tokj_prefix(w, e);
+    const uint64_t found = __ballot(match);
+    if (match) {
+      const uint32_t slot = used + (uint32_t)__builtin_popcountll(found & ((1ull << lane) - 1ull));
+      if (slot < FBM_WIRE_JLWTOK_SLOTS) {  // (always: matches are 20 bytes apart)
+        uint32_t items = 0;
+        const uint32_t exit = wire_jlwtok_chain(w, e, left, &items);
+        maps[tile * FBM_WIRE_JLWTOK_SLOTS + slot] = wire_jlwtok_entry(e, exit, items);
+      }
+    }
+    used += (uint32_t)__builtin_popcountll(found);
+  }
+  if (lane < FBM_WIRE_JLWTOK_SLOTS && (uint32_t)lane >= used) maps[tile * FBM_WIRE_JLWTOK_SLOTS + lane] = ~0u;
+}
+
+// (wire_jlwtok_scan_body: in() and out(st) as wire_tok_scan_body's; wire_jlwtok_scan_kernel and wire_jlwseg_scan_kernel)
+template <class In, class Out>
+__device__ __forceinline__ void wire_jlwtok_scan_body(const uint32_t* __restrict__ maps, uint64_t tiles,
+                                                      uint64_t* __restrict__ entry, In in, Out out) {
+  __shared__ uint64_t comp[FBM_WIRE_JLWTOK_SLOTS][FBM_WIRE_SCAN_THREADS];  // [slot][thread]: consecutive threads, consecutive banks
+  __shared__ uint64_t ent[FBM_WIRE_SCAN_THREADS];
+  const int t = threadIdx.x;
+  uint64_t b0, b1;
+  wire_tok_run(tiles, t, &b0, &b1);
+#pragma unroll 1
+  for (int k = 0; k < FBM_WIRE_JLWTOK_SLOTS; ++k) {
+    uint64_t s = FBM_WIRE_TOKJ_GONE;
+    if (b0 < b1) {
+      const uint32_t m = maps[b0 * FBM_WIRE_JLWTOK_SLOTS + k];
+      if (m != ~0u) {
+        s = (uint64_t)(m & 0x3ffu);
+#pragma unroll 1
+        for (uint64_t b = b0; b < b1 && (s & 0xffffull) != FBM_WIRE_TOKJ_GONE; ++b) s = wire_jlwtok_apply(s, maps + b * FBM_WIRE_JLWTOK_SLOTS);
+      }
+    }
+    comp[k][t] = s;
+  }
+  __syncthreads();
+  if (t == 0) {
+    uint64_t st = in();
+#pragma unroll 1
+    for (int u = 0; u < FBM_WIRE_SCAN_THREADS; ++u) {
+      ent[u] = st;
+      uint64_t c0, c1;
+      wire_tok_run(tiles, u, &c0, &c1);
+      if (c0 < c1) st = wire_jlwtok_apply_run(st, maps + c0 * FBM_WIRE_JLWTOK_SLOTS, &comp[0][u], FBM_WIRE_SCAN_THREADS);
+    }
+    out(st);
+  }
+  __syncthreads();
+  uint64_t st = ent[t];
+#pragma unroll 1
+  for (uint64_t b = b0; b < b1; ++b) {
+    entry[b] = st;
+    st = wire_jlwtok_apply(st, maps + b * FBM_WIRE_JLWTOK_SLOTS);
+  }
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_jlwtok_scan_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
+                                                                                 uint32_t head, uint64_t n,
+                                                                                 uint64_t* __restrict__ entry,
+                                                                                 uint64_t* __restrict__ result) {
+  wire_jlwtok_scan_body(maps, tiles, entry, [&] { return (uint64_t)head; }, [&](uint64_t st) {
+    result[0] = (st >> 16) < n ? (st >> 16) : n;
+    result[1] = 0;  // wire_jlwtok_emit_kernel writes the end where item n - 1 is one of the chain's
+  });
+}
+
+__global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_jlwtok_emit_kernel(const uint8_t* __restrict__ span, uint64_t span_len,
+                                                                          int64_t origin, uint64_t tiles,
+                                                                          const uint64_t* __restrict__ entry, uint64_t base,
+                                                                          uint64_t n, uint64_t* __restrict__ ckpt,
+                                                                          uint64_t n_ckpt, uint64_t* __restrict__ result) {
+  __shared__ uint32_t sh_tile[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOKJ_WORDS];
+  __shared__ uint64_t sh_out[FBM_WIRE_TOK_WAVES][FBM_WIRE_TOKJ_ITEMS];
+  __shared__ int sh_meta[FBM_WIRE_TOK_WAVES][2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t tile = (uint64_t)blockIdx.x * FBM_WIRE_TOK_WAVES + wave;
+  const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+  wire_tokj_stage(span, span_len, tbase, sh_tile[wave]);
+  const uint64_t st = tile < tiles ? entry[tile] : FBM_WIRE_TOKJ_GONE;
+  if (lane == 0) {
+    int end = -1;
+    const uint32_t cnt = wire_jlwtok_emit_walk(sh_tile[wave], st, (int64_t)span_len - tbase, (int64_t)base + tbase, n, sh_out[wave], &end);
+    sh_meta[wave][0] = (int)cnt, sh_meta[wave][1] = end;
+  }
+  __syncthreads();
+  const uint32_t cnt = (uint32_t)sh_meta[wave][0];
+  const int end = sh_meta[wave][1];
+  const uint64_t k0 = st >> 16;
+  for (uint32_t j = lane; j < cnt; j += 64)
+    if (k0 + j < n_ckpt) ckpt[k0 + j] = sh_out[wave][j];
+  if (lane == 0 && end >= 0) result[1] = (uint64_t)((int64_t)base + tbase + end);
+}
+
 // ---- the tokenizers as resumable scans (fbm_wire_stream_feed) --------------------------------------------------
 // fbm_wire.hpp has the stream's record and which tiles a feed runs.  A feed is the one-shot call's three launches over
 // its tiles [lo, hi): the maps and emit kernels above, given tile lo's span offset as their origin, and between them a
@@ -645,7 +771,7 @@ __global__ void __launch_bounds__(FBM_WIRE_BLOCK) wire_tokj_emit_kernel(const ui
 //       reading its entry state from state[CARRY] (fresh: the stream's first tiles, `head`) and writing the state behind
 //       the segment back there, result[0] beside it -- and leaving result[1] alone: wire_seg_begin_kernel zeroed it and
 //       the one emit launch whose tiles hold item n - 1's start writes it
-// LDS: the one-shot scans' (LOM 22528 bytes, JL 34816 bytes).  Bound: their runs' dependent loads, as the one-shot's.
+// LDS: the one-shot scans' (LOM 22528 bytes, JL 34816 bytes, JLW 67584 bytes).  Bound: their runs' dependent loads, as the one-shot's.
 __global__ void wire_seg_begin_kernel(uint64_t* __restrict__ state, uint64_t first, uint64_t n, uint64_t scheme) {
   const int t = threadIdx.x;
   if (t >= FBM_WIRE_STREAM_STATE_WORDS) return;
@@ -677,6 +803,16 @@ __global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_seg_scan_jl_kernel
                                                                                  uint64_t tiles_done, int last) {
   wire_tokj_scan_body(maps, tiles, entry, [&] { return fresh ? (uint64_t)head : state[FBM_WIRE_SEG_CARRY]; },
                       [&](uint64_t st) { wire_seg_note(state, st, (st >> 16) < n ? (st >> 16) : n, fed, tiles_done, last); });
+}
+
+// (FBM_WIRE_JLW: wire_jlwtok_scan_kernel's body in the same way; LDS 67584 bytes)
+__global__ void __launch_bounds__(FBM_WIRE_SCAN_THREADS) wire_jlwseg_scan_kernel(const uint32_t* __restrict__ maps, uint64_t tiles,
+                                                                                 uint32_t head, int fresh, uint64_t n,
+                                                                                 uint64_t* __restrict__ entry,
+                                                                                 uint64_t* __restrict__ state, uint64_t fed,
+                                                                                 uint64_t tiles_done, int last) {
+  wire_jlwtok_scan_body(maps, tiles, entry, [&] { return fresh ? (uint64_t)head : state[FBM_WIRE_SEG_CARRY]; },
+                        [&](uint64_t st) { wire_seg_note(state, st, (st >> 16) < n ? (st >> 16) : n, fed, tiles_done, last); });
 }
 
 static int wire_grid(uint64_t blocks, const char* what, unsigned& g) {
@@ -837,6 +973,28 @@ int launch_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t bas
   return check_launch("wire_tokj_emit_kernel");
 }
 
+uint64_t wire_tokenize_jlw_workspace(uint64_t span_len) {
+  const uint64_t tiles = (span_len + 3 + FBM_WIRE_TOK_TILE - 1) / FBM_WIRE_TOK_TILE;  // whatever the alignment
+  return (wire_jlwtok_workspace_of(tiles) + 255) / 256 * 256 + 256;
+}
+
+int launch_wire_tokenize_jlw(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                             uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace, hipStream_t s) {
+  const wire_tok_cut c = wire_tok_cut_of(span, span_len, first - base);
+  unsigned g = 0;
+  int rc = wire_grid((c.tiles + FBM_WIRE_TOK_WAVES - 1) / FBM_WIRE_TOK_WAVES, "fbm_wire_tokenize_jlw", g);
+  if (rc) return rc;
+  uint64_t* entry = reinterpret_cast<uint64_t*>(workspace);
+  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(c.tiles));
+  hipLaunchKernelGGL(wire_jlwtok_maps_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, c.origin, c.tiles, maps);
+  if ((rc = check_launch("wire_jlwtok_maps_kernel"))) return rc;
+  hipLaunchKernelGGL(wire_jlwtok_scan_kernel, dim3(1), dim3(FBM_WIRE_SCAN_THREADS), 0, s, maps, c.tiles, c.head, n, entry, result);
+  if ((rc = check_launch("wire_jlwtok_scan_kernel"))) return rc;
+  hipLaunchKernelGGL(wire_jlwtok_emit_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, span_len, c.origin, c.tiles, entry, base,
+                     n, ckpt, n_ckpt, result);
+  return check_launch("wire_jlwtok_emit_kernel");
+}
+
 int launch_wire_stream_begin(int scheme, uint64_t first, uint64_t n, uint64_t* state, hipStream_t s) {
   hipLaunchKernelGGL(wire_seg_begin_kernel, dim3(1), dim3(64), 0, s, state, first, n, (uint64_t)scheme);
   return check_launch("wire_seg_begin_kernel");
@@ -854,6 +1012,16 @@ int launch_wire_stream_feed(int scheme, const uint8_t* span, uint64_t base, uint
   uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(tiles));
   uint64_t* result = state + FBM_WIRE_SEG_RESULT;
   const int fresh = p.lo == 0;
+  if (scheme == FBM_WIRE_JLW) {
+    hipLaunchKernelGGL(wire_jlwtok_maps_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, avail, p.origin, tiles, maps);
+    if ((rc = check_launch("wire_jlwtok_maps_kernel"))) return rc;
+    hipLaunchKernelGGL(wire_jlwseg_scan_kernel, dim3(1), dim3(FBM_WIRE_SCAN_THREADS), 0, s, maps, tiles, p.head, fresh, n, entry,
+                       state, avail, p.hi, last);
+    if ((rc = check_launch("wire_jlwseg_scan_kernel"))) return rc;
+    hipLaunchKernelGGL(wire_jlwtok_emit_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, avail, p.origin, tiles, entry, base, n,
+                       ckpt, n_ckpt, result);
+    return check_launch("wire_jlwtok_emit_kernel");
+  }
   if (scheme == FBM_WIRE_JL) {
     hipLaunchKernelGGL(wire_tokj_maps_kernel, dim3(g), dim3(FBM_WIRE_BLOCK), 0, s, span, avail, p.origin, tiles, maps);
     if ((rc = check_launch("wire_tokj_maps_kernel"))) return rc;
@@ -962,6 +1130,11 @@ void host_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t bas
 void host_wire_tokenize_jl(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
                            uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
   wire_tokenize_jl_host(span, span_len, base, first, n, ckpt, n_ckpt, result, workspace);
+}
+
+void host_wire_tokenize_jlw(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                            uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  wire_tokenize_jlw_host(span, span_len, base, first, n, ckpt, n_ckpt, result, workspace);
 }
 
 }  // namespace fbm

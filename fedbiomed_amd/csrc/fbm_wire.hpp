@@ -604,12 +604,170 @@ inline void wire_tokenize_jl_host(const uint8_t* span, uint64_t span_len, uint64
   wire_seg_host_jl(span, span_len, base, n, c.origin, c.tiles, c.head, ckpt, n_ckpt, result, workspace);
 }
 
+// ---- tokenize (JLW): the same for the wide family's items (values below 2^4096) ---------------------------------
+// The JL tokenizer's design over the same tiles and the same 24 deciding bytes, with the reach of a 536-byte item: an
+// entry or exit offset lies below 536 and takes 10 bits, up to 27 prefix matches (20 bytes apart) stand in the reach,
+// so a map is FBM_WIRE_JLWTOK_SLOTS = 32 packed words,
+//   entry offset | exit offset << 10 | items << 20      (an unused slot: all ones; a dead exit: FBM_WIRE_JLWTOK_DEAD)
+// The running state keeps its form, items << 16 | offset (offset FBM_WIRE_TOKJ_GONE: dead), and so do the staged tile
+// (FBM_WIRE_TOKJ_WORDS), the items that start in one tile at most (FBM_WIRE_TOKJ_ITEMS) and the workspace's layout.
+#define FBM_WIRE_JLWTOK_REACH 536   // = FBM_WIRE_JLW_ITEM_MAX: entry and exit offsets lie below
+#define FBM_WIRE_JLWTOK_SLOTS 32    // words of a tile's map (27 entries at most)
+#define FBM_WIRE_JLWTOK_DEAD 0x3ffu // a map entry's exit: the chain ended in the tile
+static_assert(FBM_WIRE_TOK_TILE >= FBM_WIRE_JLWTOK_REACH && FBM_WIRE_JLWTOK_REACH == FBM_WIRE_JLW_ITEM_MAX, "a chain skips no tile");
+static_assert(FBM_WIRE_TOKJ_ITEMS < 4096 && FBM_WIRE_JLWTOK_REACH < (int)FBM_WIRE_JLWTOK_DEAD && FBM_WIRE_JLWTOK_DEAD < 1024,
+              "a map entry's fields: 10, 10 and 12 bits");
+static_assert((FBM_WIRE_JLWTOK_REACH + 19) / 20 <= FBM_WIRE_JLWTOK_SLOTS, "prefix matches are 20 bytes apart");
+static_assert(FBM_WIRE_JLWTOK_REACH < (int)FBM_WIRE_TOKJ_GONE, "a state's offset");
+
+// wire_tokj_step for a value of up to 513 bytes: what fbm_wire_item accepts with max_vlen = FBM_WIRE_JLW_MAX_VLEN
+FBM_HD uint32_t wire_jlwtok_step(const uint32_t* w, uint32_t off, int64_t left, uint32_t* L) {
+  if (!wire_tokj_prefix(w, off)) return 0;
+  const uint32_t h = wire_tokj_u32(w, off + 20);  // c4 L v0 .. / c5 Lhi Llo v0
+  const uint32_t b = h & 0xffu;
+  uint32_t len, hdr, v0;
+  if (b == 0xc4u)
+    len = (h >> 8) & 0xffu, hdr = 22, v0 = (h >> 16) & 0xffu;
+  else if (b == 0xc5u)
+    len = ((h >> 8) & 0xffu) << 8 | ((h >> 16) & 0xffu), hdr = 23, v0 = h >> 24;
+  else
+    return 0;
+  if (len < 1 || len > FBM_WIRE_JLW_VLEN_MAX || (int64_t)(hdr + len) > left) return 0;
+  if (v0 >= 0x80u || (len == FBM_WIRE_JLW_VLEN_MAX && v0 != 0)) return 0;  // a negative value, or one of 2^4096 or more
+  *L = len;
+  return hdr + len;
+}
+// (wire_tokj_chain)
+FBM_HD uint32_t wire_jlwtok_chain(const uint32_t* w, uint32_t e, int64_t left, uint32_t* items) {
+  uint32_t off = e, c = 0, L = 0;
+  while (off < FBM_WIRE_TOK_TILE) {
+    const uint32_t s = wire_jlwtok_step(w, off, left - (int64_t)off, &L);
+    if (s == 0) {
+      *items = c;
+      return FBM_WIRE_JLWTOK_DEAD;
+    }
+    off += s, ++c;
+  }
+  *items = c;
+  return off - FBM_WIRE_TOK_TILE;
+}
+FBM_HD uint32_t wire_jlwtok_entry(uint32_t e, uint32_t exit, uint32_t items) { return e | exit << 10 | items << 20; }
+// the slot of a map (FBM_WIRE_JLWTOK_SLOTS words) whose entry offset is `off`, or -1 (an unused slot's is 1023: never one)
+FBM_HD int wire_jlwtok_find(const uint32_t* map, uint64_t off) {
+  int hit = -1;
+#pragma unroll
+  for (int k = 0; k < FBM_WIRE_JLWTOK_SLOTS; ++k) hit = (map[k] & 0x3ffu) == off ? k : hit;  // (entries differ: one hit at most)
+  return hit;
+}
+// a state stepped through one map
+FBM_HD uint64_t wire_jlwtok_apply(uint64_t state, const uint32_t* map) {
+  const uint64_t off = state & 0xffffull;
+  if (off == FBM_WIRE_TOKJ_GONE) return state;
+  const int k = wire_jlwtok_find(map, off);
+  if (k < 0) return state | FBM_WIRE_TOKJ_GONE;
+  const uint32_t m = map[k], exit = (m >> 10) & 0x3ffu;
+  return ((state >> 16) + (m >> 20)) << 16 | (exit == FBM_WIRE_JLWTOK_DEAD ? FBM_WIRE_TOKJ_GONE : (uint64_t)exit);
+}
+// a state stepped through a run of tiles whose composite from each of its first map's entries is comp[]
+FBM_HD uint64_t wire_jlwtok_apply_run(uint64_t state, const uint32_t* first_map, const uint64_t* comp, int stride) {
+  const uint64_t off = state & 0xffffull;
+  if (off == FBM_WIRE_TOKJ_GONE) return state;
+  const int k = wire_jlwtok_find(first_map, off);
+  if (k < 0) return state | FBM_WIRE_TOKJ_GONE;
+  const uint64_t c = comp[k * stride];
+  return ((state >> 16) + (c >> 16)) << 16 | (c & 0xffffull);
+}
+// (wire_tokj_emit_walk)
+FBM_HD uint32_t wire_jlwtok_emit_walk(const uint32_t* w, uint64_t state, int64_t left, int64_t abs0, uint64_t n, uint64_t* out,
+                                      int* end_off) {
+  const uint64_t k0 = state >> 16;
+  uint32_t off = (uint32_t)(state & 0xffffull), c = 0, L = 0;
+  *end_off = -1;
+  if (off == (uint32_t)FBM_WIRE_TOKJ_GONE) return 0;
+  while (off < FBM_WIRE_TOK_TILE && c < FBM_WIRE_TOKJ_ITEMS && k0 + c < n) {
+    const uint32_t s = wire_jlwtok_step(w, off, left - (int64_t)off, &L);
+    if (s == 0) break;
+    out[c] = (uint64_t)(abs0 + (int64_t)(off + s - L)) << 16 | L;
+    off += s;
+    if (k0 + c == n - 1) *end_off = (int)off;
+    ++c;
+  }
+  return c;
+}
+
+// workspace: every tile's entry state (u64 each, rounded up to 256 bytes), then every tile's map
+inline uint64_t wire_jlwtok_workspace_of(uint64_t tiles) { return wire_tok_maps_at(tiles) + tiles * FBM_WIRE_JLWTOK_SLOTS * 4; }
+
+inline void wire_jlwtok_host_map(const uint32_t* w, int64_t left, uint32_t* map) {
+  int slot = 0;
+  for (int k = 0; k < FBM_WIRE_JLWTOK_SLOTS; ++k) map[k] = ~0u;
+  for (uint32_t e = 0; e < FBM_WIRE_JLWTOK_REACH; ++e)
+    if (wire_tokj_prefix(w, e) && slot < FBM_WIRE_JLWTOK_SLOTS) {
+      uint32_t items = 0;
+      const uint32_t exit = wire_jlwtok_chain(w, e, left, &items);
+      map[slot++] = wire_jlwtok_entry(e, exit, items);
+    }
+}
+
+// fbm_wire_tokenize_jlw's three kernels (fbm_wire.hip) over host buffers, tile by tile and run by run as the kernels
+// cut them, through the same routines (host_wire_tokenize_jlw); as wire_seg_host_jl in every other respect.
+inline uint64_t wire_seg_host_jlw(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t n, int64_t origin,
+                                  uint64_t tiles, uint64_t carry, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result,
+                                  void* workspace) {
+  uint64_t* entry = reinterpret_cast<uint64_t*>(workspace);
+  uint32_t* maps = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + wire_tok_maps_at(tiles));
+  uint32_t w[FBM_WIRE_TOKJ_WORDS];
+  for (uint64_t tile = 0; tile < tiles; ++tile) {  // wire_jlwtok_maps_kernel
+    const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+    wire_tokj_host_stage(span, span_len, tbase, w);
+    wire_jlwtok_host_map(w, (int64_t)span_len - tbase, maps + tile * FBM_WIRE_JLWTOK_SLOTS);
+  }
+  uint64_t st = carry;  // wire_jlwtok_scan_kernel
+  for (int t = 0; t < FBM_WIRE_TOK_SCAN_THREADS; ++t) {
+    uint64_t b0, b1, comp[FBM_WIRE_JLWTOK_SLOTS];
+    wire_tok_run(tiles, t, &b0, &b1);
+    if (b0 == b1) continue;
+    for (int k = 0; k < FBM_WIRE_JLWTOK_SLOTS; ++k) {
+      const uint32_t m = maps[b0 * FBM_WIRE_JLWTOK_SLOTS + k];
+      uint64_t s = m == ~0u ? FBM_WIRE_TOKJ_GONE : (uint64_t)(m & 0x3ffu);
+      for (uint64_t b = b0; b < b1; ++b) s = wire_jlwtok_apply(s, maps + b * FBM_WIRE_JLWTOK_SLOTS);
+      comp[k] = s;
+    }
+    uint64_t in = st;
+    for (uint64_t b = b0; b < b1; ++b) {
+      entry[b] = in;
+      in = wire_jlwtok_apply(in, maps + b * FBM_WIRE_JLWTOK_SLOTS);
+    }
+    st = wire_jlwtok_apply_run(st, maps + b0 * FBM_WIRE_JLWTOK_SLOTS, comp, 1);  // (= in)
+  }
+  result[0] = (st >> 16) < n ? (st >> 16) : n;
+  uint64_t out[FBM_WIRE_TOKJ_ITEMS];
+  for (uint64_t tile = 0; tile < tiles; ++tile) {  // wire_jlwtok_emit_kernel
+    const int64_t tbase = origin + (int64_t)(tile * FBM_WIRE_TOK_TILE);
+    wire_tokj_host_stage(span, span_len, tbase, w);
+    int end = -1;
+    const uint32_t cnt = wire_jlwtok_emit_walk(w, entry[tile], (int64_t)span_len - tbase, (int64_t)base + tbase, n, out, &end);
+    for (uint32_t j = 0; j < cnt; ++j)
+      if ((entry[tile] >> 16) + j < n_ckpt) ckpt[(entry[tile] >> 16) + j] = out[j];
+    if (end >= 0) result[1] = (uint64_t)((int64_t)base + tbase + end);
+  }
+  return st;
+}
+
+inline void wire_tokenize_jlw_host(const uint8_t* span, uint64_t span_len, uint64_t base, uint64_t first, uint64_t n,
+                                   uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace) {
+  const wire_tok_cut c = wire_tok_cut_of(span, span_len, first - base);
+  result[1] = 0;
+  wire_seg_host_jlw(span, span_len, base, n, c.origin, c.tiles, c.head, ckpt, n_ckpt, result, workspace);
+}
+
 // ---- the tokenizers as resumable scans (fbm_wire_stream_begin / fbm_wire_stream_feed) ---------------------------
 // Both tokenizers are a scan over tiles, and a tile's place depends on the span's address, its base and `first` alone,
 // not on the span's length: a span that grows keeps its tiles.  A feed runs the three passes over the tiles that have
 // become final since the last one, the scan entered in the running state the last feed left in the stream's record and
 // leaving its own there.  A tile is final once every item that starts in it lies wholly below avail_len -- the tile's
-// end plus the longest item's reach, FBM_WIRE_NATIVE_MAX - 1 or FBM_WIRE_ITEM_MAX bytes --: then its map, its items'
+// end plus the longest item's reach, FBM_WIRE_NATIVE_MAX - 1, FBM_WIRE_ITEM_MAX or (FBM_WIRE_JLW, the streams that
+// fbm_wire_stream_begin_jlw opens) FBM_WIRE_JLW_ITEM_MAX bytes --: then its map, its items'
 // table words and whether item n - 1 ends inside the span are what the whole span's one call finds.  The last feed
 // takes every tile left, the partial one included, under the span's final length.  The passes write a segment's entry
 // states and maps at the front of the workspace, each feed over the last one's (the stream orders them).
@@ -655,7 +813,7 @@ inline const char* wire_seg_plan_of(const uint64_t* rec, int scheme, const uint8
   if (last) {
     p->hi = c.tiles;
   } else {
-    const int64_t reach = scheme == FBM_WIRE_JL ? FBM_WIRE_ITEM_MAX : FBM_WIRE_NATIVE_MAX - 1;
+    const int64_t reach = scheme == FBM_WIRE_JL ? FBM_WIRE_ITEM_MAX : scheme == FBM_WIRE_JLW ? FBM_WIRE_JLW_ITEM_MAX : FBM_WIRE_NATIVE_MAX - 1;
     const int64_t room = (int64_t)avail - reach - c.origin;
     p->hi = room > 0 ? (uint64_t)room / FBM_WIRE_TOK_TILE : 0;
   }
@@ -679,10 +837,8 @@ inline const char* wire_seg_host_feed(int scheme, const uint8_t* span, uint64_t 
   if (p.hi > p.lo) {
     const uint64_t carry = p.lo == 0 ? (uint64_t)p.head : state[FBM_WIRE_SEG_CARRY];
     const uint64_t n = state[FBM_WIRE_SEG_ITEMS];
-    state[FBM_WIRE_SEG_CARRY] =
-        scheme == FBM_WIRE_JL
-            ? wire_seg_host_jl(span, avail, base, n, p.origin, p.hi - p.lo, carry, ckpt, n_ckpt, state + FBM_WIRE_SEG_RESULT, workspace)
-            : wire_seg_host_lom(span, avail, base, n, p.origin, p.hi - p.lo, carry, ckpt, n_ckpt, state + FBM_WIRE_SEG_RESULT, workspace);
+    const auto run = scheme == FBM_WIRE_JL ? wire_seg_host_jl : scheme == FBM_WIRE_JLW ? wire_seg_host_jlw : wire_seg_host_lom;
+    state[FBM_WIRE_SEG_CARRY] = run(span, avail, base, n, p.origin, p.hi - p.lo, carry, ckpt, n_ckpt, state + FBM_WIRE_SEG_RESULT, workspace);
   }
   wire_seg_fed(state, p, span, base, avail, last);
   return nullptr;

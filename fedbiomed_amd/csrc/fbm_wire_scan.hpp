@@ -23,6 +23,9 @@
 //
 // fbm_wire_scan_jlw is the pass with the map item's bound at L <= 513 (a value < 2^4096) and FBM_WIRE_JLW as the
 // scheme of an array that holds a map item: fbm_wire_scan_out carries both, every other caller leaves the defaults.
+// fbm_wire_scan_deferred_jlw and fbm_wire_scan_prefix_jlw are the deferring and the prefix pass under the same bound:
+// a large array of wide maps is then a candidate for fbm_wire_tokenize_jlw (fbm_wire.hpp, "tokenize (JLW)") and is
+// named and recorded as FBM_WIRE_JLW.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -150,6 +153,8 @@ static inline uint64_t fbm_wire_be(const uint8_t* p, int bytes) {
 // whose first item begins with the whole 20-byte prefix and c4 / c5, and whose items at their smallest (23 bytes
 // each) fit the bytes left, is a candidate too (for fbm_wire_tokenize_jl).  Candidates of both kinds take the
 // message's FBM_WIRE_MAX_DEFERRED slots in order of appearance; a resolved one is recorded under its own scheme.
+// Under fbm_wire_scan_out's wide bound (fbm_wire_scan_deferred_jlw) such a candidate is one for fbm_wire_tokenize_jlw
+// and carries FBM_WIRE_JLW; fbm_wire_scan_prefix_run takes the same two values as arguments.
 struct fbm_wire_defer {
   uint64_t defer_items;  // 0: no all-native array is a candidate
   const uint64_t* resolved;
@@ -240,7 +245,7 @@ static inline int fbm_wire_scan_run(const uint8_t* d, uint64_t len, uint64_t min
         else if (df->defer_items_jl && children >= df->defer_items_jl && children <= body / FBM_WIRE_JL_ITEM_MIN &&
                  memcmp(d + pos + skip, FBM_WIRE_PREFIX, FBM_WIRE_PREFIX_LEN) == 0 &&
                  (d[pos + skip + FBM_WIRE_PREFIX_LEN] == 0xc4 || d[pos + skip + FBM_WIRE_PREFIX_LEN] == 0xc5))
-          cand = FBM_WIRE_JL;  // (children >= 1 and 23 children <= body: the 21 bytes compared lie inside the message)
+          cand = o->map_scheme;  // (children >= 1 and 23 children <= body: the 21 bytes compared lie inside the message)
       }
       if (cand >= 0) {
         const uint64_t k = candidates++;
@@ -310,7 +315,7 @@ gave_up:
 
 // fbm_wire_item over a prefix: the item's byte count, 0 where no further byte makes it an accepted form, -1 where
 // that takes bytes at or past len
-static inline int64_t fbm_wire_item_prefix(const uint8_t* d, uint64_t pos, uint64_t len) {
+static inline int64_t fbm_wire_item_prefix(const uint8_t* d, uint64_t pos, uint64_t len, uint32_t max_vlen = FBM_WIRE_JL_MAX_VLEN) {
   if (pos >= len) return -1;
   const uint64_t left = len - pos;
   const uint8_t b = d[pos];
@@ -334,15 +339,16 @@ static inline int64_t fbm_wire_item_prefix(const uint8_t* d, uint64_t pos, uint6
   } else {
     return 0;
   }
-  if (L < 1 || L > 257) return 0;
+  if (L < 1 || L > max_vlen) return 0;
   if (v >= len) return -1;
-  if (d[v] >= 0x80 || (L == 257 && d[v] != 0)) return 0;
+  if (d[v] >= 0x80 || (L == max_vlen && d[v] != 0)) return 0;
   if (len - v < L) return -1;
   return (int64_t)(v + L - pos);
 }
 
 static inline int fbm_wire_scan_prefix_run(const uint8_t* d, uint64_t len, uint64_t min_items, uint64_t defer_items,
-                                           uint64_t defer_items_jl, fbm_wire_pending2* pending) {
+                                           uint64_t defer_items_jl, fbm_wire_pending2* pending,
+                                           uint32_t max_vlen = FBM_WIRE_JL_MAX_VLEN, int32_t map_scheme = FBM_WIRE_JL) {
   uint64_t stack[FBM_WIRE_MAX_DEPTH];
   int depth = 1;
   uint64_t pos = 0;
@@ -417,7 +423,7 @@ static inline int fbm_wire_scan_prefix_run(const uint8_t* d, uint64_t len, uint6
         const uint64_t have = len - first < FBM_WIRE_PREFIX_LEN ? len - first : FBM_WIRE_PREFIX_LEN;
         if (memcmp(d + first, FBM_WIRE_PREFIX, have) == 0) {
           if (len - first < FBM_WIRE_PREFIX_LEN + 1) return FBM_WIRE_SCAN_MORE;
-          if (d[first + FBM_WIRE_PREFIX_LEN] == 0xc4 || d[first + FBM_WIRE_PREFIX_LEN] == 0xc5) cand = FBM_WIRE_JL;
+          if (d[first + FBM_WIRE_PREFIX_LEN] == 0xc4 || d[first + FBM_WIRE_PREFIX_LEN] == 0xc5) cand = map_scheme;
         }
       }
       if (cand >= 0) {
@@ -427,7 +433,7 @@ static inline int fbm_wire_scan_prefix_run(const uint8_t* d, uint64_t len, uint6
       }
       uint64_t p = first, i = 0;  // fbm_wire_candidate's walk
       for (; i < children; ++i) {
-        const int64_t c = fbm_wire_item_prefix(d, p, len);
+        const int64_t c = fbm_wire_item_prefix(d, p, len, max_vlen);
         if (c < 0) return FBM_WIRE_SCAN_MORE;
         if (c == 0) break;
         p += (uint64_t)c;

@@ -230,6 +230,11 @@ DEVICE_SCAN_MIN_ITEMS = 1 << 16
 # profiles/wire_devscan_jl_ab.jsonl, DESIGN.md 4.2: 0.95 ms against 1.00 here, 2.8 against 4.0 at 2^17, 8.8 against
 # 14.6 at 2^19).
 DEVICE_SCAN_JL_MIN_ITEMS = 1 << 14
+# The same under ``jl_limbs=128`` (wide maps of up to 536 bytes; fbm_wire_tokenize_jlw): the smallest swept count from
+# which on the device route's slowest take lay below the host walk's fastest (tools/jl_wide_sweep.py --take,
+# profiles/jl_wide_wire.jsonl, DESIGN.md 4.2 "Wide items": 1.19 ms against 1.11 at 31 250, 5.07 against 5.26 here, 10.6
+# against 13.4 at 333 334).  The host scanner steps over a wide item as fast as over a narrow one, so it holds out longer.
+DEVICE_SCAN_JLW_MIN_ITEMS = 1 << 17
 _LAST: Dict[str, Any] = {}  # the last call's phases in seconds (tools/wire_ref_ab.py)
 _PHASE_TIMING = False  # tools/wire_ref_ab.py sets it: the resident upload then synchronises to time its "h2d"
 
@@ -436,23 +441,35 @@ def _upload_arrays(data: bytes, arrays: list) -> list:
     return handles
 
 
-def _scan_resident(data: bytes, min_items: int, defer_items: int, defer_jl_items: int = 0):
+def _scan_resident(data: bytes, min_items: int, defer_items: int, defer_jl_items: int = 0, jl_limbs: int = 64):
     """The scan of `loads_reference(resident=True)` (the same seam): `_device.wire_scan_resident`'s (arrays, handles)."""
     from . import _device as D
 
     timing: Dict[str, float] = {}
     out = D.wire_scan_resident(data, min_items, defer_items, timing, _STATS, sync_phases=_PHASE_TIMING,
-                               defer_jl_items=defer_jl_items)
+                               defer_jl_items=defer_jl_items, jl_limbs=jl_limbs)
     _LAST.update(timing)
     return out
 
 
 # ---- a stock peer's reply taken onto the device chunk by chunk as it arrives -------------------------------------
-def _scan_prefix(data: bytes, min_items: int, defer_items: int, defer_jl_items: int):
+def _scan_prefix(data: bytes, min_items: int, defer_items: int, defer_jl_items: int, jl_limbs: int = 64):
     """The host's prefix scan of `StreamAssembler` (a seam like the others): `_device.wire_scan_prefix`."""
     from . import _device as D
 
-    return D.wire_scan_prefix(data, min_items, defer_items, defer_jl_items)
+    return D.wire_scan_prefix(data, min_items, defer_items, defer_jl_items, jl_limbs)
+
+
+def _jl_min_items(value: Optional[int], jl_limbs: int) -> int:
+    """`device_scan_jl_min_items` with its default, which is the narrow or the wide tokenizer's."""
+    if value is not None:
+        return int(value)
+    return DEVICE_SCAN_JL_MIN_ITEMS if jl_limbs == 64 else DEVICE_SCAN_JLW_MIN_ITEMS
+
+
+def _stream_params(object_hook, min_items: int, dmin: int, jmin: int, jl_limbs: int) -> tuple:
+    """What a `loads_reference` call must share with the `StreamAssembler` whose message it reads."""
+    return (object_hook, int(min_items), dmin, jmin) + ((jl_limbs,) if jl_limbs != 64 else ())
 
 
 def _open_stream(scheme: str, begin: int, first: int, n_items: int, cap: int, ctx: dict):
@@ -521,7 +538,10 @@ class StreamAssembler:
     map, ``max(min_items, device_scan_jl_min_items)`` of those maps (the arguments and defaults are
     `loads_reference`'s; they are needed when the first chunk arrives, and a `loads_reference` call with other
     values reads ``bytes(msg)``).  Until one is found no device call is made; a message of one chunk, one without such
-    an array in its first four chunks and a malformed one are kept as `ChunkAssembler` keeps them.  Once it is known
+    an array in its first four chunks and a malformed one are kept as `ChunkAssembler` keeps them.  ``jl_limbs=128``
+    (with `loads_reference`'s meaning, and one of the arguments a later call must share): the maps are the wide ones
+    of up to 513 value bytes, found by fbm_wire_scan_prefix_jlw and tokenized by fbm_wire_stream_feed_jlw, the default
+    of `device_scan_jl_min_items` is `DEVICE_SCAN_JLW_MIN_ITEMS`, and the array comes back as a "jlw" update.  Once it is known
     a device block takes the message from the array's header on -- ``size * len(first chunk)`` bytes bound it: the
     reference's sender cuts every chunk but the last to ``MAX_MESSAGE_BYTES_LENGTH`` --, the kept chunks and then
     every further one go up through a pinned staging ring on a stream the assembler owns, and after each upload the
@@ -534,11 +554,13 @@ class StreamAssembler:
     message itself is never joined here.  What ends streaming is logged under this module's logger.)"""
 
     def __init__(self, object_hook=None, min_items: int = 1024, device_scan_min_items: Optional[int] = None,
-                 device_scan_jl_min_items: Optional[int] = None, max_block_bytes: int = 1 << 30) -> None:
-        self._max_block = int(max_block_bytes)
+                 device_scan_jl_min_items: Optional[int] = None, max_block_bytes: int = 1 << 30, jl_limbs: int = 64) -> None:
+        if jl_limbs not in (64, 128):
+            raise ValueError("jl_limbs must be 64 or 128")
+        self._max_block, self._limbs = int(max_block_bytes), jl_limbs
         dmin = DEVICE_SCAN_MIN_ITEMS if device_scan_min_items is None else int(device_scan_min_items)
-        jmin = DEVICE_SCAN_JL_MIN_ITEMS if device_scan_jl_min_items is None else int(device_scan_jl_min_items)
-        self._params = (object_hook, int(min_items), dmin, jmin)
+        jmin = _jl_min_items(device_scan_jl_min_items, jl_limbs)
+        self._params = _stream_params(object_hook, min_items, dmin, jmin, jl_limbs)
         self._jl = _hook_reads_ints(object_hook)
         self._ctx: dict = {}  # the device side's stream and staging ring, kept from message to message
         self._reset()
@@ -550,7 +572,7 @@ class StreamAssembler:
 
     def _look(self, size: int) -> None:
         """After one of the first four chunks: the prefix scan, and where it finds the array, the device block."""
-        _, min_items, dmin, jmin = self._params
+        _, min_items, dmin, jmin = self._params[:4]
         if len(self._parts) == 1:
             prefix = self._parts[0]
         else:  # (rare: the array begins behind the first chunk.  Each chunk is copied once into the growing prefix)
@@ -558,7 +580,10 @@ class StreamAssembler:
                 self._prefix = bytearray(self._parts[0])
             self._prefix += self._parts[-1]
             prefix = self._prefix
-        kind, cand = _scan_prefix(prefix, min_items, max(dmin, 1), max(jmin, 1) if self._jl else 0)
+        if self._limbs == 64:
+            kind, cand = _scan_prefix(prefix, min_items, max(dmin, 1), max(jmin, 1) if self._jl else 0)
+        else:
+            kind, cand = _scan_prefix(prefix, min_items, max(dmin, 1), max(jmin, 1) if self._jl else 0, self._limbs)
         if kind != "more" or len(self._parts) >= 4:
             self._prefix = None
         if kind == "more":
@@ -569,7 +594,7 @@ class StreamAssembler:
         begin, first, n_items, scheme = cand
         cap = size * len(self._parts[0])
         # (deferred2's bound, which the prefix cannot see: the items at their smallest fit what is still to come)
-        if n_items * (23 if scheme == "jl" else 1) > cap - first:
+        if n_items * (1 if scheme == "lom" else 23) > cap - first:
             return
         if cap - begin > self._max_block:
             return
@@ -615,7 +640,8 @@ class StreamAssembler:
 _NOT_STREAMED = object()
 
 
-def _loads_streamed(msg: StreamedMessage, object_hook, min_items: int, resident: bool, dmin: int, jmin: int):
+def _loads_streamed(msg: StreamedMessage, object_hook, min_items: int, resident: bool, dmin: int, jmin: int,
+                    jl_limbs: int = 64):
     """`loads_reference` of a streamed message without joining it, or _NOT_STREAMED where the call is the one on
     ``bytes(msg)``: read without ``resident``, with other arguments than the assembler's, refused by the tokenizer, or
     with a reduced message that does not unpack."""
@@ -625,7 +651,7 @@ def _loads_streamed(msg: StreamedMessage, object_hook, min_items: int, resident:
 
     if not msg._began:
         return _NOT_STREAMED
-    if not resident or not msg.streamed or msg._params != (object_hook, int(min_items), dmin, jmin):
+    if not resident or not msg.streamed or msg._params != _stream_params(object_hook, min_items, dmin, jmin, jl_limbs):
         msg._fell_back()
         return _NOT_STREAMED
     begin, first, n_items, scheme = msg._cand
@@ -647,7 +673,7 @@ def _loads_streamed(msg: StreamedMessage, object_hook, min_items: int, resident:
 
     before = dict(_STATS)
     try:
-        return _loads_reference(reduced, hook, min_items, True, dmin, jmin, count_plain=False)
+        return _loads_reference(reduced, hook, min_items, True, dmin, jmin, count_plain=False, jl_limbs=jl_limbs)
     except Exception as err:  # what msgpack raises for the reduced message it raises for the whole one: that call decides
         _log.info("loads_reference: the streamed message did not unpack (%s: %s); reading its joined bytes", type(err).__name__, err)
         _STATS.update(before)
@@ -687,25 +713,22 @@ def loads_reference(data, object_hook=None, min_items: int = 1024, resident: boo
 
     ``jl_limbs=128`` (a deployment whose biprime has 1025 to 2048 bits: ciphertexts below 2^4096): the scan is
     fbm_wire_scan_jlw, which takes the big-int map with up to 513 value bytes, and an array that holds one comes back
-    as an `EncryptedParams` / `ResidentUpdate` of scheme "jlw" (packed ``[n, 128]``).  Every array is then walked by
-    the host scanner: the device tokenizers keep their 2^2048 domain and are not asked, and a `StreamedMessage` is
-    read from its joined bytes.  With the default 64 nothing changes: a value of 2^2048 or more leaves its array to
-    msgpack."""
+    as an `EncryptedParams` / `ResidentUpdate` of scheme "jlw" (packed ``[n, 128]``).  With ``resident=True`` an array
+    of at least `device_scan_jl_min_items` of those maps (None: `DEVICE_SCAN_JLW_MIN_ITEMS`) goes through the wide
+    tokenizer (fbm_wire_tokenize_jlw), counted under the same keys "device_scan_jl" / "device_scan_jl_refused"; an
+    all-native array takes the LOM tokenizer as with 64; and a `StreamedMessage` of a ``StreamAssembler(jl_limbs=128)``
+    is read without joining its chunks, under the rules above.  With the default 64 nothing changes: a value of
+    2^2048 or more leaves its array to msgpack."""
     if jl_limbs not in (64, 128):
         raise ValueError("jl_limbs must be 64 or 128")
     dmin = DEVICE_SCAN_MIN_ITEMS if device_scan_min_items is None else int(device_scan_min_items)
-    jmin = DEVICE_SCAN_JL_MIN_ITEMS if device_scan_jl_min_items is None else int(device_scan_jl_min_items)
-    if jl_limbs == 128:
-        if isinstance(data, StreamedMessage):
-            data._fell_back()
-            data = bytes(data)
-        return _loads_reference(data, object_hook, min_items, resident, dmin, jmin, jl_limbs=128)
+    jmin = _jl_min_items(device_scan_jl_min_items, jl_limbs)
     if isinstance(data, StreamedMessage):
-        out = _loads_streamed(data, object_hook, min_items, resident, dmin, jmin)
+        out = _loads_streamed(data, object_hook, min_items, resident, dmin, jmin, jl_limbs)
         if out is not _NOT_STREAMED:
             return out
         data = bytes(data)
-    return _loads_reference(data, object_hook, min_items, resident, dmin, jmin)
+    return _loads_reference(data, object_hook, min_items, resident, dmin, jmin, jl_limbs=jl_limbs)
 
 
 def _loads_reference(data: bytes, object_hook, min_items: int, resident: bool, dmin: int, jmin: int,
@@ -720,10 +743,12 @@ def _loads_reference(data: bytes, object_hook, min_items: int, resident: bool, d
 
     _LAST.clear()
     held: Dict[int, Any] = {}  # the arrays the device tokenized: index -> handle
-    if resident and jl_limbs == 64:
+    if resident:
         # (an array of maps is this library's only under a hook that reads them: otherwise it never goes up)
-        arrays, held = _scan_resident(data, min_items, max(dmin, 1), max(jmin, 1) if _hook_reads_ints(object_hook) else 0)
-    else:  # (jl_limbs == 128: the host scanner walks every array, the tokenizers' domain ends at 2^2048)
+        djl = max(jmin, 1) if _hook_reads_ints(object_hook) else 0
+        arrays, held = _scan_resident(data, min_items, max(dmin, 1), djl) if jl_limbs == 64 else \
+            _scan_resident(data, min_items, max(dmin, 1), djl, jl_limbs)
+    else:
         t0 = time.perf_counter()
         arrays = D.wire_scan(data, min_items) if jl_limbs == 64 else D.wire_scan(data, min_items, jl_limbs)
         _LAST["scan"] = time.perf_counter() - t0

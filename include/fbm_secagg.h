@@ -704,6 +704,46 @@ int fbm_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, ui
 int fbm_wire_scan_prefix(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
                          uint64_t defer_items_jl, fbm_wire_pending2* pending);
 
+/* ---- the wide family's arrays tokenized on the device, at once or chunk by chunk (additions under ABI 7) ----------
+ * The entry points above keep their two schemes and refuse FBM_WIRE_JLW like any unknown one; these are their twins
+ * for items of the wide map form -- the 20-byte prefix, c4 L or c5 BE16 L (minimal or not), 1 <= L <= 513, a first
+ * value byte < 0x80 that is 0 where L == 513: what fbm_wire_scan_jlw accepts --, 23..536 bytes each.  The design is
+ * fbm_wire_tokenize_jl's over the same 4 KiB tiles: a tile's transfer map takes an entry offset < 536 to an exit
+ * offset < 536 and the items between, at most 27 live entries in 32 words; the maps are scanned from the entry
+ * `first` gives; a last pass walks each tile from its now known entry.
+ *
+ * fbm_wire_tokenize_jlw: fbm_wire_tokenize_jl's arguments, checks, result words and refusals, with the item form
+ * above and a workspace of fbm_wire_tokenize_jlw_workspace(span_len) bytes.  ckpt[i] is word for word the table
+ * fbm_wire_scan_jlw writes for the same array (byte count 1..513).
+ *
+ * fbm_wire_scan_deferred_jlw: fbm_wire_scan_deferred2's pass under fbm_wire_scan_jlw's rules -- an array of at least
+ * max(min_items, defer_items_jlw) items whose first item begins with the prefix and c4 / c5, and with 23 n_items <= the
+ * bytes left, is a candidate for fbm_wire_tokenize_jlw; pending->scheme and a resolved array's scheme are then
+ * FBM_WIRE_JLW, and an array walked on the host that holds a map item is FBM_WIRE_JLW as well.  All-native candidates
+ * (defer_items_lom) go to fbm_wire_tokenize_lom as before.  fbm_wire_scan_prefix_jlw: fbm_wire_scan_prefix in the
+ * same way.
+ *
+ * fbm_wire_stream_begin_jlw / fbm_wire_stream_feed_jlw: fbm_wire_stream_begin / _feed for one array of wide maps (the
+ * scheme argument is gone: the narrow functions refuse FBM_WIRE_JLW).  The record's running state is the entry offset
+ * below 536 and the items so far; a feed that is not the last runs the tiles whose end lies at least 536 bytes below
+ * avail_len; workspace: fbm_wire_stream_jlw_workspace(cap_len) bytes; n_ckpt = n_items.  Behind the last feed state[3],
+ * state[4] and ckpt are word for word what fbm_wire_tokenize_jlw writes for the whole span in one call.  Every other
+ * rule, bound and error as the narrow stream's. */
+uint64_t fbm_wire_tokenize_jlw_workspace(uint64_t span_len);
+int fbm_wire_tokenize_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
+                          uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace,
+                          void* stream);
+int fbm_wire_scan_deferred_jlw(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
+                               uint64_t defer_items_jlw, const uint64_t* resolved, uint64_t n_resolved,
+                               fbm_wire_array* arrays, uint64_t arrays_cap, uint64_t* n_arrays, uint64_t* ckpt,
+                               uint64_t ckpt_cap, uint64_t* n_ckpt, fbm_wire_pending2* pending);
+int fbm_wire_scan_prefix_jlw(const uint8_t* data, uint64_t len, uint64_t min_items, uint64_t defer_items_lom,
+                             uint64_t defer_items_jlw, fbm_wire_pending2* pending);
+uint64_t fbm_wire_stream_jlw_workspace(uint64_t cap_len);
+int fbm_wire_stream_begin_jlw(uint64_t first, uint64_t n_items, uint64_t* state, void* stream);
+int fbm_wire_stream_feed_jlw(const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last, uint64_t* ckpt,
+                             uint64_t n_ckpt, uint64_t* state, void* workspace, void* stream);
+
 /* Drops the library's host-side caches: the short path's constant C per (N, |key|) -- kept under a
  * SHA-256 digest of (N, |key|), never the key itself, and zeroed here and on eviction -- and the
  * per-biprime public parameters.  The reference keeps nothing between calls (a fresh

@@ -161,6 +161,13 @@ int fbm_test_wire_tokenize_lom(const uint8_t* span, uint64_t span_len, uint64_t 
 int fbm_test_wire_stream_begin(int scheme, uint64_t first, uint64_t n_items, uint64_t* state);
 int fbm_test_wire_stream_feed(int scheme, const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last,
                               uint64_t* ckpt, uint64_t n_ckpt, uint64_t* state, void* workspace);
+/* fbm_wire_tokenize_jlw and fbm_wire_stream_begin_jlw / _feed_jlw over HOST buffers in the same way
+ * (host_wire_tokenize_jlw; wire_seg_host_feed with FBM_WIRE_JLW), same arguments and argument errors. */
+int fbm_test_wire_tokenize_jlw(const uint8_t* span, uint64_t span_len, uint64_t span_base, uint64_t first,
+                               uint64_t n_items, uint64_t* ckpt, uint64_t n_ckpt, uint64_t* result, void* workspace);
+int fbm_test_wire_stream_begin_jlw(uint64_t first, uint64_t n_items, uint64_t* state);
+int fbm_test_wire_stream_feed_jlw(const uint8_t* span, uint64_t span_base, uint64_t avail_len, int last, uint64_t* ckpt,
+                                  uint64_t n_ckpt, uint64_t* state, void* workspace);
 
 /* The LOM aggregate kernel fbm_lom_aggregate launches for n_parties rows of n elements at y (device
  * pointer; its alignment picks the form), as rocprofv3 names it without the "fbm::" namespace, e.g.

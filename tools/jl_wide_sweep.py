@@ -24,6 +24,15 @@ on the host msgpack's unpackb with the reference's hook and packb of the same me
 run lies below the fastest split one:
 
     python tools/jl_wide_sweep.py --wire --out profiles/jl_wide_wire.jsonl
+
+--take ("wide items"): at each of --counts full-width items, (a) `wire.loads_reference(resident=True,
+jl_limbs=128)` of one reply through the wide device tokenizer (device_scan_jl_min_items=1) against the host scanner's
+walk (the threshold past the array's size), and (b) the last chunk to the `ResidentUpdate` through
+`StreamAssembler(jl_limbs=128)` against `ChunkAssembler` + the host walk, chunks of 4 MB paced 1.3 ms apart as
+tools/wire_ref_ab.py --stream paces them, with the host time inside all `add` calls.  One session, one warm-up of
+every leg, the legs alternating within a repetition; the rows are appended to --out:
+
+    python tools/jl_wide_sweep.py --take --counts 4096 16384 31250 131072 333334 --out profiles/jl_wide_wire.jsonl
 """
 import argparse
 import json
@@ -47,6 +56,7 @@ def main():
     ap.add_argument("--seal", action="store_true")
     ap.add_argument("--wire", action="store_true")
     ap.add_argument("--items", type=int, default=31250)
+    ap.add_argument("--take", action="store_true")
     args = ap.parse_args()
     import torch
 
@@ -86,6 +96,57 @@ def main():
                      "slowest_prepared_over_fastest_unprepared": max(ms["encrypt_tensor_factor"]) / min(ms["encrypt_tensor"]),
                      "fold_bytes": 512 * 3 * n_ct, "fold_gb_per_s": 512 * 3 * n_ct / min(ms["jlw_fold_k1"]) / 1e6})
         return emit(rows, args.out)
+    if args.take:  # DESIGN 4.2, "wide items": the reply's way onto the device, at once and chunk by chunk
+        from fedbiomed_amd import wire
+
+        def int_hook(o):  # the reference Serializer's rule (serializer.py:140-149)
+            return int.from_bytes(o["value"], "big", signed=True) if o.get("__type__") == "int" else o
+
+        chunk, gap = 4 << 20, 1.3e-3
+        for items in args.counts:
+            r = torch.randint(-2**31, 2**31, (items, 128), dtype=torch.int64, device=dev).to(torch.int32)
+            r[:, 127] |= -2**31  # full width: every item 536 bytes
+            data = wire.reference_bytes(r)
+            del r
+            chunks = [data[i:i + chunk] for i in range(0, len(data), chunk)]
+            kw = dict(object_hook=int_hook, min_items=1, resident=True, jl_limbs=128)
+
+            def take(jmin, key):
+                wire.reference_stats(reset=True)
+                up = wire.loads_reference(data, device_scan_jl_min_items=jmin, **kw)
+                assert up.n_items == items and wire.reference_stats()[key] == 1
+
+            def receive(asm, jmin, rec):
+                t_add, start = 0.0, time.perf_counter()
+                for i, c in enumerate(chunks, 1):  # chunk i arrives at start + (i - 1) * gap whatever `add` cost
+                    while time.perf_counter() < start + (i - 1) * gap:
+                        pass
+                    t0 = time.perf_counter()
+                    msg = asm.add(c, len(chunks), i)
+                    t_add += time.perf_counter() - t0
+                up = wire.loads_reference(msg, device_scan_jl_min_items=jmin, **kw)
+                torch.cuda.synchronize(dev)
+                rec.update(ms=(time.perf_counter() - t0) * 1e3, add_total_ms=t_add * 1e3, chunks=len(chunks))
+                assert up.n_items == items and getattr(msg, "joins", 1) == (0 if jmin == 1 else 1)
+
+            sa = wire.StreamAssembler(object_hook=int_hook, min_items=1, device_scan_jl_min_items=1, jl_limbs=128)
+            legs = [("take_device_route", lambda rec: rec.update(ms=timed(lambda: take(1, "device_scan_jl")))),
+                    ("take_host_walk", lambda rec: rec.update(ms=timed(lambda: take(items + 1, "resident")))),
+                    ("stream_last_chunk", lambda rec: receive(sa, 1, rec)),
+                    ("joined_last_chunk", lambda rec: receive(wire.ChunkAssembler(), items + 1, rec))]
+            for what, fn in legs:
+                if len(chunks) > 1 or "take" in what:  # (a message of one chunk is not streamed)
+                    fn({})
+            for rep in range(args.reps):
+                for what, fn in legs:
+                    if len(chunks) > 1 or "take" in what:
+                        rows.append({"what": what, "items": items, "message_bytes": len(data), "rep": rep})
+                        fn(rows[-1])
+            ms = {w: [x["ms"] for x in rows if x["what"] == w and x["items"] == items] for w, _ in legs}
+            rows.append({"what": "take_summary", "items": items,
+                         "device_route_wins": max(ms["take_device_route"]) < min(ms["take_host_walk"]),
+                         "stream_wins": bool(ms["stream_last_chunk"]) and max(ms["stream_last_chunk"]) < min(ms["joined_last_chunk"])})
+        return emit(rows, args.out, "a")
     if args.wire:  # DESIGN 4.2, "wide items": a stock peer's reply of --items full-width ciphertexts
         import msgpack
 
@@ -163,8 +224,8 @@ def main():
     emit(rows, args.out)
 
 
-def emit(rows, out):
-    with open(out, "w") as f:
+def emit(rows, out, mode="w"):
+    with open(out, mode) as f:
         for r in rows:
             f.write(json.dumps(r) + "\n")
             print(json.dumps(r))
